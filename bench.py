@@ -28,16 +28,29 @@ time outside the timed region.  `--rehearse-world W` runs, in one process on
 one GPU, exactly the shard rank 0 of a W-rank run evaluates (the per-rank
 kernel and fixed per-step host cost at that shard size).
 
+A plain run does only what `value` needs: it sets up, warms up, times the
+steps, writes the last step's outputs if `--dump-outputs DIR` is given, and
+prints the line.  `--full` adds what takes work of its own: the CPU baselines
+(`cpu_baseline`), `api_level`, and the correctness checks of the last step's
+outputs against EvaluateAt / the two-server reconstruction.
+
+`--dump-outputs DIR` writes DIR/outputs.npy (DIR/outputs.rank<r>.npy with N >
+1): the packed outputs the last timed step left in HBM, as float64
+[output][32-bit word, low first] so every bit survives; an output buffer over
+8 MiB is sampled at 2^20 fixed (seeded) positions, listed in
+DIR/outputs_index.npy.  Keys, points and seeds are fixed, so two builds run
+with the same arguments can be compared output for output.
+
 The line also carries, beside `value` and never in it:
 * `roofline.sustained_clock_ghz` / `clk_per_aes_per_cu`: the shader clock the
   timed launches themselves ran at (s_memtime / s_memrealtime stamps of every
   workgroup, dpf_hip_clock_probe), so a box can be told from a regression;
-* `api_level` (configs 2 and 3, N = 1; `--no-host-output` skips it): the
+* `api_level` (`--full`, configs 2 and 3, N = 1; `--no-host-output` skips it): the
   reference's own call shape, EvaluateUntil<uint64_t / absl::uint128>(0, {},
   ctx) returning a std::vector in host memory (the device kernel + the D2H
   copy into the caller's vector), timed on the same key -- PCIe-inclusive.
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
      python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -86,9 +99,17 @@ def parse():
     ap.add_argument("--log-domain", type=int, default=LOG_PER_GPU,
                     help="log2 outputs: of the whole domain (strong scaling) or per GPU (weak); "
                          "default 30 = the BASELINE config (31 per GPU for full_domain_u128)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure also run what takes work of its own: the CPU "
+                         "baselines, the host-output API rate (`api_level`) and the correctness "
+                         "checks of the last step's outputs.  Off by default: a plain run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy "
+                         "(float64; a fixed, seeded sample of outputs larger than the size cap)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--host-output", dest="host_output", action="store_true", default=True,
-                    help="full_domain / full_domain_u128 at N = 1 (default on): also time the "
+                    help="--full, full_domain / full_domain_u128 at N = 1 (default on): also time the "
                          "drop-in API call that returns host memory, EvaluateUntil<T>(0, {}, ctx) "
                          "-> std::vector<T> (reported in `api_level`, never as `value`)")
     ap.add_argument("--no-host-output", dest="host_output", action="store_false")
@@ -130,6 +151,11 @@ def parse():
         args.warmup = 1 if long_step else 3
     if args.scaling is None:
         args.scaling = "weak" if args.workload == "full_domain_u128" else "strong"
+    if args.steps < 1:
+        raise SystemExit(f"--steps {args.steps}: need at least one timed step")
+    if args.dump_outputs and args.workload.startswith("synthetic"):
+        raise SystemExit("--dump-outputs: the synthetic_* driver keeps its outputs in C++ and "
+                         "returns none to dump")
     if args.rehearse_world is not None and (args.gpus != 1 or not args.workload.startswith("full_domain")):
         raise SystemExit("--rehearse-world runs one full_domain* process (--gpus 1)")
     return args
@@ -508,6 +534,16 @@ def group_up(dist) -> bool:
     return dist.is_available() and dist.is_initialized()
 
 
+def benchmark_key(dpf, log_domain: int, beta):
+    """The full_domain* workloads' key (party 0) and its alpha.  Same key on
+    every rank and in every run: root seeds injected
+    (GenerateKeysIncrementalWithSeeds)."""
+    alpha = 0x2545F4914F6CDD1D % (1 << log_domain)
+    key, _ = dpf.generate_keys_incremental(alpha, [beta], seeds=(0x243F6A8885A308D3,
+                                                                 0x13198A2E03707344))
+    return alpha, key
+
+
 def main():
     args = parse()
     maybe_self_launch(args)
@@ -556,11 +592,7 @@ def main():
     dpf = D.DistributedPointFunction.create(params)
     if args.workload == "full_domain_tuple":
         dpf.register_value_type(vtype)
-    # Same key on every rank: root seeds injected (GenerateKeysIncrementalWithSeeds).
-    alpha = 0x2545F4914F6CDD1D % (1 << log_domain)
-    beta = D.to_value(vtype, beta_py)
-    key, _ = dpf.generate_keys_incremental(alpha, [beta], seeds=(0x243F6A8885A308D3,
-                                                                 0x13198A2E03707344))
+    alpha, key = benchmark_key(dpf, log_domain, D.to_value(vtype, beta_py))
     ctx0 = dpf.create_evaluation_context(key)
     depth = dpf.hierarchy_to_tree()[0] - S.shard_bits(shards)   # tree levels expanded per rank
     outputs_per_rank = 1 << S.strong_scaling_log_outputs(log_domain, shards)
@@ -600,9 +632,13 @@ def main():
     ginfo = S.group_info(kern_ms, device=coll)
     clocks = S.gather_over_ranks(clock["clock_ghz"], device=coll)
 
-    # Spot-check the last step's output (sum of the two parties' shares is beta
-    # at alpha, 0 elsewhere) on a few positions of this rank's shard.
-    _check_shard(dpf, key, out, shard, shards, outputs_per_rank, alpha, bits)
+    if args.dump_outputs:
+        dump_device_elements(args.dump_outputs, dump_name("outputs", world, rank), out, esz,
+                             outputs_per_rank)
+    # --full: spot-check the last step's output (sum of the two parties' shares
+    # is beta at alpha, 0 elsewhere) on a few positions of this rank's shard.
+    if args.full:
+        _check_shard(dpf, key, out, shard, shards, outputs_per_rank, alpha, bits)
 
     # Value hashes per leaf: the blocks the conversion reads (b = 1 for
     # integers and direct tuples; 2 for Tuple<IntModN32 x 2>: 16 + 4 bytes
@@ -687,11 +723,11 @@ def main():
             res["rehearsal"] = (f"one process evaluating shard 0 of a {shards}-rank split: "
                                 f"`value` is that shard's rate on one GPU, not an N-GPU result")
         profile_check(res["roofline"], tr, aes_per_launch, kern_ms_max)
-        if (args.host_output and world == 1 and shards == 1
+        if (args.full and args.host_output and world == 1 and shards == 1
                 and args.workload in ("full_domain", "full_domain_u128")):
             res["api_level"] = host_output_rate(dpf, ctx0, bits, args.host_output_reps, out,
                                                 outputs_per_rank, kern_ms_max)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ovt = None
             if args.workload == "full_domain_tuple":
                 ovt = (("tuple", [("intmodn", 32, 4294967291)] * 2)
@@ -865,8 +901,16 @@ def main_evaluate_at(args):
     kern_ms_max = S.max_over_ranks(kern_ms, device=coll)
     ginfo = S.group_info(kern_ms, device=coll)
 
-    # Correctness spot checks outside the timed region.
-    if summed:
+    if args.dump_outputs:
+        if summed and total is not None:      # the group sum every rank received
+            dump_array(args.dump_outputs, dump_name("sums", world, rank),
+                       dump_words(np.asarray(total), 8))
+        else:
+            dump_device_elements(args.dump_outputs, dump_name("sums" if summed else "outputs",
+                                                              world, rank),
+                                 out, 8, ppk if summed else nk * ppk)
+    # --full: correctness spot checks outside the timed region.
+    if args.full and summed:
         s0 = total if total is not None else out.cpu().numpy()
         dpf.evaluate_at_batch_sum_to_device(dpf.upload_key_batch(b1, stream=stream), 0, points,
                                             out, stream=stream)
@@ -874,7 +918,7 @@ def main_evaluate_at(args):
         rec = (np.asarray(s0).view(np.uint64) + np.asarray(s1).view(np.uint64)).tolist()
         if rec != [1, 1, 1, 1] + [0] * (ppk - 4):
             raise SystemExit(f"rank {rank}: two-server reconstruction failed: {rec[:8]}")
-    else:
+    elif args.full:
         host_pts = points.view(-1, 2)
         for k in (0, nk // 2, nk - 1):
             pk = host_pts[k * ppk:(k + 1) * ppk].cpu().numpy().view(np.uint64)
@@ -919,7 +963,7 @@ def main_evaluate_at(args):
             "process_group": ginfo,
         }
         profile_check(res["roofline"], tr, aes_per_launch, kern_ms_max)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             nb = min(nk, 32768)
             if summed:
                 host_pts = np.tile(shared.astype(np.uint64), (nb, 1))
@@ -963,7 +1007,7 @@ def main_synthetic(args):
         D._call(host.run_synthetic_data_benchmark, args.domain, 1 << 20, conc, 1, 4, 1,
                 mode == "direct", False, device_ctx)
     r = D._call(host.run_synthetic_data_benchmark, args.domain, 1 << 20, conc, 1, 4,
-                args.steps, mode == "direct", True, device_ctx)
+                args.steps, mode == "direct", args.full, device_ctx)   # --full: verified
     pub = PUBLISHED_SYNTHETIC.get((mode, args.domain), {}).get(args.distribution)
     secs = r["seconds_per_iteration"]
     outs = sum(r["outputs_per_level"])
@@ -1079,7 +1123,15 @@ def main_heavy_hitters(args):
     elapsed = S.max_over_ranks(t1 - t0, device=coll)
     kern_ms_max = S.max_over_ranks(kern_ms, device=coll)
     ginfo = S.group_info(kern_ms, device=coll)
-    verified = os.environ.get("DPF_BENCH_SKIP_VERIFY") != "1"  # probe libraries only
+    if args.dump_outputs and rank == 0:
+        # The last pass: the selected heavy hitters (128-bit values as four
+        # 32-bit words, low first) and every level's reconstructed sums.
+        words = [[(v >> s) & 0xFFFFFFFF for s in (0, 32, 64, 96)] for v in final]
+        dump_array(args.dump_outputs, "heavy_hitters", np.array(words, np.float64).reshape(-1, 4))
+        dump_array(args.dump_outputs, "level_counts", np.concatenate([c for _, _, c, _ in record]))
+        dump_array(args.dump_outputs, "level_tags", np.concatenate([t for _, _, _, t in record]))
+    # --full: every level against the plaintext histogram (DPF_BENCH_SKIP_VERIFY=1: probe libraries only)
+    verified = args.full and os.environ.get("DPF_BENCH_SKIP_VERIFY") != "1"
     if rank == 0 and verified:
         HH.verify(record, logs, values, idx)        # every level, untimed
     outputs_per_pass = sum(len(v) for _, v, _, _ in record) * n_keys * 2
@@ -1093,8 +1145,11 @@ def main_heavy_hitters(args):
                            workload="heavy_hitters")
           if n_keys == 1 << 20 and world == 1 and args.top_k == 1024 else None)
     if rank == 0:
-        ref = HH.plaintext_prefix_counts(values, idx, 128)
-        true_top = set(sorted(ref, key=lambda v: (-ref[v], v))[:args.top_k])
+        recall = None
+        if args.full:
+            ref = HH.plaintext_prefix_counts(values, idx, 128)
+            true_top = set(sorted(ref, key=lambda v: (-ref[v], v))[:args.top_k])
+            recall = len(true_top & set(final)) / max(len(true_top), 1)
         res = {
             "metric": HH_METRIC,
             "value": outputs_per_pass * args.steps / elapsed,
@@ -1118,7 +1173,7 @@ def main_heavy_hitters(args):
             "keygen_s_rank0": keygen_s, "keygen_threads": threads,
             "verified": ("two-server reconstruction == plaintext prefix histogram at every level"
                          if verified else False),
-            "true_top_k_recall": len(true_top & set(final)) / max(len(true_top), 1),
+            "true_top_k_recall": recall,
             **aes_rooflines(achieved, "hh_keys_kernel (cached levels) + batch_level_kernel<Mod32V, 2, true> (level 0)",
                             traffic=tr[0] if tr else None, traffic_unit="bytes per pass",
                             traffic_source=tr[1] if tr else None, pmc=tr[2] if tr else None,
@@ -1126,7 +1181,7 @@ def main_heavy_hitters(args):
             "process_group": ginfo,
         }
         profile_check(res["roofline"], tr, aes_rank, kern_ms_max)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_heavy_hitters(logs, record, alphas, seeds,
                                                              args.top_k)
         print(json.dumps(res), flush=True)
@@ -1204,9 +1259,11 @@ def main_dcf(args):
     elapsed = S.max_over_ranks(t1 - t0, device=coll)
     kern_ms_max = S.max_over_ranks(kern_ms, device=coll)
     ginfo = S.group_info(kern_ms, device=coll)
-    # Spot check against the single-key API (itself parity-tested vs the oracle).
-    host_pts = pts.cpu().numpy().view(np.uint64)
-    for k in (0, nk - 1):
+    if args.dump_outputs:
+        dump_device_elements(args.dump_outputs, dump_name("outputs", world, rank), out, 8, nk * ppk)
+    # --full: spot check against the single-key API (itself parity-tested vs the oracle).
+    host_pts = pts.cpu().numpy().view(np.uint64) if args.full else None
+    for k in (0, nk - 1) if args.full else ():
         xs = [int(a) | int(b) << 64 for a, b in host_pts[k * ppk:k * ppk + 16]]
         want = dcf.evaluate_packed(keys[k], xs).view(np.uint64).reshape(-1)
         got = out.view(torch.int64)[k * ppk:k * ppk + 16].cpu().numpy().view(np.uint64)
@@ -1237,7 +1294,7 @@ def main_dcf(args):
             "process_group": ginfo,
         }
         profile_check(res["roofline"], tr, aes_launch, kern_ms_max)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle as O
             P = O.dcf_params(n, ("int", 64))
@@ -1295,6 +1352,42 @@ def cpu_baseline_heavy_hitters(logs, record, alphas, seeds, top_k, budget_s=15.0
             "sample": f"{done} clients x all {len(logs)} levels of server 0 at the GPU run's "
                       f"candidates (EvaluateUntil per key, oracle over OpenSSL AES-NI); "
                       f"{dt:.1f} s wall on {CPU_THREADS} host threads"}
+
+
+DUMP_WHOLE_BYTES = 8 << 20   # --dump-outputs: a larger device output is sampled
+DUMP_SAMPLE = 1 << 20        # elements sampled from it (<= 40 MiB on disk with their indices)
+
+
+def dump_name(name: str, world: int, rank: int) -> str:
+    return name if world == 1 else f"{name}.rank{rank}"
+
+
+def dump_array(dirname: str, name: str, arr) -> None:
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
+def dump_words(buf: np.ndarray, esz: int) -> np.ndarray:
+    """Packed little-endian integer elements of `esz` bytes (a multiple of 4)
+    as float64 [element][32-bit word, low first]: every word is exact in
+    float64, which a 64- or 128-bit element is not."""
+    return np.ascontiguousarray(buf).view(np.uint8).reshape(-1, esz).view(np.uint32).astype(np.float64)
+
+
+def dump_device_elements(dirname: str, name: str, out, esz: int, n: int) -> None:
+    """--dump-outputs of a device buffer of `n` packed `esz`-byte elements, as
+    dump_words lays them out: the whole buffer up to DUMP_WHOLE_BYTES, else the
+    elements at DUMP_SAMPLE fixed (seeded) indices, first and last included,
+    with the indices beside them in <name>_index.npy."""
+    import torch
+    if n * esz <= DUMP_WHOLE_BYTES:
+        dump_array(dirname, name, dump_words(out[:n * esz].cpu().numpy(), esz))
+        return
+    rng = np.random.default_rng(0xD0F)
+    idx = np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, size=DUMP_SAMPLE - 2)]))
+    rows = out[:n * esz].view(torch.int32).view(n, esz // 4)[torch.from_numpy(idx).to(out.device)]
+    dump_array(dirname, name, dump_words(rows.cpu().numpy(), esz))
+    dump_array(dirname, name + "_index", idx)
 
 
 def _check_shard(dpf, key, out, rank, world, n, alpha, bits=64):

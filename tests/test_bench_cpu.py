@@ -122,6 +122,59 @@ def test_default_line_is_the_metric_configuration(bench):
     with pytest.raises(SystemExit):
         _parse(bench, ["--gpus", "2", "--rehearse-world", "8"])
     assert _parse(bench, ["--rehearse-world", "8"]).rehearse_world == 8
+    # A plain run measures the headline only; the baselines, api_level and the
+    # output checks run under --full.
+    assert not a.full and a.dump_outputs is None
+    f = _parse(bench, ["--full", "--dump-outputs", "d", "--steps", "7"])
+    assert f.full and f.host_output and not f.no_cpu_baseline
+    assert f.dump_outputs == "d" and f.steps == 7
+    with pytest.raises(SystemExit):
+        _parse(bench, ["--steps", "0"])
+    with pytest.raises(SystemExit):
+        _parse(bench, ["--workload", "synthetic_direct", "--dump-outputs", "d"])
+
+
+def test_dump_words_keeps_every_bit(bench):
+    import numpy as np
+    u64 = np.array([0, 1, 2**64 - 1, 0x0123456789ABCDEF], np.uint64)
+    w = bench.dump_words(u64, 8)
+    assert w.dtype == np.float64 and w.shape == (4, 2)
+    assert w[3].tolist() == [0x89ABCDEF, 0x01234567] and w[2].tolist() == [2**32 - 1] * 2
+    u128 = np.arange(32, dtype=np.uint8)                  # two 16-byte elements
+    w = bench.dump_words(u128, 16)
+    assert w.shape == (2, 4) and w[1, 0] == 0x13121110 and w[1, 3] == 0x1F1E1D1C
+
+
+@pytest.mark.parametrize("esz", [8, 16])
+def test_dump_device_elements_whole_and_sampled(bench, tmp_path, esz):
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(5)
+    # Up to DUMP_WHOLE_BYTES the whole buffer is written (a tail past n is not).
+    n = 1000
+    host = rng.integers(0, 256, size=(n + 3) * esz, dtype=np.uint8)
+    bench.dump_device_elements(str(tmp_path), "small", torch.from_numpy(host), esz, n)
+    got = np.load(tmp_path / "small.npy")
+    assert got.dtype == np.float64 and not (tmp_path / "small_index.npy").exists()
+    assert np.array_equal(got.astype(np.uint32).view(np.uint8).reshape(-1), host[:n * esz])
+    # One element more than that: DUMP_SAMPLE fixed positions, the same every call.
+    n = bench.DUMP_WHOLE_BYTES // esz + 1
+    host = rng.integers(0, 256, size=n * esz, dtype=np.uint8)
+    for name in ("a", "b"):
+        bench.dump_device_elements(str(tmp_path), name, torch.from_numpy(host), esz, n)
+    idx = np.load(tmp_path / "a_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b_index.npy"))
+    assert idx.dtype == np.float64 and idx[0] == 0 and idx[-1] == n - 1
+    assert np.all(np.diff(idx) > 0)
+    assert min(n, bench.DUMP_SAMPLE) // 2 < len(idx) <= bench.DUMP_SAMPLE   # duplicates drawn once
+    got = np.load(tmp_path / "a.npy")
+    assert got.shape == (len(idx), esz // 4)
+    want = host.reshape(n, esz)[idx.astype(np.int64)]
+    assert np.array_equal(got.astype(np.uint32).view(np.uint8), want)
+    assert np.array_equal(got, np.load(tmp_path / "b.npy"))
+    size = sum(os.path.getsize(tmp_path / f) for f in ("a.npy", "a_index.npy"))
+    # The largest case: 2^20 16-byte elements and their indices.
+    assert size <= 64 << 20 and bench.DUMP_SAMPLE * (16 // 4 + 1) * 8 + 256 <= 64 << 20
 
 
 def test_line_keys_pinned_in_source(bench):
@@ -129,5 +182,7 @@ def test_line_keys_pinned_in_source(bench):
     # only on a GPU; pinned here by source so a refactor cannot drop them).
     src = open(os.path.join(ROOT, "bench.py")).read()
     for key in ('"scaling": args.scaling', "sustained_clock_ghz=", "clk_per_aes_per_cu=",
-                '"step_overhead"', 'res["api_level"]', "H.clock_probe(True)"):
+                '"step_overhead"', 'res["api_level"]', "H.clock_probe(True)",
+                '"ms_per_step": ms_per_step', "if (args.full and args.host_output",
+                "if args.full and world == 1 and not args.no_cpu_baseline"):
         assert key in src, key

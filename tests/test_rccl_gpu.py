@@ -102,7 +102,9 @@ def test_share_collectives_through_rccl():
 def test_bench_in_a_one_rank_rccl_group(argv):
     env = _env()
     env["DPF_BENCH_FORCE_PG"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+    # --full keeps the checks of the last step's outputs (the two-server
+    # reconstruction of the aggregated shares among them).
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full",
                         "--no-cpu-baseline", "--no-host-output", *argv],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -45,7 +45,7 @@ for r in $(seq 1 $ROUNDS); do
       *) echo "ab.sh: bad variant $v"; restore; exit 2 ;;
     esac
     log=$O/${TAG}_$(echo $v | tr ':=/,' '____')_r$r.log
-    env $envset timeout -k 10 600 python bench.py $ARGS --no-cpu-baseline > $log 2>&1
+    env $envset timeout -k 10 600 python bench.py $ARGS --full --no-cpu-baseline > $log 2>&1
     rc=$?; restore
     [ $rc -eq 0 ] || { echo "$v failed"; tail -5 $log; exit 1; }
     python3 - "$v" "$log" <<'PY'

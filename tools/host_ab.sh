@@ -33,7 +33,7 @@ for r in $(seq 1 $ROUNDS); do
     for v in "$@"; do
       cp vlib/host_$v/* $L/
       log=$O/host_ab_${v}_r$r.log
-      timeout -k 10 600 python bench.py $a --no-cpu-baseline > $log 2>&1
+      timeout -k 10 600 python bench.py $a --full --no-cpu-baseline > $log 2>&1
       rc=$?; restore
       [ $rc -eq 0 ] || { echo "$v failed"; tail -5 $log; exit 1; }
       python3 -c "

@@ -26,7 +26,7 @@ prof() { bash tools/profile_workload.sh "$@" || exit 1; }
 # bench line <name> <bench.py args...> -> $O/bench_<tag>_<name>.json
 line() {
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $O/bench_${TAG}_$name.log 2>&1 || { tail $O/bench_${TAG}_$name.log; exit 1; }
+  timeout -k 10 400 python bench.py --full "$@" > $O/bench_${TAG}_$name.log 2>&1 || { tail $O/bench_${TAG}_$name.log; exit 1; }
   grep '^{' $O/bench_${TAG}_$name.log > $O/bench_${TAG}_$name.json
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read()); r=d.get('roofline',{}); print(sys.argv[2], d['value'], d['unit'], 'frac', r.get('frac'), 'profile_vs_launch', r.get('profile_vs_launch'))" $O/bench_${TAG}_$name.json $name
 }
@@ -46,10 +46,10 @@ part1)
   cat $O/${TAG}_smoke.log
   prof $TAG full_domain "expand_octet_kernel<FastIntLeaf<64, false> >" launch:3 -- --steps 20 --warmup 3 --no-cpu-baseline --no-host-output
   cp $O/${TAG}_full_domain_summary.json profiles/ || exit 1
-  timeout -k 10 300 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -20 $O/${TAG}_bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -20 $O/${TAG}_bench.err; exit 1; }
   cat $O/${TAG}_bench.json
-  timeout -k 10 300 python bench.py --host-output --no-cpu-baseline --steps 5 --warmup 1 > $O/${TAG}_api_u64.json 2> $O/${TAG}_api_u64.err || { tail -20 $O/${TAG}_api_u64.err; exit 1; }
-  timeout -k 10 500 python bench.py --workload full_domain_u128 --host-output --host-output-reps 6 --no-cpu-baseline --steps 3 --warmup 1 > $O/${TAG}_api_u128.json 2> $O/${TAG}_api_u128.err || { tail -20 $O/${TAG}_api_u128.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --host-output --no-cpu-baseline --steps 5 --warmup 1 > $O/${TAG}_api_u64.json 2> $O/${TAG}_api_u64.err || { tail -20 $O/${TAG}_api_u64.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --workload full_domain_u128 --host-output --host-output-reps 6 --no-cpu-baseline --steps 3 --warmup 1 > $O/${TAG}_api_u128.json 2> $O/${TAG}_api_u128.err || { tail -20 $O/${TAG}_api_u128.err; exit 1; }
   echo "api lines ok"
   # The shard each rank of a 2/4/8-GPU run evaluates (strong scaling), on this GPU.
   for w in 2 4 8; do
