@@ -245,16 +245,59 @@ struct ExpandParams {
   const uint8_t* cw_right;
   char* out;
   RoundKeys rkl, rkr, rkv, rkd;
-  // Octet kernel only: 0 = item u on thread u (grid stride); > 0 = workgroup b
-  // owns items [b, b + 1) * dyn_chunks * 64 and its waves take them 64 at a
-  // time from an LDS counter (dynamic distribution, dpf_kernels.hip).
+  // 0 = item u on thread u (grid stride); > 0 = the waves take the items 64
+  // at a time from a counter (dynamic distribution, dpf_kernels.hip):
+  // the launch's chunks of 64 undivided items per workgroup.
   int dyn_chunks;
+  // Chunk schedule of a dynamic launch (dyn_chunks > 0; plan_chunks in
+  // dpf_kernels.hip, take_expand_chunk below).  The chunks are numbered in
+  // the order they are taken, in up to three phases: phase j's chunks are 64
+  // items of shape (k0 + 2j, S - 2j), i.e. subtrees 4^j times smaller, so the
+  // launch ends on small pieces of work.  ph_end[j] is the counter value at
+  // which phase j ends (per counter: the whole launch for chunk_counter, the
+  // workgroup's share for the LDS counter; an absent phase ends where the one
+  // before it does), ph_item[j] the phase's first item in its own shape.
+  int ph_end[3];
+  int64_t ph_item[3];
+  // One counter for the whole launch (global memory, zeroed in stream order
+  // by the tree-top pass), or NULL: every workgroup counts through its own
+  // share of each phase in LDS.
+  unsigned int* chunk_counter;
   // Clock probe (dpf_hip_clock_probe): NULL, or [shader clocks, 100 MHz ticks,
-  // workgroups] that wave 0 of every workgroup adds its s_memtime /
-  // s_memrealtime deltas around its work into.  Nothing reads it back in the
-  // kernel; no output depends on it.
+  // workgroups, ...] that wave 0 of every workgroup adds its s_memtime /
+  // s_memrealtime deltas around its work into (ClockStamp below).  Nothing
+  // reads it back in the kernel; no output depends on it.
   unsigned long long* clock;
 };
+
+// The next chunk of a dynamic expand launch (ExpandParams::ph_end): the
+// wave's lane 0 draws a number from the launch's counter -- one relaxed
+// device-scope add, about 10^5 per launch -- or from the workgroup's LDS
+// counter, and the phase, its shape and the chunk's first item follow from
+// scalar compares.  Returns the lane's item and sets k0 and S, or returns
+// `done` once the counter has run out; wave-uniform.
+__device__ __forceinline__ int64_t take_expand_chunk(const ExpandParams& p, int* lds_counter,
+                                                     int64_t done, int& k0, int& S) {
+  unsigned int c = 0;
+  if ((threadIdx.x & 63) == 0)
+    c = p.chunk_counter ? __hip_atomic_fetch_add(p.chunk_counter, 1u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT)
+                        : (unsigned int)atomicAdd(lds_counter, 1);
+  c = __builtin_amdgcn_readfirstlane(c);
+  const unsigned int e0 = (unsigned int)p.ph_end[0], e1 = (unsigned int)p.ph_end[1],
+                     e2 = (unsigned int)p.ph_end[2];
+  if (c >= e2) return done;
+  // Selects, not indexing: the parameters stay in scalar registers.
+  const int j = (c >= e0) + (c >= e1);
+  const unsigned int first = j == 0 ? 0u : (j == 1 ? e0 : e1);
+  const unsigned int last = j == 0 ? e0 : (j == 1 ? e1 : e2);
+  const int64_t item0 = j == 0 ? p.ph_item[0] : (j == 1 ? p.ph_item[1] : p.ph_item[2]);
+  const int64_t group = p.chunk_counter ? 0 : (int64_t)blockIdx.x;
+  const int64_t chunk = group * (int64_t)(last - first) + (c - first);
+  k0 = p.k0 + 2 * j;
+  S = p.S - 2 * j;
+  return item0 + chunk * 64 + (int64_t)(threadIdx.x & 63);
+}
 
 // Dynamic distribution of 64-item chunks over a workgroup's waves (r16).
 // A CU's arbiter favours its oldest waves, so with a fixed share per thread
@@ -285,6 +328,12 @@ __device__ __forceinline__ int64_t take_chunk(int* counter, int64_t per_wg, int6
 #ifndef DPF_CLOCK_PROBE_WAVE
 #define DPF_CLOCK_PROBE_WAVE 0   // the stamped wave of each workgroup (variant builds: the last)
 #endif
+// Words of the probe's accumulator: [0..2] as ExpandParams::clock says, then
+// the launch's first begin, first exit and last exit stamps, and from
+// kProbeWords on the last exit of each of the first kProbeWorkgroups workgroups.
+constexpr int kProbeFirstBegin = 3, kProbeFirstExit = 4, kProbeLastExit = 5, kProbeWords = 8;
+constexpr int kProbeWorkgroups = 1024;
+constexpr size_t kProbeBytes = (kProbeWords + kProbeWorkgroups) * sizeof(unsigned long long);
 struct ClockStamp {
   unsigned long long c0 = 0, r0 = 0;
   __device__ __forceinline__ void begin(const unsigned long long* acc) {
@@ -303,6 +352,28 @@ struct ClockStamp {
         atomicAdd(acc + 0, c1 - c0);
         atomicAdd(acc + 1, r1 - r0);
         atomicAdd(acc + 2, 1ull);
+        atomicMax(acc + kProbeFirstBegin, ~r0);
+      }
+    }
+    exits(acc);
+  }
+  // Exit stamps (dpf_hip_clock_probe_exits): every wave folds the time it
+  // leaves the kernel into the launch's first and last exit and into its
+  // workgroup's last exit.  s_memrealtime counts at a constant rate on the
+  // whole chip; minima are kept as maxima of the complement, so a zeroed
+  // accumulator is empty.  The pair kernel, short of scalar registers, keeps
+  // no begin stamp through its loop: its wave 0 files it at once (first_begin).
+  static __device__ __forceinline__ void first_begin(unsigned long long* acc) {
+    if (DPF_CLOCK_PROBE && acc != nullptr && threadIdx.x == 0)
+      atomicMax(acc + kProbeFirstBegin, ~__builtin_amdgcn_s_memrealtime());
+  }
+  static __device__ __forceinline__ void exits(unsigned long long* acc) {
+    if (DPF_CLOCK_PROBE && acc != nullptr) {
+      const unsigned long long r = __builtin_amdgcn_s_memrealtime();
+      if ((threadIdx.x & 63) == 0) {
+        atomicMax(acc + kProbeFirstExit, ~r);
+        atomicMax(acc + kProbeLastExit, r);
+        if (blockIdx.x < kProbeWorkgroups) atomicMax(acc + kProbeWords + blockIdx.x, r);
       }
     }
   }

@@ -128,28 +128,38 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void eval_paths_kernel(PathP
   }
 }
 
-template <class Leaf>
+// SCHED: the instance for launches with a chunk schedule (one counter for
+// the launch or tapered chunks; always dynamic).  Its k0 and S change from
+// chunk to chunk, which costs every instance 3-5 VGPRs and some of them
+// spills, so the static launches and the uniform per-workgroup chunks keep
+// an instance in which both are launch constants.
+template <class Leaf, bool SCHED = false>
 __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_kernel(ExpandParams p, Leaf leaf) {
   __shared__ LdsImage lds;
-  __shared__ int next_chunk;   // take_chunk (dpf_device.h), p.dyn_chunks > 0
+  __shared__ int next_chunk;   // take_chunk / take_expand_chunk (dpf_device.h), dynamic launches
   leaf.init();
   fill_tables(lds.tab);
   fill_cws(lds, p.cw_seed, p.cw_left, p.cw_right, p.num_levels);
   if (threadIdx.x == 0) next_chunk = 0;
   __syncthreads();
   const LdsLookup lk = make_lookup(lds, KeySet{key_ref(p.rkl), key_ref(p.rkr), key_ref(p.rkv), key_ref(p.rkd)});
-  const int k0 = p.k0, S = p.S;
-  const int B = S >= 1 ? 1 : 0;  // leaf pairs share their parent
-  const int G = S - B;            // depth of the DFS stack
-  const int64_t ngroups = (int64_t)1 << G;
+  int k0 = p.k0, S = p.S;
+  if constexpr (SCHED) ClockStamp::first_begin(p.clock);
   // Items by grid stride, or 64 at a time per wave (dyn_chunks > 0, as the
-  // octet kernel).
+  // octet kernel; SCHED: the chunk's shape (k0, S) comes with it).
   const int64_t nch = (p.num_items + 63) / 64;
-  for (int64_t item = p.dyn_chunks ? take_chunk(&next_chunk, p.dyn_chunks, nch, p.num_items)
-                                   : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       item < p.num_items;
-       item = p.dyn_chunks ? take_chunk(&next_chunk, p.dyn_chunks, nch, p.num_items)
-                           : item + (int64_t)gridDim.x * blockDim.x) {
+  const int64_t end = SCHED ? INT64_MAX : p.num_items;
+  auto take = [&]() -> int64_t {
+    if constexpr (SCHED) return take_expand_chunk(p, &next_chunk, end, k0, S);
+    else return take_chunk(&next_chunk, p.dyn_chunks, nch, p.num_items);
+  };
+  for (int64_t item = SCHED || p.dyn_chunks ? take()
+                                            : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+       item < end;
+       item = SCHED || p.dyn_chunks ? take() : item + (int64_t)gridDim.x * blockDim.x) {
+    const int B = S >= 1 ? 1 : 0;  // leaf pairs share their parent
+    const int G = S - B;            // depth of the DFS stack
+    const int64_t ngroups = (int64_t)1 << G;
     // 1. walk from the start seed to this item's subtree root.
     const int64_t r = item >> k0;
     Block4 s = load_block(p.seeds_in + r);
@@ -199,6 +209,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_kernel(ExpandPar
       }
     }
   }
+  if constexpr (SCHED) ClockStamp::exits(p.clock);
 }
 
 // Octet form of expand_kernel for integer leaves that fill whole 16-byte
@@ -289,14 +300,14 @@ template <> struct OctetStash<SwarLeaf> {
   static constexpr int value = DPF_OCTET_LDS_STASH < 1 ? DPF_OCTET_LDS_STASH : 1;
 };
 
-template <class Leaf>
+template <class Leaf, bool SCHED = false>   // SCHED: as expand_kernel's
 __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(ExpandParams p,
                                                                              Leaf leaf) {
   __shared__ LdsImage lds;
   constexpr int kStash = OctetStash<Leaf>::value;
   __shared__ uint4 stash[kStash >= 1 ? kBlock : 1];
   __shared__ uint3 stash2[kStash >= 2 ? kBlock : 1];
-  __shared__ int next_chunk;   // dynamic distribution: the workgroup's next 64 items
+  __shared__ int next_chunk;   // dynamic distribution: the workgroup's own chunk counter
   static_assert(sizeof(LdsImage) + (kStash >= 1 ? 16 * kBlock : 0) +
                     (kStash >= 2 ? 12 * kBlock : 0) + 16 <= 160 * 1024, "LDS over 160 KiB");
   leaf.init();
@@ -305,29 +316,38 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(Exp
   if (threadIdx.x == 0) next_chunk = 0;
   __syncthreads();
   const LdsLookup lk = make_lookup(lds, KeySet{key_ref(p.rkl), key_ref(p.rkr), key_ref(p.rkv), key_ref(p.rkd)});
-  const int k0 = p.k0, S = p.S;
-  const int G = S - 3;
-  const int64_t ngroups = (int64_t)1 << G;
+  int k0 = p.k0, S = p.S;
   ClockStamp stamp;
   stamp.begin(p.clock);
   // Items: thread u takes u, u + threads, ... (static), or -- dyn_chunks > 0
-  // -- each wave takes the workgroup's next 64 items from next_chunk until
-  // its range is used up.  The CU's arbiter favours its oldest waves (in
-  // config 2 wave 0 of a workgroup finished in 7.8 ms, wave 15 in 16.6 ms of
-  // a 16.9 ms launch): with a fixed share the last third of a launch runs on
-  // fewer and fewer waves, while taken dynamically the fast waves do more
-  // and all finish together.  Every lane of a wave holds the same chunk, so
-  // the DFS stays wave-uniform.
+  // -- each wave takes the next 64 items from the launch's counter (or its
+  // workgroup's share from its LDS counter) until they are used up.  The CU's
+  // arbiter favours its oldest waves (in config 2 wave 0 of a workgroup
+  // finished in 7.8 ms, wave 15 in 16.6 ms of a 16.9 ms launch): with a fixed
+  // share the last third of a launch runs on fewer and fewer waves, while
+  // taken dynamically the fast waves and the fast CUs do more and all finish
+  // together; the last chunks are of smaller subtrees (take_expand_chunk), so
+  // the waves also stop within a small chunk's time of each other.  Every
+  // lane of a wave holds the same chunk, so the DFS stays wave-uniform.
   const int lane = (int)(threadIdx.x & 63);
+  const int64_t end = SCHED ? INT64_MAX : p.num_items;
   auto take = [&]() -> int64_t {
-    int c = 0;
-    if (lane == 0) c = atomicAdd(&next_chunk, 1);
-    c = __builtin_amdgcn_readfirstlane(c);
-    return c < p.dyn_chunks ? ((int64_t)blockIdx.x * p.dyn_chunks + c) * 64 + lane : p.num_items;
+    if constexpr (SCHED) {
+      return take_expand_chunk(p, &next_chunk, end, k0, S);
+    } else {   // the workgroup's own range of uniform chunks
+      int c = 0;
+      if (lane == 0) c = atomicAdd(&next_chunk, 1);
+      c = __builtin_amdgcn_readfirstlane(c);
+      return c < p.dyn_chunks ? ((int64_t)blockIdx.x * p.dyn_chunks + c) * 64 + lane
+                              : p.num_items;
+    }
   };
-  for (int64_t item = p.dyn_chunks ? take() : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       item < p.num_items;
-       item = p.dyn_chunks ? take() : item + (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t item = SCHED || p.dyn_chunks ? take()
+                                            : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+       item < end;
+       item = SCHED || p.dyn_chunks ? take() : item + (int64_t)gridDim.x * blockDim.x) {
+    const int G = S - 3;
+    const int64_t ngroups = (int64_t)1 << G;
     // 1. walk from the start seed to this item's subtree root.
     const int64_t r = item >> k0;
     Block4 s = load_block(p.seeds_in + r);
@@ -578,7 +598,12 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_small_kernel(Exp
 struct SeedLeaf {
   dpf_block* seeds;
   uint8_t* ctrl;
-  __device__ __forceinline__ void init() const {}
+  // The chunk counter of the launch that follows (ExpandParams::chunk_counter)
+  // or NULL: zeroed here, in stream order before that launch.
+  unsigned int* counter;
+  __device__ __forceinline__ void init() const {
+    if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *counter = 0u;
+  }
   __device__ __forceinline__ void emit2(const LdsLookup&, KeyRef, Block4 s0, uint32_t t0, Block4 s1,
                                         uint32_t t1, int64_t first, char*) const {
     store_block(seeds + first, s0);
@@ -915,7 +940,10 @@ struct TopScratch {
   }
 };
 // Returns the error of a failed launch, else kOk (p rewritten when the pass ran).
-int expand_top(ExpandParams& p, hipStream_t s, TopScratch& scratch) {
+// With `counter`, the scratch also holds the launch's chunk counter on a
+// 128-byte line of its own, zeroed by the pass (*counter set when it ran).
+int expand_top(ExpandParams& p, hipStream_t s, TopScratch& scratch,
+               unsigned int** counter = nullptr) {
   const int64_t starts = p.num_items >> p.k0;
   // Few start seeds (full-domain calls and their shards): with many starts
   // every item's walk is short and a workgroup per start would idle.
@@ -939,11 +967,15 @@ int expand_top(ExpandParams& p, hipStream_t s, TopScratch& scratch) {
   (void)pool_kept;
   const size_t items = (size_t)p.num_items;
   void* mem = nullptr;
-  HIP_TRY(hipMallocAsync(&mem, items * (sizeof(dpf_block) + 1), s));
+  const size_t roots = (items * (sizeof(dpf_block) + 1) + 127) / 128 * 128;
+  HIP_TRY(hipMallocAsync(&mem, roots + (counter ? 128 : 0), s));
   scratch.mem = mem;
   scratch.s = s;
   SeedLeaf leaf{static_cast<dpf_block*>(mem),
-                static_cast<uint8_t*>(mem) + items * sizeof(dpf_block)};
+                static_cast<uint8_t*>(mem) + items * sizeof(dpf_block),
+                counter ? reinterpret_cast<unsigned int*>(static_cast<char*>(mem) + roots)
+                        : nullptr};
+  if (counter) *counter = leaf.counter;
   ExpandParams q = p;
   q.k0 = t;
   q.S = D;
@@ -992,20 +1024,96 @@ int octet_walk_levels() {
   const int k = std::atoi(v);
   return k < 0 ? 0 : (k > 4 ? 4 : k);
 }
+// Who takes which chunk, and how the chunks shrink towards the end of the
+// launch (r17; ExpandParams::ph_end, take_expand_chunk).
+//   * One counter for all workgroups: with a fixed range per workgroup, a CU
+//     that starts late or runs slow finishes late and nobody takes its
+//     chunks.  DPF_OCTET_GLOBAL=0 (read per launch) keeps a counter and an
+//     equal share of every phase per workgroup (A/B and test hook).
+//   * Tapered chunks (guided self-scheduling): when the counter runs out
+//     every wave is somewhere inside a chunk, so the launch drains for up to
+//     one chunk's time on fewer and fewer waves -- launch / chunks-per-wave,
+//     a quarter of the 2^27 shard's launch at its 4 chunks per wave.  So the
+//     item range is cut into up to three phases, taken in order: phase j's
+//     items are subtrees of depth S - 2j (4^j times smaller) that walk 2j more
+//     levels from the same tree-top roots.  A phase hands over to the next
+//     finer one when at most DPF_OCTET_TAPER_AT (default 2) of its chunks
+//     per resident wave are left; a phase exists only while its depth is >=
+//     the kernel's minimum.  DPF_OCTET_TAPER=<0..2> (read per launch) caps
+//     the number of finer phases; 0: uniform chunks.
+// The plan is a pure function of the launch's shape, the CU count and the
+// hooks, exported as dpf_hip_octet_schedule for the CPU tests.
+int env_int(const char* name, int dflt, int lo, int hi) {
+  const char* v = std::getenv(name);
+  if (!v || !*v) return dflt;
+  const int k = std::atoi(v);
+  return k < lo ? lo : (k > hi ? hi : k);
+}
+}  // namespace
+namespace dpf_rt {
+ChunkPlan plan_chunks(int64_t num_items, int k0, int S, int min_S, int64_t cus, bool sched_ok) {
+  ChunkPlan c{};
+  const int sh = octet_dynamic_shift(S);
+  if (sh <= 0 || S - sh < min_S || k0 + sh > 62 || cus <= 0 || num_items <= 0 ||
+      num_items > (INT64_MAX >> (sh + 4)) || (num_items << sh) % (cus * 64) != 0 ||
+      (num_items << sh) < 4 * cus * kBlock || (num_items << sh) / 64 > (INT32_MAX >> 4))
+    return c;
+  c.shift = sh;
+  // Both are on by default from 2^20 leaf blocks per CU: measured against the
+  // parent build, 2^29 / 2^28 blocks ran 1.025x / 1.035x faster (15.31 vs
+  // 15.70 ms, 7.41 vs 7.67 ms), 2^27 / 2^26 blocks 0.7% / 4% slower (3.85 vs
+  // 3.82 ms, 2.01 vs 1.94 ms; at 2^26 each half alone was slower too), so the
+  // smaller launches keep a counter per workgroup and uniform chunks
+  // (profiles/r17/octet_taper_ab.txt).
+  const int big = sched_ok && (num_items << S) / cus >= ((int64_t)1 << 20);
+  c.global = env_int("DPF_OCTET_GLOBAL", big, 0, 1);
+  c.groups = c.global ? 1 : cus;
+  const int k = k0 + sh, s = S - sh;
+  const int64_t coarse = (num_items << sh) / 64;   // chunks of shape (k, s)
+  // Chunks (in phase 0's size) from each phase's start to the end of the
+  // launch: per resident wave `at` of phase 0's, then `at` of phase 1's.
+  const int finer = env_int("DPF_OCTET_TAPER", big ? 2 : 0, 0, 2);
+  const int64_t at = env_int("DPF_OCTET_TAPER_AT", 2, 1, 16) * cus * (kBlock / 64);
+  auto exists = [&](int j) { return j <= finer && s - 2 * j >= min_S && k + 2 * j <= 62; };
+  int64_t start[4] = {0, coarse, coarse, coarse};
+  if (exists(1)) start[1] = coarse - (coarse < at ? coarse : at);
+  if (exists(2)) start[2] = coarse - (coarse - start[1] < (at >> 2) ? coarse - start[1] : (at >> 2));
+  for (int j = 0; j < 3; ++j) {
+    c.k0[j] = k + 2 * j;
+    c.S[j] = s - 2 * j;
+    c.chunks[j] = (start[j + 1] - start[j]) << (2 * j);
+    c.first_item[j] = (start[j] * 64) << (2 * j);
+  }
+  return c;
+}
+}  // namespace dpf_rt
+namespace {
 // Runs the tree-top pass and sets p's shape (and *grid, *blk) for the octet
 // kernel launch.
+thread_local ChunkPlan g_last_plan{};   // dpf_hip_last_expand_schedule
+// sched_ok: whether launches of this kernel and leaf type get the chip-wide
+// counter and the taper by default (SchedDefault; the hooks still set them).
 int subtree_shape(ExpandParams& p, int min_S, hipStream_t s, TopScratch& top, int* grid,
-                  int* blk) {
+                  int* blk, bool sched_ok) {
   p.dyn_chunks = 0;
+  p.chunk_counter = nullptr;
+  g_last_plan = ChunkPlan{};
   const int64_t cus = num_cus();
-  const int sh = octet_dynamic_shift(p.S);
-  if (sh > 0 && p.S - sh >= min_S && p.k0 + sh <= 62 &&
-      (p.num_items << sh) % (cus * 64) == 0 && (p.num_items << sh) >= 4 * cus * kBlock) {
+  const ChunkPlan plan = plan_chunks(p.num_items, p.k0, p.S, min_S, cus, sched_ok);
+  if (const int sh = plan.shift) {
     ExpandParams q = p;
     q.S -= sh;
     q.k0 += sh;
     q.num_items <<= sh;
     q.dyn_chunks = (int)(q.num_items / (cus * 64));
+    int64_t taken = 0;
+    for (int j = 0; j < 3; ++j) {
+      taken += plan.chunks[j] / plan.groups;
+      q.ph_end[j] = (int)taken;
+      q.ph_item[j] = plan.first_item[j];
+    }
+    unsigned int* counter = nullptr;
+    unsigned int** want_counter = plan.global ? &counter : nullptr;
     // The tree-top pass stops `w` levels above the items (a quarter of the
     // roots for w = 2: fewer rounds of its latency-bound workgroups), and
     // every item walks those levels itself (one path step per level, in the
@@ -1016,8 +1124,9 @@ int subtree_shape(ExpandParams& p, int min_S, hipStream_t s, TopScratch& top, in
       t.k0 = q.k0 - w;
       t.S = q.S + w;
       t.num_items = q.num_items >> w;
-      if (int st = expand_top(t, s, top)) return st;
+      if (int st = expand_top(t, s, top, want_counter)) return st;
       if (t.k0 == 0) {
+        q.chunk_counter = counter;
         q.seeds_in = t.seeds_in;
         q.ctrl_in = t.ctrl_in;
         q.cw_seed = t.cw_seed;
@@ -1026,14 +1135,17 @@ int subtree_shape(ExpandParams& p, int min_S, hipStream_t s, TopScratch& top, in
         q.num_levels = q.S + w;
         q.k0 = w;
         p = q;
+        g_last_plan = plan;
         *grid = (int)cus;
         *blk = kBlock;
         return kOk;
       }
     }
-    if (int st = expand_top(q, s, top)) return st;
+    if (int st = expand_top(q, s, top, want_counter)) return st;
     if (q.k0 == 0) {
+      q.chunk_counter = counter;
       p = q;
+      g_last_plan = plan;
       *grid = (int)cus;
       *blk = kBlock;
       return kOk;
@@ -1044,8 +1156,30 @@ int subtree_shape(ExpandParams& p, int min_S, hipStream_t s, TopScratch& top, in
   *grid = grid_for(p.num_items, *blk);
   return kOk;
 }
+// The two SCHED instances that spill are not a default: the octet kernel
+// with SwarLeaf (4 VGPRs) and the pair kernel with Mod32Leaf<5> (20 B of
+// scratch per lane); every other SCHED instance has none.
+template <class Leaf, bool OCTET> struct SchedDefault { static constexpr bool value = true; };
+template <> struct SchedDefault<SwarLeaf, true> { static constexpr bool value = false; };
+template <> struct SchedDefault<Mod32Leaf<kMod32MaxLeaves>, false> {
+  static constexpr bool value = false;
+};
+template <class Leaf>
 int octet_shape(ExpandParams& p, hipStream_t s, TopScratch& top, int* grid, int* blk) {
-  return subtree_shape(p, 3, s, top, grid, blk);
+  return subtree_shape(p, 3, s, top, grid, blk, SchedDefault<Leaf, true>::value);
+}
+// Launches with one counter for the launch or with finer phases run the
+// kernels' SCHED instance; static launches and uniform chunks per workgroup
+// the one whose subtree shape is a launch constant.
+bool has_schedule(const ExpandParams& p) {
+  return p.dyn_chunks && (p.chunk_counter || p.ph_end[0] != p.ph_end[2]);
+}
+template <class Leaf>
+void launch_octet_kernel(int grid, int blk, hipStream_t s, const ExpandParams& p, const Leaf& leaf) {
+  if (has_schedule(p))
+    hipLaunchKernelGGL((expand_octet_kernel<Leaf, true>), dim3(grid), dim3(blk), 0, s, p, leaf);
+  else
+    hipLaunchKernelGGL((expand_octet_kernel<Leaf, false>), dim3(grid), dim3(blk), 0, s, p, leaf);
 }
 
 template <class Leaf>
@@ -1062,8 +1196,12 @@ int launch_expand(const ExpandParams& p0, const Leaf& leaf, hipStream_t s) {
   ExpandParams p = p0;
   TopScratch top;
   int grid = 0, blk = 0;
-  if (int st = subtree_shape(p, 1, s, top, &grid, &blk)) return st;
-  hipLaunchKernelGGL(expand_kernel<Leaf>, dim3(grid), dim3(blk), 0, s, p, leaf);
+  if (int st = subtree_shape(p, 1, s, top, &grid, &blk, SchedDefault<Leaf, false>::value))
+    return st;
+  if (has_schedule(p))
+    hipLaunchKernelGGL((expand_kernel<Leaf, true>), dim3(grid), dim3(blk), 0, s, p, leaf);
+  else
+    hipLaunchKernelGGL((expand_kernel<Leaf, false>), dim3(grid), dim3(blk), 0, s, p, leaf);
   HIP_TRY(hipGetLastError());
   return kOk;
 }
@@ -1079,9 +1217,8 @@ bool launch_octet(const ExpandParams& p0, const dpf_block* vcw, int E, int party
   ExpandParams p = p0;
   TopScratch top;
   int grid = 0, blk = 0;
-  if ((*st = octet_shape(p, s, top, &grid, &blk)) != kOk) return true;
-  hipLaunchKernelGGL((expand_octet_kernel<FastIntLeaf<BITS, XOR>>), dim3(grid), dim3(blk), 0, s, p,
-                     FastIntLeaf<BITS, XOR>{vcw, E, party, store_bytes, {}});
+  if ((*st = octet_shape<FastIntLeaf<BITS, XOR>>(p, s, top, &grid, &blk)) != kOk) return true;
+  launch_octet_kernel(grid, blk, s, p, FastIntLeaf<BITS, XOR>{vcw, E, party, store_bytes, {}});
   return true;
 }
 
@@ -1494,10 +1631,71 @@ int dpf_hip_clock_probe(int on) {
   }
   if (!on) return kOk;
   void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, 4 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(p, 0, 4 * sizeof(unsigned long long)));
+  HIP_TRY(hipMalloc(&p, kProbeBytes));
+  HIP_TRY(hipMemset(p, 0, kProbeBytes));
   HIP_TRY(hipDeviceSynchronize());
   dpf_rt::g_clock_acc.store(static_cast<unsigned long long*>(p));
+  return kOk;
+}
+
+int dpf_hip_clock_probe_exits(double* out) {
+  unsigned long long* acc = dpf_rt::g_clock_acc.load();
+  if (!acc) return fail(kFailedPrecondition, "clock probe is off (dpf_hip_clock_probe(1))");
+  if (!out) return fail(kInvalidArgument, "NULL pointer");
+  std::vector<unsigned long long> h(kProbeWords + kProbeWorkgroups);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h.data(), acc, kProbeBytes, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 6; ++i) out[i] = 0.0;
+  if (h[kProbeLastExit] == 0 || h[kProbeFirstBegin] == 0) return kOk;   // nothing stamped
+  const unsigned long long t0 = ~h[kProbeFirstBegin];
+  auto sec = [&](unsigned long long t) { return (double)(int64_t)(t - t0) * 1e-8; };
+  double lo = 0, hi = 0, sum = 0;
+  int n = 0;
+  for (int i = 0; i < kProbeWorkgroups; ++i) {
+    if (!h[kProbeWords + i]) continue;
+    const double t = sec(h[kProbeWords + i]);
+    lo = n ? (t < lo ? t : lo) : t;
+    hi = n ? (t > hi ? t : hi) : t;
+    sum += t;
+    ++n;
+  }
+  out[0] = sec(~h[kProbeFirstExit]);
+  out[1] = sec(h[kProbeLastExit]);
+  out[2] = lo;
+  out[3] = hi;
+  out[4] = n ? sum / n : 0.0;
+  out[5] = n;
+  return kOk;
+}
+
+static void write_plan(const dpf_rt::ChunkPlan& c, int64_t* out) {
+  for (int i = 0; i < 15; ++i) out[i] = 0;
+  out[0] = c.shift;
+  if (!c.shift) return;
+  out[1] = c.global;
+  out[2] = c.groups;
+  for (int j = 0; j < 3; ++j) {
+    out[3 + 4 * j] = c.chunks[j];
+    out[4 + 4 * j] = c.first_item[j];
+    out[5 + 4 * j] = c.k0[j];
+    out[6 + 4 * j] = c.S[j];
+  }
+}
+
+int dpf_hip_octet_schedule(int64_t num_items, int k0, int subtree_depth, int min_depth,
+                           int compute_units, int64_t* out) {
+  if (!out) return fail(kInvalidArgument, "NULL pointer");
+  if (num_items < 1 || k0 < 0 || subtree_depth < 0 || k0 + subtree_depth > 62 ||
+      compute_units < 1)
+    return fail(kInvalidArgument, "launch shape out of range");
+  write_plan(dpf_rt::plan_chunks(num_items, k0, subtree_depth, min_depth, compute_units, true),
+             out);
+  return kOk;
+}
+
+int dpf_hip_last_expand_schedule(int64_t* out) {
+  if (!out) return fail(kInvalidArgument, "NULL pointer");
+  write_plan(g_last_plan, out);
   return kOk;
 }
 
@@ -1507,7 +1705,7 @@ int dpf_hip_clock_probe_read(double* clock_ghz, int64_t* workgroups, double* mea
   unsigned long long h[4] = {0, 0, 0, 0};
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(h, acc, sizeof(h), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemset(acc, 0, sizeof(h)));
+  HIP_TRY(hipMemset(acc, 0, kProbeBytes));
   HIP_TRY(hipDeviceSynchronize());
   // s_memtime counts shader clocks, s_memrealtime a constant 100 MHz.
   if (clock_ghz) *clock_ghz = h[1] ? (double)h[0] / (double)h[1] * 0.1 : 0.0;
@@ -2265,8 +2463,7 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
 #if defined(DPF_FORCE_S)
   if (num_levels >= DPF_FORCE_S) S = DPF_FORCE_S;  // variant builds (tools/variant_bench.py)
 #endif
-  ExpandParams p;
-  p.dyn_chunks = 0;
+  ExpandParams p{};   // static launch, no chunk schedule
   p.num_levels = num_levels;
   p.S = S;
   p.k0 = num_levels - S;
@@ -2339,8 +2536,8 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
         note_expand<SwarLeaf>(p, true);
         TopScratch top;
         int grid = 0, blk = 0;
-        if (int st = octet_shape(p, s, top, &grid, &blk)) return st;
-        hipLaunchKernelGGL((expand_octet_kernel<SwarLeaf>), dim3(grid), dim3(blk), 0, s, p, w);
+        if (int st = octet_shape<SwarLeaf>(p, s, top, &grid, &blk)) return st;
+        launch_octet_kernel(grid, blk, s, p, w);
         HIP_TRY(hipGetLastError());
         return kOk;
       }
@@ -2371,8 +2568,8 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
         note_expand<Mod32Leaf<2>>(p, true);
         TopScratch top;
         int grid = 0, blk = 0;
-        if (int st = octet_shape(p, s, top, &grid, &blk)) return st;
-        hipLaunchKernelGGL((expand_octet_kernel<Mod32Leaf<2>>), dim3(grid), dim3(blk), 0, s, p, m);
+        if (int st = octet_shape<Mod32Leaf<2>>(p, s, top, &grid, &blk)) return st;
+        launch_octet_kernel(grid, blk, s, p, m);
         HIP_TRY(hipGetLastError());
         return kOk;
       }

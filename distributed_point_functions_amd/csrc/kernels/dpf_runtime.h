@@ -26,6 +26,22 @@ int grid_for(int64_t work_items, int block);   // workgroups of `block` threads,
 // fixed share per thread): dynamic when the launch gives every wave at least
 // 4 chunks and `env` is not "0" (A/B and test hooks, read per launch).
 int64_t dynamic_chunks_per_wg(int64_t items, int grid, int block, const char* env);
+// Chunk schedule of a full-domain expand launch of `num_items` subtrees of
+// depth S, each k0 levels below its start seed, on `cus` workgroups of 16
+// waves (dpf_kernels.hip, "Who takes which chunk"; reads the DPF_OCTET_*
+// hooks).  shift == 0: a static launch, nothing else is set.  Else phase j
+// (taken in order) is chunks[j] chunks of 64 items of shape (k0[j], S[j]),
+// the first of them item first_item[j] in that shape; absent phases have no
+// chunks.
+struct ChunkPlan {
+  int shift;     // levels taken off the subtrees for dynamic distribution
+  int global;    // 1: one counter for the launch; 0: one per workgroup
+  int64_t groups;   // counters: 1, or cus (each then takes chunks[j] / cus of phase j)
+  int k0[3], S[3];
+  int64_t chunks[3], first_item[3];
+};
+// sched_ok false: the counter per launch and the taper only where the hooks ask.
+ChunkPlan plan_chunks(int64_t num_items, int k0, int S, int min_S, int64_t cus, bool sched_ok);
 int validate_desc(const dpf_value_desc* d);    // kOk or the failure code
 int packed_size(const dpf_value_desc* d);      // bytes of one packed element
 bool fast_int(const dpf_value_desc* d);        // one plain/XOR integer leaf, direct, b == 1

@@ -97,6 +97,14 @@ def load(require_gpu: bool = False):
         L.dpf_hip_clock_probe_read.argtypes = [ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_int64),
                                                ctypes.POINTER(ctypes.c_double)]
+        # Diagnostics a parent build swapped in for an A/B (tools/ab.sh lib:<name>)
+        # may not have yet; build() checks the in-tree library for every symbol.
+        for name, types in (("dpf_hip_clock_probe_exits", [ctypes.POINTER(ctypes.c_double)]),
+                            ("dpf_hip_octet_schedule",
+                             [I64, I, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_last_expand_schedule", [ctypes.POINTER(ctypes.c_int64)])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = types
         _lib = L
     if require_gpu:
         import torch
@@ -136,6 +144,44 @@ def clock_probe_read() -> dict:
     ghz, wg, mean_s = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
     check(load().dpf_hip_clock_probe_read(ctypes.byref(ghz), ctypes.byref(wg), ctypes.byref(mean_s)))
     return {"clock_ghz": ghz.value, "workgroups": wg.value, "mean_workgroup_ms": mean_s.value * 1e3}
+
+
+def clock_probe_exits() -> dict:
+    """When the waves of the last expand launch left the kernel, in ms after
+    its first workgroup began (call after one launch, before
+    clock_probe_read, which zeroes the stamps)."""
+    out = (ctypes.c_double * 6)()
+    check(load().dpf_hip_clock_probe_exits(out))
+    ms = [v * 1e3 for v in out[:5]]
+    return {"first_exit_ms": ms[0], "last_exit_ms": ms[1], "workgroup_last_exit_min_ms": ms[2],
+            "workgroup_last_exit_max_ms": ms[3], "workgroup_last_exit_mean_ms": ms[4],
+            "workgroups": int(out[5])}
+
+
+def octet_schedule(num_items: int, k0: int, subtree_depth: int, min_depth: int,
+                   compute_units: int) -> dict:
+    """The chunk schedule of a full-domain expand launch of that shape (no
+    GPU needed; reads the DPF_OCTET_* hooks): {"shift", "global", "counters",
+    "phases": [{"chunks", "first_item", "k0", "depth"}]}, phases in the order
+    they are taken; shift 0 is a static launch without phases."""
+    out = (ctypes.c_int64 * 15)()
+    check(load().dpf_hip_octet_schedule(num_items, k0, subtree_depth, min_depth, compute_units,
+                                        out))
+    return _plan(out)
+
+
+def last_expand_schedule() -> dict:
+    """The chunk schedule this thread's last expand launch ran with on its
+    device, as octet_schedule returns it (shift 0: a static launch)."""
+    out = (ctypes.c_int64 * 15)()
+    check(load().dpf_hip_last_expand_schedule(out))
+    return _plan(out)
+
+
+def _plan(out) -> dict:
+    phases = [{"chunks": out[3 + 4 * j], "first_item": out[4 + 4 * j], "k0": out[5 + 4 * j],
+               "depth": out[6 + 4 * j]} for j in range(3) if out[3 + 4 * j]]
+    return {"shift": out[0], "global": bool(out[1]), "counters": out[2], "phases": phases}
 
 
 def check(st: int):

@@ -205,6 +205,39 @@ const char* dpf_hip_last_expand_kernel(int* subtree_depth);
 int dpf_hip_clock_probe(int on);
 int dpf_hip_clock_probe_read(double* clock_ghz, int64_t* workgroups, double* mean_workgroup_s);
 
+/* Diagnostic: when the waves of the expand launches (octet and pair kernels)
+ * left the kernel.  While the probe is on, lane 0 of every wave folds its
+ * s_memrealtime exit stamp into the accumulator.  Waits for the device and
+ * writes six doubles, times in seconds after the first workgroup's begin
+ * stamp: out[0] first wave exit, out[1] last wave exit, out[2] / out[3] /
+ * out[4] the earliest / latest / mean of the workgroups' last exits, out[5]
+ * the number of workgroups seen (all zero when nothing was stamped).  The
+ * stamps are absolute, so the figures describe one launch: call it after
+ * each launch, then dpf_hip_clock_probe_read, which zeroes the accumulator
+ * (this call does not). */
+int dpf_hip_clock_probe_exits(double* out);
+
+/* The chunk schedule dpf_hip_expand gives a launch of `num_items` subtrees
+ * of depth `subtree_depth`, each `k0` levels below its start seed, with
+ * `compute_units` workgroups and the kernel's minimum subtree depth (3 for
+ * the octet kernel, 1 for the pair kernel); no device is touched, the
+ * DPF_OCTET_* environment hooks are read.  Writes 15 values: out[0] the
+ * levels taken off the subtrees for dynamic distribution (0: a static
+ * launch, the rest is zero), out[1] whether the launch has one chunk counter
+ * (else one per workgroup), out[2] the number of counters, then for each of
+ * the three phases, in the order they are taken, the number of 64-item
+ * chunks, the first item, the levels walked and the subtree depth of its
+ * items (out[3 + 4 j] ..).  A phase without chunks is absent. */
+int dpf_hip_octet_schedule(int64_t num_items, int k0, int subtree_depth, int min_depth,
+                           int compute_units, int64_t* out);
+
+/* Diagnostic: the chunk schedule the calling thread's last dpf_hip_expand
+ * launch of the octet or pair kernel really ran with on its device, in
+ * dpf_hip_octet_schedule's layout (out[0] == 0: a static launch, also when
+ * the tree-top pass could not start the items).  Tests use it to pin that a
+ * mode took the path it names. */
+int dpf_hip_last_expand_schedule(int64_t* out);
+
 /* Diagnostic: which kernel the calling thread's last
  * dpf_hip_eval_prefix_batch(_cached) launched: "hh_level" (the lean
  * heavy-hitters kernel: cached or gathered start seeds, two expanded levels,
