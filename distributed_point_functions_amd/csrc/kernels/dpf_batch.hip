@@ -764,8 +764,7 @@ int dpf_hip_gather_seeds_layout(int64_t num_keys, int64_t num_rows, const int64_
   if (gx > 64) gx = 64;
   // DPF_BATCH_GATHER_KEYS=1|2|4 (read per call; default 4): keys per lane and
   // pass, an A/B hook.
-  const char* kv = getenv("DPF_BATCH_GATHER_KEYS");
-  const int kpl = kv && (kv[0] == '1' || kv[0] == '2') ? kv[0] - '0' : 4;
+  const int kpl = hook_is("DPF_BATCH_GATHER_KEYS", '1') ? 1 : hook_is("DPF_BATCH_GATHER_KEYS", '2') ? 2 : 4;
   const int64_t ky = (num_keys + kpl - 1) / kpl;
   int64_t gy = ky < 65535 ? ky : 65535;
   if (gx * gy > 262144) gy = (262144 + gx - 1) / gx;
@@ -886,8 +885,8 @@ int dpf_hip_eval_prefix_batch_layout(
     p.num_starts = num_starts;
     p.waves_per_chunk = (num_starts + 63) / 64;
     // ~4 wave tasks per wave slot, 16 when they are taken dynamically.
-    const char* dyn = std::getenv("DPF_BATCH_DYNAMIC");
-    const int64_t want_waves = (int64_t)num_cus() * (kBlock / 64) * (dyn && dyn[0] == '0' ? 4 : 16);
+    const int64_t want_waves =
+        (int64_t)num_cus() * (kBlock / 64) * (hook_is("DPF_BATCH_DYNAMIC", '0') ? 4 : 16);
     int64_t chunks = (want_waves + p.waves_per_chunk - 1) / p.waves_per_chunk;
     if (chunks > num_keys) chunks = num_keys;
     if (chunks < 1) chunks = 1;
@@ -937,8 +936,7 @@ int dpf_hip_eval_prefix_batch_layout(
       p.leaf_seeds = leaf_cache;
       p.leaf_stride = leaf_stride;
       p.leaf_slot = leaf_slot;
-      const char* chk = getenv("DPF_HIP_CHECK_SLOTS");
-      if (leaf_slot && seeds_in && chk && chk[0] == '1') {
+      if (leaf_slot && seeds_in && hook_is("DPF_HIP_CHECK_SLOTS", '1')) {
         HIP_TRY(hipStreamSynchronize(s));
         if (int e = check_slot_table(num_starts, expand_levels, parent, leaf_slot, leaf_stride))
           return e;
@@ -953,8 +951,7 @@ int dpf_hip_eval_prefix_batch_layout(
     // or a gather, no walk, two expanded levels, IntModN<uint32_t> sums): the
     // lean kernel of dpf_batch_hh.hip.  DPF_BATCH_NO_LEAN=1 keeps the general
     // kernel (A/B and test hook).
-    const char* no_lean_env = getenv("DPF_BATCH_NO_LEAN");
-    const bool no_lean = no_lean_env && no_lean_env[0] == '1';
+    const bool no_lean = hook_is("DPF_BATCH_NO_LEAN", '1');
     if (sum && !no_lean && walk_levels == 0 && expand_levels == 2 && seeds_in &&
         elements_per_leaf == 1 && mod32_eligible(desc, &b) && nl <= 2 && (nl == 1 || b == 2)) {
       HHLevelArgs a;

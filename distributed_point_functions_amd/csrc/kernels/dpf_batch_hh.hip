@@ -736,8 +736,7 @@ int launch_hh_keys(const HHLevelArgs& a, hipStream_t s) {
   // 16 / 32 / 64, profiles/r16/hh_dynamic_ab.txt; DPF_HH_DYNAMIC=0 turns that
   // off): split the start nodes when there are few 64-key groups.
   // DPF_HH_DYNAMIC=<n>: n tasks per wave slot (A/B hook).
-  const char* dyn_env = std::getenv("DPF_HH_DYNAMIC");
-  const int per_slot = dyn_env && *dyn_env ? std::atoi(dyn_env) : 64;
+  const int per_slot = hook_int("DPF_HH_DYNAMIC", 64);
   const bool dynamic = per_slot > 0;
   const int64_t want_waves = (int64_t)num_cus() * (kHHKeysBlock / 64) * (dynamic ? per_slot : 4);
   int64_t ranges = (want_waves + groups - 1) / groups;
@@ -821,8 +820,7 @@ int launch_hh_level(const HHLevelArgs& a, hipStream_t s) {
   p.waves_per_chunk = (a.num_starts + 63) / 64;
   // ~4 tasks per wave slot, or DPF_HH_DYNAMIC (default 64) taken dynamically
   // (0: the fixed grid-stride share).
-  const char* dyn_env = std::getenv("DPF_HH_DYNAMIC");
-  const int per_slot = dyn_env && *dyn_env ? std::atoi(dyn_env) : 64;
+  const int per_slot = hook_int("DPF_HH_DYNAMIC", 64);
   const bool dynamic = per_slot > 0;
   const int64_t want_waves = (int64_t)num_cus() * (kBlock / 64) * (dynamic ? per_slot : 4);
   int64_t chunks = (want_waves + p.waves_per_chunk - 1) / p.waves_per_chunk;

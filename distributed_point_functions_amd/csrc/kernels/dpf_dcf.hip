@@ -376,10 +376,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_fast_quad_kernel(Dc
 }
 
 // DPF_DCF_QUAD=0 (read per launch) turns the latency mode off (A/B hook).
-bool dcf_quad_on() {
-  const char* v = getenv("DPF_DCF_QUAD");
-  return !(v && v[0] == '0');
-}
+bool dcf_quad_on() { return !hook_is("DPF_DCF_QUAD", '0'); }
 
 template <int BITS, bool XOR>
 void launch_dcf_fast(const DcfFastParams& p0, const DcfVcw& vc, hipStream_t s) {
@@ -475,8 +472,7 @@ extern "C" int dpf_hip_dcf_eval_batch(int64_t num_keys, int64_t points_per_key, 
   // the general kernel (parity tests run both).
   bool identity = true;
   for (int i = 0; i < num_levels; ++i) identity = identity && level_depth[i] == i;
-  const char* general = getenv("DPF_DCF_GENERAL");
-  if (fast && identity && !(general && general[0] == '1')) {
+  if (fast && identity && !hook_is("DPF_DCF_GENERAL", '1')) {
     DcfFastParams f;
     memset(&f, 0, sizeof(f));
     f.num_items = items;

@@ -1,5 +1,5 @@
 // dpf_device.h -- device-side building blocks shared by the gfx950 kernel
-// translation units (dpf_kernels.hip, dpf_batch.hip): the bank-replicated LDS
+// translation units (dpf_kernels.hip, dpf_batch.hip, dpf_batch_hh.hip, dpf_dcf.hip): the bank-replicated LDS
 // T-table AES, tree steps (distributed_point_function.cc:315-343,
 // evaluate_prg_hwy.cc:452-486), leaf conversion/correction (value_type_helpers.h,
 // int_mod_n.h) and the exact wide accumulators of the sum paths.
@@ -246,11 +246,11 @@ struct ExpandParams {
   char* out;
   RoundKeys rkl, rkr, rkv, rkd;
   // 0 = item u on thread u (grid stride); > 0 = the waves take the items 64
-  // at a time from a counter (dynamic distribution, dpf_kernels.hip):
+  // at a time from a counter (dynamic distribution, dpf_kernels.hip subtree_shape):
   // the launch's chunks of 64 undivided items per workgroup.
   int dyn_chunks;
   // Chunk schedule of a dynamic launch (dyn_chunks > 0; plan_chunks in
-  // dpf_kernels.hip, take_expand_chunk below).  The chunks are numbered in
+  // dpf_expand_plan.hip, take_expand_chunk below).  The chunks are numbered in
   // the order they are taken, in up to three phases: phase j's chunks are 64
   // items of shape (k0 + 2j, S - 2j), i.e. subtrees 4^j times smaller, so the
   // launch ends on small pieces of work.  ph_end[j] is the counter value at

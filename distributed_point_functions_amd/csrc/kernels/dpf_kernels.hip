@@ -21,18 +21,11 @@
 // All arithmetic is integer/bitwise; no MFMA (nothing here is a contraction).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
 
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <thread>
 #include <vector>
 #include <string>
 
@@ -495,7 +488,6 @@ struct PointParams {
 //     a level of <= 256 parents do that in quads.
 // Nodes live in nodes[] / tbits[] (<= 1024 per level, so D <= 11), read into
 // registers before a barrier and rewritten after it.
-constexpr int kSmallMaxD = 11;
 template <class Leaf> struct IsFastInt : std::false_type {};
 template <int BITS, bool XOR> struct IsFastInt<FastIntLeaf<BITS, XOR>> : std::true_type {};
 template <class Leaf>
@@ -800,6 +792,9 @@ int num_cus() {
   return cus;
 }
 
+int max_block() { return kBlock; }
+int max_subtree_depth() { return kSMax; }
+
 int block_for(int64_t work_items) {
   // A launch smaller than one full workgroup per CU runs LDS-bound on the few
   // CUs it occupies: give each CU a smaller workgroup instead (the tables cost
@@ -813,8 +808,7 @@ int block_for(int64_t work_items) {
 }
 
 int64_t dynamic_chunks_per_wg(int64_t items, int grid, int block, const char* env) {
-  const char* v = env ? std::getenv(env) : nullptr;
-  if (v && v[0] == '0') return 0;
+  if (env && hook_is(env, '0')) return 0;
   const int64_t chunks = (items + 63) / 64;
   if (chunks < (int64_t)grid * (block / 64) * 4) return 0;
   return (chunks + grid - 1) / grid;
@@ -879,26 +873,6 @@ void note_expand(const ExpandParams& p, bool octet) {
   g_last_expand_s = p.S;
 }
 
-// Latency mode for small trees (expand_small_kernel): num_starts << t
-// workgroups, t as large as keeps them within one per CU, and D = L - t
-// levels breadth-first in each; D must be 1..kSmallMaxD.  Returns false (and
-// launches nothing) when the tree does not fit that shape.  DPF_EXPAND_SMALL=0
-// (read per launch) turns it off: the A/B and test hook.
-bool small_on() {
-  const char* v = std::getenv("DPF_EXPAND_SMALL");
-  return !(v && v[0] == '0');
-}
-bool small_shape(int64_t num_starts, int num_levels, int* t, int* D) {
-  const int64_t cus = num_cus();
-  if (!small_on() || num_levels < 1 || num_starts < 1 || num_starts > cus) return false;
-  int tt = 0;
-  while (tt < num_levels - 1 && (num_starts << (tt + 1)) <= cus) ++tt;
-  const int d = num_levels - tt;
-  if (d < 1 || d > kSmallMaxD) return false;
-  *t = tt;
-  *D = d;
-  return true;
-}
 // Launches expand_small_kernel<Leaf> when the tree has the small shape.
 template <class Leaf>
 bool try_small(const ExpandParams& p0, const Leaf& leaf, hipStream_t s) {
@@ -927,11 +901,7 @@ bool try_small(const ExpandParams& p0, const Leaf& leaf, hipStream_t s) {
 // to its subtree root in lane quads, then up to 11 levels through LDS, every
 // node hashed once -- and writes the 2^k0-per-start item roots (17 B each,
 // stream-ordered scratch); the octet kernel then starts at them (k0 = 0).
-// DPF_EXPAND_TOP=0 (read per launch) keeps the per-lane walk.
-bool top_on() {
-  const char* v = std::getenv("DPF_EXPAND_TOP");
-  return !(v && v[0] == '0');
-}
+// top_shape (dpf_expand_plan.hip) says whether the pass applies and its shape.
 struct TopScratch {
   void* mem = nullptr;
   hipStream_t s = nullptr;
@@ -945,17 +915,8 @@ struct TopScratch {
 int expand_top(ExpandParams& p, hipStream_t s, TopScratch& scratch,
                unsigned int** counter = nullptr) {
   const int64_t starts = p.num_items >> p.k0;
-  // Few start seeds (full-domain calls and their shards): with many starts
-  // every item's walk is short and a workgroup per start would idle.
-  if (!top_on() || p.k0 < 8 || starts > num_cus() || p.num_items < 4 * (int64_t)num_cus())
-    return kOk;
-  // Workgroups: one per subtree at depth t under each start, at least one
-  // per CU; D = k0 - t levels breadth-first (1..kSmallMaxD).
-  int t = 0;
-  while ((starts << t) < num_cus() && t < p.k0 - 1) ++t;
-  if (p.k0 - t > kSmallMaxD) t = p.k0 - kSmallMaxD;
-  const int D = p.k0 - t;
-  if (D < 1 || (starts << t) > INT32_MAX) return kOk;
+  int t = 0, D = 0;
+  if (!top_shape(p.num_items, p.k0, &t, &D)) return kOk;
   static const bool pool_kept = [] {
     int dev = 0;
     hipMemPool_t pool;
@@ -997,97 +958,6 @@ int expand_top(ExpandParams& p, hipStream_t s, TopScratch& scratch,
   return kOk;
 }
 
-// Dynamic item distribution for the octet kernel (ExpandParams::dyn_chunks):
-// a launch with at least 4 items per thread of one full workgroup per CU
-// gets subtrees two levels shallower (4x the items, the two levels above
-// them done by the tree-top pass) so every wave can take several chunks of
-// 64 items from its workgroup's counter.  Applied only when the tree-top
-// pass starts the items (k0 = 0 after it): otherwise every item would walk
-// two more levels.  DPF_OCTET_DYNAMIC=0 (read per launch) keeps the static
-// one-item-per-thread shape, =<1..4> sets the levels taken off the subtrees
-// (2^that items per thread; A/B and test hook).  Default: 4 levels off
-// subtrees of >= 11 (config 2 15.00 vs 15.05-15.17 ms, config 3's uint128
-// shard 58.2 vs 60.9 ms, Tuple<IntModN32 x 2> 39.2 vs 40.9 ms), else 2 (the
-// 2^27 / 2^28 shards 1.96 / 3.82 ms at 2 vs 2.04 / 3.90 at 4; 3 was worse than
-// both everywhere; profiles/r16/octet_dynamic_ab.txt).
-int octet_dynamic_shift(int S) {
-  const char* v = std::getenv("DPF_OCTET_DYNAMIC");
-  if (!v || !*v) return S >= 11 ? 4 : 2;
-  const int k = std::atoi(v);
-  return k <= 0 ? 0 : (k > 4 ? 4 : k);
-}
-// Levels each dynamically taken item walks below the tree-top pass's roots
-// (DPF_OCTET_WALK=<n>, read per launch; 0: the pass goes down to the items).
-int octet_walk_levels() {
-  const char* v = std::getenv("DPF_OCTET_WALK");
-  if (!v || !*v) return 2;
-  const int k = std::atoi(v);
-  return k < 0 ? 0 : (k > 4 ? 4 : k);
-}
-// Who takes which chunk, and how the chunks shrink towards the end of the
-// launch (r17; ExpandParams::ph_end, take_expand_chunk).
-//   * One counter for all workgroups: with a fixed range per workgroup, a CU
-//     that starts late or runs slow finishes late and nobody takes its
-//     chunks.  DPF_OCTET_GLOBAL=0 (read per launch) keeps a counter and an
-//     equal share of every phase per workgroup (A/B and test hook).
-//   * Tapered chunks (guided self-scheduling): when the counter runs out
-//     every wave is somewhere inside a chunk, so the launch drains for up to
-//     one chunk's time on fewer and fewer waves -- launch / chunks-per-wave,
-//     a quarter of the 2^27 shard's launch at its 4 chunks per wave.  So the
-//     item range is cut into up to three phases, taken in order: phase j's
-//     items are subtrees of depth S - 2j (4^j times smaller) that walk 2j more
-//     levels from the same tree-top roots.  A phase hands over to the next
-//     finer one when at most DPF_OCTET_TAPER_AT (default 2) of its chunks
-//     per resident wave are left; a phase exists only while its depth is >=
-//     the kernel's minimum.  DPF_OCTET_TAPER=<0..2> (read per launch) caps
-//     the number of finer phases; 0: uniform chunks.
-// The plan is a pure function of the launch's shape, the CU count and the
-// hooks, exported as dpf_hip_octet_schedule for the CPU tests.
-int env_int(const char* name, int dflt, int lo, int hi) {
-  const char* v = std::getenv(name);
-  if (!v || !*v) return dflt;
-  const int k = std::atoi(v);
-  return k < lo ? lo : (k > hi ? hi : k);
-}
-}  // namespace
-namespace dpf_rt {
-ChunkPlan plan_chunks(int64_t num_items, int k0, int S, int min_S, int64_t cus, bool sched_ok) {
-  ChunkPlan c{};
-  const int sh = octet_dynamic_shift(S);
-  if (sh <= 0 || S - sh < min_S || k0 + sh > 62 || cus <= 0 || num_items <= 0 ||
-      num_items > (INT64_MAX >> (sh + 4)) || (num_items << sh) % (cus * 64) != 0 ||
-      (num_items << sh) < 4 * cus * kBlock || (num_items << sh) / 64 > (INT32_MAX >> 4))
-    return c;
-  c.shift = sh;
-  // Both are on by default from 2^20 leaf blocks per CU: measured against the
-  // parent build, 2^29 / 2^28 blocks ran 1.025x / 1.035x faster (15.31 vs
-  // 15.70 ms, 7.41 vs 7.67 ms), 2^27 / 2^26 blocks 0.7% / 4% slower (3.85 vs
-  // 3.82 ms, 2.01 vs 1.94 ms; at 2^26 each half alone was slower too), so the
-  // smaller launches keep a counter per workgroup and uniform chunks
-  // (profiles/r17/octet_taper_ab.txt).
-  const int big = sched_ok && (num_items << S) / cus >= ((int64_t)1 << 20);
-  c.global = env_int("DPF_OCTET_GLOBAL", big, 0, 1);
-  c.groups = c.global ? 1 : cus;
-  const int k = k0 + sh, s = S - sh;
-  const int64_t coarse = (num_items << sh) / 64;   // chunks of shape (k, s)
-  // Chunks (in phase 0's size) from each phase's start to the end of the
-  // launch: per resident wave `at` of phase 0's, then `at` of phase 1's.
-  const int finer = env_int("DPF_OCTET_TAPER", big ? 2 : 0, 0, 2);
-  const int64_t at = env_int("DPF_OCTET_TAPER_AT", 2, 1, 16) * cus * (kBlock / 64);
-  auto exists = [&](int j) { return j <= finer && s - 2 * j >= min_S && k + 2 * j <= 62; };
-  int64_t start[4] = {0, coarse, coarse, coarse};
-  if (exists(1)) start[1] = coarse - (coarse < at ? coarse : at);
-  if (exists(2)) start[2] = coarse - (coarse - start[1] < (at >> 2) ? coarse - start[1] : (at >> 2));
-  for (int j = 0; j < 3; ++j) {
-    c.k0[j] = k + 2 * j;
-    c.S[j] = s - 2 * j;
-    c.chunks[j] = (start[j + 1] - start[j]) << (2 * j);
-    c.first_item[j] = (start[j] * 64) << (2 * j);
-  }
-  return c;
-}
-}  // namespace dpf_rt
-namespace {
 // Runs the tree-top pass and sets p's shape (and *grid, *blk) for the octet
 // kernel launch.
 thread_local ChunkPlan g_last_plan{};   // dpf_hip_last_expand_schedule
@@ -1114,36 +984,31 @@ int subtree_shape(ExpandParams& p, int min_S, hipStream_t s, TopScratch& top, in
     }
     unsigned int* counter = nullptr;
     unsigned int** want_counter = plan.global ? &counter : nullptr;
-    // The tree-top pass stops `w` levels above the items (a quarter of the
-    // roots for w = 2: fewer rounds of its latency-bound workgroups), and
-    // every item walks those levels itself (one path step per level, in the
-    // octet kernel's throughput mode).
+    // The tree-top pass stops `up` levels above the items (a quarter of the
+    // roots for 2: fewer rounds of its latency-bound workgroups), and every
+    // item walks those levels itself (one path step per level, in the octet
+    // kernel's throughput mode).  Where it does not apply at that height, it
+    // is tried again down to the items (up = 0).
     const int w = octet_walk_levels();
-    if (w > 0 && q.k0 - w >= 8) {
-      ExpandParams t = q;
-      t.k0 = q.k0 - w;
-      t.S = q.S + w;
-      t.num_items = q.num_items >> w;
+    int up = w > 0 && q.k0 - w >= 8 ? w : 0;
+    ExpandParams t;
+    for (;; up = 0) {
+      t = q;
+      t.k0 = q.k0 - up;
+      t.S = q.S + up;
+      t.num_items = q.num_items >> up;
       if (int st = expand_top(t, s, top, want_counter)) return st;
-      if (t.k0 == 0) {
-        q.chunk_counter = counter;
-        q.seeds_in = t.seeds_in;
-        q.ctrl_in = t.ctrl_in;
-        q.cw_seed = t.cw_seed;
-        q.cw_left = t.cw_left;
-        q.cw_right = t.cw_right;
-        q.num_levels = q.S + w;
-        q.k0 = w;
-        p = q;
-        g_last_plan = plan;
-        *grid = (int)cus;
-        *blk = kBlock;
-        return kOk;
-      }
+      if (t.k0 == 0 || up == 0) break;
     }
-    if (int st = expand_top(q, s, top, want_counter)) return st;
-    if (q.k0 == 0) {
+    if (t.k0 == 0) {   // the pass ran: the items start `up` levels below its roots
       q.chunk_counter = counter;
+      q.seeds_in = t.seeds_in;
+      q.ctrl_in = t.ctrl_in;
+      q.cw_seed = t.cw_seed;
+      q.cw_left = t.cw_left;
+      q.cw_right = t.cw_right;
+      q.num_levels = q.S + up;
+      q.k0 = up;
       p = q;
       g_last_plan = plan;
       *grid = (int)cus;
@@ -1164,82 +1029,124 @@ template <> struct SchedDefault<SwarLeaf, true> { static constexpr bool value = 
 template <> struct SchedDefault<Mod32Leaf<kMod32MaxLeaves>, false> {
   static constexpr bool value = false;
 };
-template <class Leaf>
-int octet_shape(ExpandParams& p, hipStream_t s, TopScratch& top, int* grid, int* blk) {
-  return subtree_shape(p, 3, s, top, grid, blk, SchedDefault<Leaf, true>::value);
-}
 // Launches with one counter for the launch or with finer phases run the
 // kernels' SCHED instance; static launches and uniform chunks per workgroup
 // the one whose subtree shape is a launch constant.
 bool has_schedule(const ExpandParams& p) {
   return p.dyn_chunks && (p.chunk_counter || p.ph_end[0] != p.ph_end[2]);
 }
-template <class Leaf>
-void launch_octet_kernel(int grid, int blk, hipStream_t s, const ExpandParams& p, const Leaf& leaf) {
-  if (has_schedule(p))
-    hipLaunchKernelGGL((expand_octet_kernel<Leaf, true>), dim3(grid), dim3(blk), 0, s, p, leaf);
-  else
-    hipLaunchKernelGGL((expand_octet_kernel<Leaf, false>), dim3(grid), dim3(blk), 0, s, p, leaf);
-}
+// Leaf policies with an expand_octet_kernel instance: integer leaves (whole
+// 16-byte blocks only: dispatch_expand's octet_ok), SWAR tuples and pairs of
+// IntModN<uint32_t> (the half's four leaves hashed as two ILP4 groups).
+template <class Leaf> struct HasOctet : std::false_type {};
+template <int BITS, bool XOR> struct HasOctet<FastIntLeaf<BITS, XOR>> : std::true_type {};
+template <> struct HasOctet<SwarLeaf> : std::true_type {};
+template <> struct HasOctet<Mod32Leaf<2>> : std::true_type {};
 
+// The one launch path of full-domain expansion: the small-tree kernel where
+// the tree has that shape, else the octet kernel for leaf policies that have
+// one whenever the subtrees have >= 8 leaves (DPF_EXPAND_NO_OCTET=1, read per
+// launch, forces expand_kernel), else the pair kernel.  The latter two take
+// the shape subtree_shape gives them (tree-top pass, dynamic 64-item chunks):
+// subtrees of >= 3 levels for octets, >= 1 for leaf pairs.
 template <class Leaf>
-int launch_expand(const ExpandParams& p0, const Leaf& leaf, hipStream_t s) {
+int dispatch_expand(const ExpandParams& p0, const Leaf& leaf, bool octet_ok, hipStream_t s) {
+  TopScratch top;
   // GenericLeaf's conversion spills in the small kernel's register budget and
   // measured 0.93-1.07x there (profiles/r15_ab.txt part 13): not dispatched.
-  if (!std::is_same_v<Leaf, GenericLeaf> && try_small(p0, leaf, s)) {
-    HIP_TRY(hipGetLastError());
-    return kOk;
+  const bool small = !std::is_same_v<Leaf, GenericLeaf> && try_small(p0, leaf, s);
+  if (!small) {
+    const bool octet = HasOctet<Leaf>::value && octet_ok && p0.S >= 3 &&
+                       !hook_is("DPF_EXPAND_NO_OCTET", '1');
+    note_expand<Leaf>(p0, octet);
+    ExpandParams p = p0;
+    int grid = 0, blk = 0;
+    const bool sched_ok = octet ? SchedDefault<Leaf, true>::value : SchedDefault<Leaf, false>::value;
+    if (int st = subtree_shape(p, octet ? 3 : 1, s, top, &grid, &blk, sched_ok)) return st;
+    const bool sched = has_schedule(p);
+    if (octet) {
+      if constexpr (HasOctet<Leaf>::value) {
+        if (sched)
+          hipLaunchKernelGGL((expand_octet_kernel<Leaf, true>), dim3(grid), dim3(blk), 0, s, p, leaf);
+        else
+          hipLaunchKernelGGL((expand_octet_kernel<Leaf, false>), dim3(grid), dim3(blk), 0, s, p, leaf);
+      }
+    } else if (sched) {
+      hipLaunchKernelGGL((expand_kernel<Leaf, true>), dim3(grid), dim3(blk), 0, s, p, leaf);
+    } else {
+      hipLaunchKernelGGL((expand_kernel<Leaf, false>), dim3(grid), dim3(blk), 0, s, p, leaf);
+    }
   }
-  note_expand<Leaf>(p0, false);
-  // The octet kernel's shape (tree-top pass, dynamic 64-item chunks) with
-  // pair leaves: subtrees of >= 1 level.
-  ExpandParams p = p0;
-  TopScratch top;
-  int grid = 0, blk = 0;
-  if (int st = subtree_shape(p, 1, s, top, &grid, &blk, SchedDefault<Leaf, false>::value))
-    return st;
-  if (has_schedule(p))
-    hipLaunchKernelGGL((expand_kernel<Leaf, true>), dim3(grid), dim3(blk), 0, s, p, leaf);
-  else
-    hipLaunchKernelGGL((expand_kernel<Leaf, false>), dim3(grid), dim3(blk), 0, s, p, leaf);
   HIP_TRY(hipGetLastError());
   return kOk;
 }
 
-// The octet kernel takes integer leaves filling whole blocks whenever the
-// subtrees have >= 8 leaves (DPF_EXPAND_NO_OCTET=1 forces expand_kernel).
-template <int BITS, bool XOR>
-bool launch_octet(const ExpandParams& p0, const dpf_block* vcw, int E, int party, int store_bytes,
-                  hipStream_t s, int* st) {
-  const char* off = getenv("DPF_EXPAND_NO_OCTET");
-  if ((off && off[0] == '1') || store_bytes != 16 || p0.S < 3) return false;
-  note_expand<FastIntLeaf<BITS, XOR>>(p0, true);
-  ExpandParams p = p0;
-  TopScratch top;
-  int grid = 0, blk = 0;
-  if ((*st = octet_shape<FastIntLeaf<BITS, XOR>>(p, s, top, &grid, &blk)) != kOk) return true;
-  launch_octet_kernel(grid, blk, s, p, FastIntLeaf<BITS, XOR>{vcw, E, party, store_bytes, {}});
-  return true;
-}
-
+// The leaf policies of dpf_hip_expand, each built from the value descriptor
+// and dispatched.  Integer leaves (and uniform tuples as E * num_leaves
+// lanes): the octet kernel only where a leaf fills its whole 16-byte block.
 template <int BITS>
-int launch_expand_fast(const ExpandParams& p, const dpf_value_desc* d, const dpf_block* vcw,
-                       int E, int party, int store_bytes, hipStream_t s) {
-  if (d->kind[0] == DPF_LEAF_XOR ? try_small(p, FastIntLeaf<BITS, true>{vcw, E, party, store_bytes, {}}, s)
-                                 : try_small(p, FastIntLeaf<BITS, false>{vcw, E, party, store_bytes, {}}, s)) {
-    HIP_TRY(hipGetLastError());
-    return kOk;
+int expand_fast_leaf(const ExpandParams& p, bool xor_leaf, const dpf_block* vcw, int E, int party,
+                     int store_bytes, hipStream_t s) {
+  const bool octet_ok = store_bytes == 16;
+  if (xor_leaf)
+    return dispatch_expand(p, FastIntLeaf<BITS, true>{vcw, E, party, store_bytes, {}}, octet_ok, s);
+  return dispatch_expand(p, FastIntLeaf<BITS, false>{vcw, E, party, store_bytes, {}}, octet_ok, s);
+}
+int expand_fast(const ExpandParams& p, const dpf_value_desc* d, const dpf_block* vcw, int E,
+                int party, int store_bytes, hipStream_t s) {
+  const bool x = d->kind[0] == DPF_LEAF_XOR;
+  switch (d->bits[0]) {
+    case 8: return expand_fast_leaf<8>(p, x, vcw, E, party, store_bytes, s);
+    case 16: return expand_fast_leaf<16>(p, x, vcw, E, party, store_bytes, s);
+    case 32: return expand_fast_leaf<32>(p, x, vcw, E, party, store_bytes, s);
+    case 64: return expand_fast_leaf<64>(p, x, vcw, E, party, store_bytes, s);
+    default: return expand_fast_leaf<128>(p, x, vcw, E, party, store_bytes, s);
   }
-  int st = kOk;
-  if (d->kind[0] == DPF_LEAF_XOR ? launch_octet<BITS, true>(p, vcw, E, party, store_bytes, s, &st)
-                                 : launch_octet<BITS, false>(p, vcw, E, party, store_bytes, s, &st)) {
-    if (st != kOk) return st;
-    HIP_TRY(hipGetLastError());
-    return kOk;
+}
+// Direct tuples of plain integers / XorWrappers of mixed widths or kinds:
+// lane i of the hashed block is element i % num_leaves.
+SwarLeaf make_swar_leaf(const dpf_value_desc* desc, const dpf_block* vcw, int lanes, int party,
+                        int store_bytes) {
+  SwarLeaf w;
+  memset(&w, 0, sizeof(w));
+  w.vcw_elems = vcw;
+  w.lanes = lanes;
+  w.party = party;
+  w.store_bytes = store_bytes;
+  const int nl = desc->num_leaves;
+  int off = 0;
+  for (int i = 0; i < lanes; ++i) {
+    const int b = desc->bits[i % nl];
+    w.lane_off[i] = (uint8_t)off;
+    w.lane_bits[i] = (uint8_t)b;
+    w.top |= (u128)1 << (off + b - 1);
+    if (desc->kind[i % nl] == DPF_LEAF_XOR)
+      w.xmask |= (b >= 128 ? ~(u128)0 : (((u128)1 << b) - 1)) << off;
+    off += b;
   }
-  if (d->kind[0] == DPF_LEAF_XOR)
-    return launch_expand(p, FastIntLeaf<BITS, true>{vcw, E, party, store_bytes, {}}, s);
-  return launch_expand(p, FastIntLeaf<BITS, false>{vcw, E, party, store_bytes, {}}, s);
+  return w;
+}
+// Tuples of IntModN<uint32_t, N>: Moller-Granlund sampling.
+template <int NL>
+Mod32Leaf<NL> make_mod32_leaf(const dpf_value_desc* desc, const dpf_block* vcw, int b, int party) {
+  Mod32Leaf<NL> m;
+  memset(&m, 0, sizeof(m));
+  m.vcw_elems = vcw;
+  m.nl = desc->num_leaves;
+  m.b = b;
+  m.party = party;
+  for (int k = 0; k < desc->num_leaves; ++k) m.div[k] = make_div32((uint32_t)desc->mod_low[k]);
+  return m;
+}
+GenericLeaf make_generic_leaf(const dpf_value_desc* desc, const dpf_block* vcw, int party,
+                              int elements_per_leaf) {
+  GenericLeaf g;
+  g.d = *desc;
+  g.vcw = vcw;
+  g.party = party;
+  g.elements_per_leaf = elements_per_leaf;
+  g.esz = packed_size(desc);
+  return g;
 }
 
 // Integer leaves, four path chains per lane (ILP4): item u covers key grp and
@@ -1440,10 +1347,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void eval_points_quad_kernel
 }
 
 // DPF_POINTS_QUAD=0 (read per launch) turns the latency mode off (A/B hook).
-bool points_quad_on() {
-  const char* v = std::getenv("DPF_POINTS_QUAD");
-  return !(v && v[0] == '0');
-}
+bool points_quad_on() { return !hook_is("DPF_POINTS_QUAD", '0'); }
 // Launches of at most this many points run in latency mode: num_cus x 256 by
 // default, i.e. as many lane quads as one pass of 1024-thread workgroups on
 // every CU holds.  BatchEvaluation/10/40000 (40000 points per call) 2.54-2.63
@@ -1451,8 +1355,7 @@ bool points_quad_on() {
 // 1.01-1.17 vs 0.97-1.00 ms); profiles/r15_ab.txt part 19.
 // DPF_POINTS_QUAD_MAX=<points> (read per launch) moves the cut-over (A/B hook).
 int64_t points_quad_max() {
-  const char* v = std::getenv("DPF_POINTS_QUAD_MAX");
-  const long long m = v && *v ? std::strtoll(v, nullptr, 10) : 0;
+  const long long m = hook_long("DPF_POINTS_QUAD_MAX", 0);
   return m > 0 ? (int64_t)m : (int64_t)num_cus() * 256;
 }
 
@@ -1462,8 +1365,7 @@ int64_t points_quad_max() {
 // with 1024-thread workgroups (config 4: +0.7% per key, +1.4% summed over
 // keys, profiles/r14_ab.txt) and two otherwise.
 int points_ilp() {
-  const char* v = std::getenv("DPF_POINTS_ILP");
-  return v && (v[0] == '2' || v[0] == '4') ? v[0] - '0' : 0;
+  return hook_is("DPF_POINTS_ILP", '2') ? 2 : hook_is("DPF_POINTS_ILP", '4') ? 4 : 0;
 }
 thread_local const char* g_last_points_kernel = "";
 
@@ -1487,8 +1389,7 @@ int launch_points_t(const PointParams& pp, const Leaf& leaf, hipStream_t s) {
       // The shared top (profiles/r16/points_shared_top_ab.txt): summed over
       // keys 6 levels, 1236 vs 1275 ms; per key 4 levels (6 measured 1358 vs
       // 1258 ms, r16h).  DPF_POINTS_SHARED_TOP=0 turns it off (A/B hook).
-      const char* top = std::getenv("DPF_POINTS_SHARED_TOP");
-      const bool want_top = !(top && top[0] == '0');
+      const bool want_top = !hook_is("DPF_POINTS_SHARED_TOP", '0');
       p.top_levels = want_top && !p.seeds_in && p.num_levels >= 6 ? 6 : 0;
       if (p.top_levels)
         hipLaunchKernelGGL((eval_points4_kernel<BITS, true, SUM, true>), dim3(grid), dim3(blk), 0, s, p);
@@ -1668,34 +1569,9 @@ int dpf_hip_clock_probe_exits(double* out) {
   return kOk;
 }
 
-static void write_plan(const dpf_rt::ChunkPlan& c, int64_t* out) {
-  for (int i = 0; i < 15; ++i) out[i] = 0;
-  out[0] = c.shift;
-  if (!c.shift) return;
-  out[1] = c.global;
-  out[2] = c.groups;
-  for (int j = 0; j < 3; ++j) {
-    out[3 + 4 * j] = c.chunks[j];
-    out[4 + 4 * j] = c.first_item[j];
-    out[5 + 4 * j] = c.k0[j];
-    out[6 + 4 * j] = c.S[j];
-  }
-}
-
-int dpf_hip_octet_schedule(int64_t num_items, int k0, int subtree_depth, int min_depth,
-                           int compute_units, int64_t* out) {
-  if (!out) return fail(kInvalidArgument, "NULL pointer");
-  if (num_items < 1 || k0 < 0 || subtree_depth < 0 || k0 + subtree_depth > 62 ||
-      compute_units < 1)
-    return fail(kInvalidArgument, "launch shape out of range");
-  write_plan(dpf_rt::plan_chunks(num_items, k0, subtree_depth, min_depth, compute_units, true),
-             out);
-  return kOk;
-}
-
 int dpf_hip_last_expand_schedule(int64_t* out) {
   if (!out) return fail(kInvalidArgument, "NULL pointer");
-  write_plan(g_last_plan, out);
+  dpf_rt::write_plan(g_last_plan, out);
   return kOk;
 }
 
@@ -1714,649 +1590,6 @@ int dpf_hip_clock_probe_read(double* clock_ghz, int64_t* workgroups, double* mea
   return kOk;
 }
 
-int dpf_hip_device_count(int* count) {
-  HIP_TRY(hipGetDeviceCount(count));
-  return kOk;
-}
-int dpf_hip_set_device(int device) {
-  HIP_TRY(hipSetDevice(device));
-  return kOk;
-}
-}  // extern "C"
-
-namespace {
-// Large copies between the device and pageable host memory: the runtime pins
-// the user pages for each such copy, which measured ~28 ms per call for
-// 4-128 MiB (tools/dpf_benchmark, BM_EvaluateRegularDpf at 2^22+ outputs)
-// against ~0.3 ms for 16 MiB through page-locked memory.  They go through two
-// page-locked 16 MiB bounce buffers instead, the DMA of one chunk overlapping
-// the host copy of the other.
-constexpr size_t kBounceMin = size_t{2} << 20;
-constexpr size_t kBounceChunk = size_t{16} << 20;
-
-// memcpy on up to 8 host threads for pieces of >= 2 MiB (the host side of a
-// bounce runs at ~28 GB/s on 8 threads vs ~5 on one, page faults included).
-void host_copy(void* dst, const void* src, size_t bytes) {
-  const size_t piece = size_t{2} << 20;
-  size_t t = bytes / piece;
-  static const size_t hw = [] {
-    const char* e = std::getenv("DPF_HOST_THREADS");   // as host_util.h HostThreads()
-    const int v = e ? std::atoi(e) : 0;
-    return v >= 1 ? static_cast<size_t>(v) : static_cast<size_t>(std::thread::hardware_concurrency());
-  }();
-  if (t > 8) t = 8;
-  if (hw && t > hw) t = hw;
-  if (t <= 1) {
-    memcpy(dst, src, bytes);
-    return;
-  }
-  std::vector<std::thread> pool;
-  for (size_t i = 0; i < t; ++i) {
-    const size_t lo = bytes * i / t, hi = bytes * (i + 1) / t;
-    pool.emplace_back([=] { memcpy((char*)dst + lo, (const char*)src + lo, hi - lo); });
-  }
-  for (auto& th : pool) th.join();
-}
-std::mutex g_bounce_mu;
-char* g_bounce[2] = {nullptr, nullptr};
-
-bool page_locked(const void* p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeHost || a.type == hipMemoryTypeDevice ||
-         a.type == hipMemoryTypeManaged;
-}
-
-int bounce_buffers() {
-  for (auto& b : g_bounce)
-    if (!b) HIP_TRY(hipHostMalloc((void**)&b, kBounceChunk, hipHostMallocDefault));
-  return kOk;
-}
-
-int bounce_d2h(void* dst, const void* src, size_t bytes, void* stream) {
-  std::lock_guard<std::mutex> lock(g_bounce_mu);
-  if (int rc = bounce_buffers()) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n = (bytes + kBounceChunk - 1) / kBounceChunk;
-  auto len = [&](size_t i) { return i + 1 < n ? kBounceChunk : bytes - i * kBounceChunk; };
-  HIP_TRY(hipMemcpyAsync(g_bounce[0], src, len(0), hipMemcpyDeviceToHost, s));
-  for (size_t i = 0; i < n; ++i) {
-    HIP_TRY(hipStreamSynchronize(s));   // chunk i is in g_bounce[i & 1]
-    if (i + 1 < n)
-      HIP_TRY(hipMemcpyAsync(g_bounce[(i + 1) & 1], (const char*)src + (i + 1) * kBounceChunk,
-                             len(i + 1), hipMemcpyDeviceToHost, s));
-    host_copy((char*)dst + i * kBounceChunk, g_bounce[i & 1], len(i));
-  }
-  return kOk;
-}
-
-// Large copies to or from pageable host memory: register the host range for
-// the copy (16 ms for 8 GiB of mapped pages, tools/host_output_microbench.cc)
-// and DMA straight into / out of it at the link rate (57 GB/s vs ~12 through
-// the bounce buffers); the bounce path stays as the fallback when the
-// registration is refused.
-// Registering a fresh range (and unmapping it after) costs more than the
-// page-locked staging below ~0.5 GiB (tools/fresh_output_microbench.cc,
-// profiles/r14_fresh_output_microbench.jsonl): 32 MiB 4.5 vs 3.9 ms, 256 MiB
-// 26.3 vs 25.9 ms; at 8 GiB the DMA straight into the range wins (42 vs ~28 GB/s).
-constexpr size_t kRegisterMin = DPF_HIP_REGISTER_MIN_BYTES;
-// The 512 MiB threshold prices the page faults of FRESH destinations.  A host
-// range whose pages are already mapped -- every H2D source, and D2H
-// destinations the caller has touched -- costs ~2 us/MiB to register (16 ms
-// for 8 GiB, tools/host_output_microbench.cc) against a DMA at ~57 GB/s
-// instead of ~12 GB/s through the bounce buffers, so those register from
-// 32 MiB (the r13 threshold); profiles/r15_ab.txt (3), r15_mapped_register_ab.jsonl.
-// DPF_HIP_REGISTER_MAPPED_MIB=<n> (read per call) overrides it: the A/B hook.
-size_t register_min_mapped() {
-  const char* v = std::getenv("DPF_HIP_REGISTER_MAPPED_MIB");
-  const long m = v && *v ? std::strtol(v, nullptr, 10) : 0;
-  return m > 0 ? static_cast<size_t>(m) << 20 : size_t{32} << 20;
-}
-// First, middle and last page of [p, p + bytes) resident (mincore): the
-// range was touched before, so registering it maps no fresh pages.
-bool pages_mapped(const void* p, size_t bytes) {
-  const uintptr_t pg = 4096, lo = reinterpret_cast<uintptr_t>(p);
-  for (uintptr_t a : {lo, lo + bytes / 2, lo + bytes - 1}) {
-    unsigned char v = 0;
-    if (mincore(reinterpret_cast<void*>(a & ~(pg - 1)), pg, &v) != 0 || !(v & 1)) return false;
-  }
-  return true;
-}
-constexpr size_t kStagedChunk = size_t{64} << 20;
-
-// The library's own transient registrations, reference-counted: a second
-// thread copying from or into a range another thread has registered for its
-// copy shares that registration (page_locked() would report the range as
-// page-locked and a plain async copy could outlive the first thread's
-// hipHostUnregister); the last user unregisters.  A request that overlaps a
-// registration without lying inside it takes the bounce path.
-struct Registration {
-  size_t bytes;
-  int users;
-};
-std::mutex g_reg_mu;
-std::map<uintptr_t, Registration> g_regs;   // base address -> registration
-std::atomic<int> g_reg_count{0};            // g_regs.size(), readable without the lock
-
-// Covers [p, p + bytes) with a library registration held by the caller (to be
-// released with release_host(*base)): an existing one that contains the range,
-// or -- for new ranges of >= kRegisterMin unless `reuse_only` -- a fresh one.
-enum Acquire { kNotOurs, kAcquired, kOverlaps };
-// kOverlaps: part of the range is in a registration of ours -- the copy must
-// take the bounce path (HIP would take the partly registered range as
-// page-locked).  kNotOurs: use the page-locked test / bounce path.
-Acquire acquire_host(void* p, size_t bytes, bool reuse_only, uintptr_t* base,
-                     size_t min_bytes = kRegisterMin) {
-  const uintptr_t lo = reinterpret_cast<uintptr_t>(p), hi = lo + bytes;
-  std::lock_guard<std::mutex> lock(g_reg_mu);
-  auto it = g_regs.upper_bound(lo);
-  if (it != g_regs.begin()) {
-    auto prev = std::prev(it);
-    if (prev->first + prev->second.bytes > lo) {          // overlaps the one below
-      if (prev->first + prev->second.bytes >= hi) {        // contains the range
-        ++prev->second.users;
-        *base = prev->first;
-        return kAcquired;
-      }
-      return kOverlaps;
-    }
-  }
-  if (it != g_regs.end() && it->first < hi) return kOverlaps;  // overlaps the one above
-  if (reuse_only || bytes < min_bytes) return kNotOurs;
-  if (hipHostRegister(p, bytes, hipHostRegisterDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    return kNotOurs;
-  }
-  g_regs[lo] = Registration{bytes, 1};
-  g_reg_count.store(static_cast<int>(g_regs.size()));
-  *base = lo;
-  return kAcquired;
-}
-
-// True if [lo, hi) overlaps a registration of ours (g_reg_mu held).
-bool overlaps_registration(uintptr_t lo, uintptr_t hi) {
-  auto it = g_regs.upper_bound(lo);
-  if (it != g_regs.begin()) {
-    auto prev = std::prev(it);
-    if (prev->first + prev->second.bytes > lo) return true;
-  }
-  return it != g_regs.end() && it->first < hi;
-}
-
-void release_host(uintptr_t base) {
-  std::lock_guard<std::mutex> lock(g_reg_mu);
-  auto it = g_regs.find(base);
-  if (it == g_regs.end() || --it->second.users > 0) return;
-  (void)hipHostUnregister(reinterpret_cast<void*>(base));
-  g_regs.erase(it);
-  g_reg_count.store(static_cast<int>(g_regs.size()));
-}
-
-// Copies chunk by chunk on `s`, calling before(ctx, end) ahead of each chunk's
-// DMA (D2H: the destination chunk becomes valid while the previous chunk's
-// DMA runs).  `h` lies in the registration acquired at `base`, released here.
-int registered_copy(char* h, char* d, size_t bytes, bool to_host, void (*before)(void*, size_t),
-                    void* ctx, hipStream_t s, uintptr_t base) {
-  int rc = kOk;
-  for (size_t off = 0; off < bytes && rc == kOk; off += kStagedChunk) {
-    const size_t len = bytes - off < kStagedChunk ? bytes - off : kStagedChunk;
-    if (before) before(ctx, off + len);
-    const hipError_t e = to_host ? hipMemcpyAsync(h + off, d + off, len, hipMemcpyDeviceToHost, s)
-                                 : hipMemcpyAsync(d + off, h + off, len, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (registered host memory)");
-  }
-  const hipError_t e = hipStreamSynchronize(s);
-  if (rc == kOk && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-  release_host(base);
-  return rc;
-}
-
-// Maps the pages of fresh host storage [p, p + bytes) by touching one byte per
-// 4 KiB page on up to `threads` threads (a one-thread first touch of a fresh
-// 8 GiB vector costs ~350 ms of page faults, tools/host_output_microbench.cc;
-// registering unmapped pages would fault them in on one thread too).
-void prefault(char* p, size_t bytes, int threads) {
-  constexpr size_t kPage = 4096;
-  const size_t pages = bytes / kPage + 1;
-  size_t t = bytes >> 24;   // one thread per 16 MiB
-  if (t > static_cast<size_t>(threads)) t = threads;
-  auto touch = [p, bytes](size_t lo, size_t hi) {
-    volatile char* v = p;
-    for (size_t i = lo; i < hi; ++i)
-      if (i * kPage < bytes) v[i * kPage] = 0;
-  };
-  if (t <= 1) {
-    touch(0, pages);
-    return;
-  }
-  std::vector<std::thread> pool;
-  size_t done = 0;   // ranges [0, done) handed to threads
-  try {
-    for (; done < t; ++done) pool.emplace_back(touch, pages * done / t, pages * (done + 1) / t);
-  } catch (...) {
-    // No thread to spare: the rest on this one.
-  }
-  if (done < t) touch(pages * done / t, pages);
-  for (auto& th : pool) th.join();
-}
-
-// A fresh destination of >= kRegisterMin is mapped and registered piece by
-// piece behind the DMA (see piece_bytes below for the piece sizes).
-// DPF_HIP_D2H_PIPELINE=0 (read per call) maps and registers the whole range
-// before the first DMA instead (the r13 path): the A/B and test hook.
-constexpr size_t kPipelineMax = size_t{16} << 30;   // above: a few large pieces
-bool d2h_pipeline_on(size_t) {
-  const char* v = std::getenv("DPF_HIP_D2H_PIPELINE");
-  return !(v && v[0] == '0');
-}
-// DPF_HIP_D2H_REGISTER_PIECES=<n> (read per call): the pipelined copy acts as
-// if the registration of its piece n (and every later one) were refused -- a
-// test hook for the bounce fallback of the rest of the range.
-long register_pieces_limit() {
-  const char* v = std::getenv("DPF_HIP_D2H_REGISTER_PIECES");
-  return v && *v ? std::strtol(v, nullptr, 10) : -1;
-}
-
-// A fresh pageable destination of >= kRegisterMin (no registration of ours
-// overlaps it): a helper thread maps (prefault, 8 threads) and registers it in
-// pieces (256 MiB, or 1/32 of the range) while this thread initialises (before) and DMAs the pieces
-// already registered, so the ~45 ms of mapping and registering 8 GiB runs
-// under the DMA instead of ahead of it.  Piece boundaries are 2 MiB-aligned
-// (no page in two registrations) and every DMA chunk lies in one piece.  A
-// piece whose registration is refused, and everything after it, goes through
-// the bounce buffers.
-constexpr size_t kPiece = size_t{256} << 20;
-constexpr int kNoHelperThread = -1000;   // pipelined_d2h could not start its helper
-// Up to kPipelineMax: ~32 pieces (256 MiB up to 8 GiB; 8 GiB copies 164-171
-// ms pipelined vs 199-209 ms registered whole).  Above it, 8 GiB pieces: a
-// 32 GiB copy (config 3's 2^31 uint128) in 33 or 129 pieces ran its DMA at
-// ~13 GB/s in 1 of 4 calls (r14) and 3 of 6 (r15), in 5 pieces never in 6
-// calls (3 pieces: never in 6), 682-758 ms per copy against 801-938 ms
-// registered whole first (profiles/r15_ab.txt part 12).  A/B hooks (read per
-// call): DPF_HIP_D2H_PIECE_MIB (a multiple of 64) and
-// DPF_HIP_D2H_PREFAULT_THREADS (default 8).
-
-size_t piece_bytes(size_t bytes) {
-  const char* v = std::getenv("DPF_HIP_D2H_PIECE_MIB");
-  const long m = v && *v ? std::strtol(v, nullptr, 10) : 0;
-  if (m >= 64 && m % 64 == 0) return static_cast<size_t>(m) << 20;
-  const size_t step = size_t{64} << 20;
-  if (bytes > kPipelineMax) return size_t{8} << 30;
-  const size_t want = (bytes / 32 + step - 1) / step * step;
-  return want > kPiece ? want : kPiece;
-}
-int prefault_threads() {
-  const char* v = std::getenv("DPF_HIP_D2H_PREFAULT_THREADS");
-  const long t = v && *v ? std::strtol(v, nullptr, 10) : 0;
-  return t >= 1 && t <= 64 ? static_cast<int>(t) : 8;
-}
-
-// With parts (nparts > 0) the DMAs run on `s` = a copy stream of their own:
-// [0, ends[j]) of `d` is ready once events[j] (recorded on the producing
-// stream) has completed, and each chunk's DMA waits on the device for the
-// first part that covers it, so the copy of part j overlaps the work that
-// produces the later parts.
-int pipelined_d2h(char* h, const char* d, size_t bytes, void (*before)(void*, size_t), void* ctx,
-                  hipStream_t s, int nparts = 0, void* const* events = nullptr,
-                  const size_t* ends = nullptr) {
-  const uintptr_t h0 = reinterpret_cast<uintptr_t>(h), h1 = h0 + bytes;
-  const size_t piece = piece_bytes(bytes);
-  const int pf_threads = prefault_threads();
-  std::vector<uintptr_t> cut{h0};   // piece i = [cut[i], cut[i + 1])
-  for (uintptr_t c = (h0 + piece) & ~((uintptr_t{2} << 20) - 1); c < h1; c += piece)
-    if (c > cut.back()) cut.push_back(c);
-  cut.push_back(h1);
-  const size_t n = cut.size() - 1;
-  std::vector<int> state(n, 0);   // 0 pending, 1 registered (in g_regs), -1 refused
-  std::mutex mu;
-  std::condition_variable cv;
-  std::atomic<bool> stop{false};
-  int device = 0;
-  (void)hipGetDevice(&device);
-  const long limit = register_pieces_limit();
-  // DPF_HIP_D2H_TRACE=1: per-call seconds spent mapping, registering and
-  // waiting for the helper thread, on stderr (a diagnostic).
-  const bool trace = std::getenv("DPF_HIP_D2H_TRACE") != nullptr;
-  using clk = std::chrono::steady_clock;
-  double t_fault = 0, t_reg = 0, t_wait = 0, t_before = 0;
-  const auto t_start = clk::now();
-  std::thread worker;
-  auto helper = [&] {
-    (void)hipSetDevice(device);
-    for (size_t i = 0; i < n && !stop.load(); ++i) {
-      char* p = reinterpret_cast<char*>(cut[i]);
-      const size_t len = cut[i + 1] - cut[i];
-      const auto a = clk::now();
-      prefault(p, len, pf_threads);
-      const auto b = clk::now();
-      int st = -1;
-      if (limit >= 0 && static_cast<long>(i) >= limit) {
-        // test hook: refused
-      } else {
-        // Under g_reg_mu from the overlap check to the insert: another thread
-        // may have registered part of this piece since acquire_host said
-        // kNotOurs.  An overlapping piece is refused (the bounce path).
-        std::lock_guard<std::mutex> lock(g_reg_mu);
-        if (!overlaps_registration(cut[i], cut[i + 1])) {
-          if (hipHostRegister(p, len, hipHostRegisterDefault) == hipSuccess) {
-            g_regs[cut[i]] = Registration{len, 1};
-            g_reg_count.store(static_cast<int>(g_regs.size()));
-            st = 1;
-          } else {
-            (void)hipGetLastError();
-          }
-        }
-      }
-      t_fault += std::chrono::duration<double>(b - a).count();
-      t_reg += std::chrono::duration<double>(clk::now() - b).count();
-      {
-        std::lock_guard<std::mutex> lock(mu);
-        state[i] = st;
-      }
-      cv.notify_all();
-      if (st < 0) break;
-    }
-  };
-  try {
-    worker = std::thread(helper);
-  } catch (...) {
-    return kNoHelperThread;   // nothing done yet: the caller copies another way
-  }
-  int rc = kOk;
-  int waited = -1;   // parts whose event `s` already waits for: [0, waited]
-  auto wait_parts = [&](size_t end) {
-    int j = waited + 1;
-    while (j < nparts - 1 && ends[j] < end) ++j;
-    if (j >= nparts || j <= waited) return;
-    const hipError_t e = hipStreamWaitEvent(s, (hipEvent_t)events[j], 0);
-    if (e != hipSuccess) rc = hip_fail(e, "hipStreamWaitEvent");
-    waited = j;
-  };
-  size_t i = 0;
-  for (; i < n && rc == kOk; ++i) {
-    int st;
-    {
-      const auto w = clk::now();
-      std::unique_lock<std::mutex> lock(mu);
-      cv.wait(lock, [&] { return state[i] != 0; });
-      st = state[i];
-      t_wait += std::chrono::duration<double>(clk::now() - w).count();
-    }
-    if (st < 0) break;
-    for (uintptr_t off = cut[i]; off < cut[i + 1] && rc == kOk; off += kStagedChunk) {
-      const size_t len = cut[i + 1] - off < kStagedChunk ? cut[i + 1] - off : kStagedChunk;
-      wait_parts(off + len - h0);
-      if (rc != kOk) break;
-      if (before) {
-        // The helper thread must be joined on every path out of here.
-        try {
-          const auto bt = clk::now();
-          before(ctx, off + len - h0);
-          t_before += std::chrono::duration<double>(clk::now() - bt).count();
-        } catch (...) {
-          rc = fail(kInternal, "dpf_hip_memcpy_d2h_staged: before_chunk threw");
-          break;
-        }
-      }
-      const hipError_t e = hipMemcpyAsync(reinterpret_cast<char*>(off), d + (off - h0), len,
-                                          hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (registered host memory)");
-    }
-  }
-  stop.store(true);
-  worker.join();
-  if (rc == kOk && i < n) {
-    // Registration refused from piece i on: the rest through the bounce buffers.
-    const size_t off = cut[i] - h0;
-    prefault(h + off, bytes - off, 8);
-    try {
-      if (before) before(ctx, bytes);
-    } catch (...) {
-      rc = fail(kInternal, "dpf_hip_memcpy_d2h_staged: before_chunk threw");
-    }
-    if (rc == kOk) wait_parts(bytes);
-    if (rc == kOk) rc = bounce_d2h(h + off, d + off, bytes - off, s);
-  }
-  const auto t_issue = clk::now();
-  const hipError_t e = hipStreamSynchronize(s);
-  if (rc == kOk && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-  const auto t_sync = clk::now();
-  for (size_t j = 0; j < n; ++j)
-    if (state[j] > 0) release_host(cut[j]);
-  if (trace)
-    fprintf(stderr, "[pipelined_d2h] %zu MiB in %zu pieces: total %.1f ms, map %.1f ms, register "
-            "%.1f ms (helper), wait %.1f ms, before_chunk %.1f ms, issue %.1f ms, final sync "
-            "%.1f ms, unregister %.1f ms\n", bytes >> 20, n,
-            1e3 * std::chrono::duration<double>(clk::now() - t_start).count(), 1e3 * t_fault,
-            1e3 * t_reg, 1e3 * t_wait, 1e3 * t_before,
-            1e3 * std::chrono::duration<double>(t_issue - t_start).count(),
-            1e3 * std::chrono::duration<double>(t_sync - t_issue).count(),
-            1e3 * std::chrono::duration<double>(clk::now() - t_sync).count());
-  return rc;
-}
-
-int bounce_h2d(void* dst, const void* src, size_t bytes, void* stream) {
-  std::lock_guard<std::mutex> lock(g_bounce_mu);
-  if (int rc = bounce_buffers()) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n = (bytes + kBounceChunk - 1) / kBounceChunk;
-  for (size_t i = 0; i < n; ++i) {
-    const size_t l = i + 1 < n ? kBounceChunk : bytes - i * kBounceChunk;
-    if (i >= 2) HIP_TRY(hipStreamSynchronize(s));   // chunk i - 2 has left g_bounce[i & 1]
-    host_copy(g_bounce[i & 1], (const char*)src + i * kBounceChunk, l);
-    HIP_TRY(hipMemcpyAsync((char*)dst + i * kBounceChunk, g_bounce[i & 1], l,
-                           hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return kOk;
-}
-}  // namespace
-
-extern "C" {
-
-int dpf_hip_alloc(void** ptr, size_t bytes) {
-  if (!ptr) return fail(kInvalidArgument, "ptr is NULL");
-  *ptr = nullptr;
-  if (bytes == 0) bytes = 1;
-  const hipError_t e = hipMalloc(ptr, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // an allocation failure must not fail the next launch check
-    *ptr = nullptr;
-  }
-  HIP_TRY(e);
-  return kOk;
-}
-int dpf_hip_mem_info(size_t* free_bytes, size_t* total_bytes) {
-  if (!free_bytes || !total_bytes) return fail(kInvalidArgument, "NULL pointer");
-  HIP_TRY(hipMemGetInfo(free_bytes, total_bytes));
-  return kOk;
-}
-int dpf_hip_free(void* ptr) {
-  if (ptr) HIP_TRY(hipFree(ptr));
-  return kOk;
-}
-int dpf_hip_memcpy_h2d(void* dst, const void* src, size_t bytes, void* stream) {
-  if (!bytes) return kOk;
-  uintptr_t base = 0;
-  if (bytes >= kBounceMin || g_reg_count.load() > 0) {
-    // Inside a registration of ours (another thread's copy), or large and new.
-    const Acquire a = acquire_host(const_cast<void*>(src), bytes,
-                                   bytes < kBounceMin || page_locked(src), &base,
-                                   register_min_mapped());
-    if (a == kAcquired)
-      return registered_copy((char*)const_cast<void*>(src), (char*)dst, bytes, false, nullptr,
-                             nullptr, (hipStream_t)stream, base);
-    if (a == kOverlaps || (bytes >= kBounceMin && !page_locked(src)))
-      return bounce_h2d(dst, src, bytes, stream);
-  }
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_host_alloc(void** ptr, size_t bytes) {
-  if (!ptr) return fail(kInvalidArgument, "ptr is NULL");
-  *ptr = nullptr;
-  if (bytes == 0) bytes = 1;
-  HIP_TRY(hipHostMalloc(ptr, bytes, hipHostMallocDefault));
-  return kOk;
-}
-int dpf_hip_host_free(void* ptr) {
-  if (ptr) HIP_TRY(hipHostFree(ptr));
-  return kOk;
-}
-int dpf_hip_memcpy_h2d_async(void* dst, const void* src, size_t bytes, void* stream) {
-  if (!bytes) return kOk;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_memcpy_d2h(void* dst, const void* src, size_t bytes, void* stream) {
-  if (!bytes) return kOk;
-  uintptr_t base = 0;
-  if (bytes >= kBounceMin || g_reg_count.load() > 0) {
-    const bool reuse_only = bytes < kBounceMin || page_locked(dst);
-    const Acquire a =
-        acquire_host(dst, bytes, reuse_only, &base,
-                     !reuse_only && pages_mapped(dst, bytes) ? register_min_mapped() : kRegisterMin);
-    if (a == kAcquired)
-      return registered_copy((char*)dst, (char*)const_cast<void*>(src), bytes, true, nullptr,
-                             nullptr, (hipStream_t)stream, base);
-    if (a == kOverlaps || (bytes >= kBounceMin && !page_locked(dst)))
-      return bounce_d2h(dst, src, bytes, stream);
-  }
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_memcpy_d2h_strided(void* dst, const void* src, size_t elem_bytes,
-                               size_t src_stride_bytes, int64_t count, void* stream) {
-  if (count < 0 || src_stride_bytes < elem_bytes) return fail(kInvalidArgument, "bad sizes");
-  if (count == 0 || elem_bytes == 0) return kOk;
-  if (!dst || !src) return fail(kInvalidArgument, "NULL pointer");
-  HIP_TRY(hipMemcpy2DAsync(dst, elem_bytes, src, src_stride_bytes, elem_bytes, (size_t)count,
-                           hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_memcpy_d2h_staged(void* dst, const void* src, size_t bytes,
-                              void (*before_chunk)(void* ctx, size_t bytes_ready), void* ctx,
-                              void* stream) {
-  return dpf_hip_memcpy_d2h_staged_after(dst, src, bytes, before_chunk, ctx, 0, nullptr, nullptr,
-                                         stream);
-}
-int dpf_hip_memcpy_d2h_staged_after(void* dst, const void* src, size_t bytes,
-                                    void (*before_chunk)(void* ctx, size_t bytes_ready), void* ctx,
-                                    int num_parts, void* const* part_events,
-                                    const size_t* part_end_bytes, void* stream) {
-  if (num_parts < 0 || (num_parts > 0 && (!part_events || !part_end_bytes)))
-    return fail(kInvalidArgument, "dpf_hip_memcpy_d2h_staged_after: bad parts");
-  for (int j = 0; j < num_parts; ++j)
-    if (!part_events[j] || (j > 0 && part_end_bytes[j] < part_end_bytes[j - 1]) ||
-        (j == num_parts - 1 && part_end_bytes[j] < bytes))
-      return fail(kInvalidArgument, "dpf_hip_memcpy_d2h_staged_after: bad parts");
-  // Every path but the pipelined one copies on `stream`, after all its parts.
-  if (!before_chunk) return dpf_hip_memcpy_d2h(dst, src, bytes, stream);
-  uintptr_t base = 0;
-  if (bytes >= kRegisterMin) {
-    const bool locked = page_locked(dst);
-    // An existing registration of ours that contains the range is shared;
-    // a fresh pageable range is mapped and registered piece by piece.
-    const Acquire a = acquire_host(dst, bytes, true, &base);
-    if (a == kAcquired)
-      return registered_copy((char*)dst, (char*)const_cast<void*>(src), bytes, true, before_chunk,
-                             ctx, (hipStream_t)stream, base);
-    if (a == kNotOurs && !locked) {
-      if (d2h_pipeline_on(bytes)) {
-        int rc;
-        if (num_parts == 0) {
-          rc = pipelined_d2h((char*)dst, (const char*)src, bytes, before_chunk, ctx,
-                             (hipStream_t)stream);
-        } else {
-          hipStream_t copy;
-          HIP_TRY(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
-          rc = pipelined_d2h((char*)dst, (const char*)src, bytes, before_chunk, ctx, copy,
-                             num_parts, part_events, part_end_bytes);
-          (void)hipStreamDestroy(copy);
-        }
-        if (rc != kNoHelperThread) return rc;
-        // No helper thread: map and register the whole range first.
-      }
-      using clk = std::chrono::steady_clock;
-      const auto t0 = clk::now();
-      prefault((char*)dst, bytes, 16);
-      const auto t1 = clk::now();
-      if (acquire_host(dst, bytes, false, &base) == kAcquired) {
-        const auto t2 = clk::now();
-        const int rc = registered_copy((char*)dst, (char*)const_cast<void*>(src), bytes, true,
-                                       before_chunk, ctx, (hipStream_t)stream, base);
-        if (std::getenv("DPF_HIP_D2H_TRACE"))
-          fprintf(stderr, "[whole_d2h] %zu MiB: total %.1f ms, map %.1f ms, register %.1f ms, "
-                  "copy+unregister %.1f ms\n", bytes >> 20,
-                  1e3 * std::chrono::duration<double>(clk::now() - t0).count(),
-                  1e3 * std::chrono::duration<double>(t1 - t0).count(),
-                  1e3 * std::chrono::duration<double>(t2 - t1).count(),
-                  1e3 * std::chrono::duration<double>(clk::now() - t2).count());
-        return rc;
-      }
-    }
-  }
-  before_chunk(ctx, bytes);
-  return dpf_hip_memcpy_d2h(dst, src, bytes, stream);
-}
-int dpf_hip_memcpy_d2h_chunked(const void* src, size_t bytes, size_t align,
-                               void (*consume)(void* ctx, const void* chunk, size_t offset,
-                                               size_t len),
-                               void* ctx, void* stream) {
-  if (!bytes) return kOk;
-  if (!src || !consume || align == 0 || align > kBounceChunk)
-    return fail(kInvalidArgument, "dpf_hip_memcpy_d2h_chunked: bad arguments");
-  std::lock_guard<std::mutex> lock(g_bounce_mu);
-  if (int rc = bounce_buffers()) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t chunk = kBounceChunk / align * align;
-  const size_t n = (bytes + chunk - 1) / chunk;
-  auto len = [&](size_t i) { return i + 1 < n ? chunk : bytes - i * chunk; };
-  HIP_TRY(hipMemcpyAsync(g_bounce[0], src, len(0), hipMemcpyDeviceToHost, s));
-  for (size_t i = 0; i < n; ++i) {
-    HIP_TRY(hipStreamSynchronize(s));   // chunk i is in g_bounce[i & 1]
-    if (i + 1 < n)
-      HIP_TRY(hipMemcpyAsync(g_bounce[(i + 1) & 1], (const char*)src + (i + 1) * chunk, len(i + 1),
-                             hipMemcpyDeviceToHost, s));
-    // The next chunk's DMA into the other bounce buffer must have finished
-    // before the buffers (and g_bounce_mu) are given up on any path out.
-    try {
-      consume(ctx, g_bounce[i & 1], i * chunk, len(i));
-    } catch (...) {
-      (void)hipStreamSynchronize(s);
-      return fail(kInternal, "dpf_hip_memcpy_d2h_chunked: consume threw");
-    }
-  }
-  return kOk;
-}
-int dpf_hip_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
-  if (!bytes) return kOk;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_memset(void* dst, int value, size_t bytes, void* stream) {
-  if (!bytes) return kOk;
-  HIP_TRY(hipMemsetAsync(dst, value, bytes, (hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_stream_sync(void* stream) {
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_event_sync(void* event) {
-  HIP_TRY(hipEventSynchronize((hipEvent_t)event));
-  return kOk;
-}
-int dpf_hip_stream_wait_event(void* stream, void* event) {
-  HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0));
-  return kOk;
-}
 int dpf_hip_packed_element_size(const dpf_value_desc* desc) {
   if (!desc) return -1;
   return packed_size(desc);
@@ -2435,38 +1668,10 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
     return fail(kInvalidArgument, "NULL pointer");
   if (num_starts > (INT64_MAX >> num_levels))
     return fail(kInvalidArgument, "expansion too large");
-  // Choose the depth-first subtree depth S (items = num_starts * 2^(L - S)
-  // subtrees, each walked k0 = L - S levels from its start seed) by the
-  // per-thread critical path: rounds of items over the launch's threads times
-  // the AES of one item, the ILP1 walk counted twice.  Small trees get shallow
-  // subtrees and more items, so a launch far below one workgroup per CU is not
-  // serialised on a few lanes' DFS; start counts that are not powers of two
-  // (5 starts x 2^27: 1.25 subtrees of depth 11 per thread = 2 rounds) get
-  // subtrees shallow enough to divide evenly (depth 9: 5 rounds of 1, +53%).
-  int S = num_levels < kSMax ? num_levels : kSMax;
-  {
-    double best = -1;
-    int best_s = S;
-    for (int cand = S; cand >= (num_levels > 0 ? 1 : 0); --cand) {
-      const int64_t items = num_starts << (num_levels - cand);
-      const int blk = block_for(items);
-      const int64_t threads = (int64_t)grid_for(items, blk) * blk;
-      const int64_t rounds = (items + threads - 1) / threads;
-      const double cost = (double)rounds * (2.0 * (num_levels - cand) + 3.0 * (double)(1ll << cand));
-      if (best < 0 || cost < best * 0.999) {
-        best = cost;
-        best_s = cand;
-      }
-    }
-    S = best_s;
-  }
-#if defined(DPF_FORCE_S)
-  if (num_levels >= DPF_FORCE_S) S = DPF_FORCE_S;  // variant builds (tools/variant_bench.py)
-#endif
   ExpandParams p{};   // static launch, no chunk schedule
   p.num_levels = num_levels;
-  p.S = S;
-  p.k0 = num_levels - S;
+  p.S = choose_subtree_depth(num_starts, num_levels);
+  p.k0 = num_levels - p.S;
   p.num_items = num_starts << p.k0;
   p.seeds_in = seeds_in;
   p.ctrl_in = control_in;
@@ -2480,17 +1685,9 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
   p.rkd = xor_keys(p.rkl, p.rkr);
   p.clock = dpf_rt::g_clock_acc.load(std::memory_order_relaxed);
   hipStream_t s = (hipStream_t)stream;
-  if (fast_int(desc)) {
-    const int bits = desc->bits[0], E = desc->elements_per_block;
-    const int store_bytes = elements_per_leaf * bits / 8;
-    switch (bits) {
-      case 8: return launch_expand_fast<8>(p, desc, value_correction, E, party, store_bytes, s);
-      case 16: return launch_expand_fast<16>(p, desc, value_correction, E, party, store_bytes, s);
-      case 32: return launch_expand_fast<32>(p, desc, value_correction, E, party, store_bytes, s);
-      case 64: return launch_expand_fast<64>(p, desc, value_correction, E, party, store_bytes, s);
-      default: return launch_expand_fast<128>(p, desc, value_correction, E, party, store_bytes, s);
-    }
-  }
+  if (fast_int(desc))
+    return expand_fast(p, desc, value_correction, desc->elements_per_block, party,
+                       elements_per_leaf * desc->bits[0] / 8, s);
   const int esz = packed_size(desc);
   if (desc->direct && desc->blocks_needed == 1) {
     // Direct tuples of plain integers / XorWrappers: the hashed block is E
@@ -2499,98 +1696,24 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
     bool uniform = true;
     for (int k = 1; k < nl; ++k) uniform = uniform && desc->bits[k] == bits && desc->kind[k] == kind;
     const int lanes = desc->elements_per_block * nl;
-    if (uniform && lanes * bits <= 128) {
-      // Every lane the same width and kind: the integer fast path with E * nl lanes.
-      const int store_bytes = elements_per_leaf * esz;
-      switch (bits) {
-        case 8: return launch_expand_fast<8>(p, desc, value_correction, lanes, party, store_bytes, s);
-        case 16: return launch_expand_fast<16>(p, desc, value_correction, lanes, party, store_bytes, s);
-        case 32: return launch_expand_fast<32>(p, desc, value_correction, lanes, party, store_bytes, s);
-        case 64: return launch_expand_fast<64>(p, desc, value_correction, lanes, party, store_bytes, s);
-        default: return launch_expand_fast<128>(p, desc, value_correction, lanes, party, store_bytes, s);
-      }
-    }
-    if (lanes <= 16 && desc->elements_per_block * esz <= 16) {
-      SwarLeaf w;
-      memset(&w, 0, sizeof(w));
-      w.vcw_elems = value_correction;
-      w.lanes = lanes;
-      w.party = party;
-      w.store_bytes = elements_per_leaf * esz;
-      int off = 0;
-      for (int i = 0; i < lanes; ++i) {
-        const int b = desc->bits[i % nl];
-        w.lane_off[i] = (uint8_t)off;
-        w.lane_bits[i] = (uint8_t)b;
-        w.top |= (u128)1 << (off + b - 1);
-        if (desc->kind[i % nl] == DPF_LEAF_XOR)
-          w.xmask |= (b >= 128 ? ~(u128)0 : (((u128)1 << b) - 1)) << off;
-        off += b;
-      }
-      const char* off_env = getenv("DPF_EXPAND_NO_OCTET");
-      if (try_small(p, w, s)) {
-        HIP_TRY(hipGetLastError());
-        return kOk;
-      }
-      if (p.S >= 3 && !(off_env && off_env[0] == '1')) {
-        note_expand<SwarLeaf>(p, true);
-        TopScratch top;
-        int grid = 0, blk = 0;
-        if (int st = octet_shape<SwarLeaf>(p, s, top, &grid, &blk)) return st;
-        launch_octet_kernel(grid, blk, s, p, w);
-        HIP_TRY(hipGetLastError());
-        return kOk;
-      }
-      return launch_expand(p, w, s);
-    }
+    // Every lane the same width and kind: the integer fast path with E * nl lanes.
+    if (uniform && lanes * bits <= 128)
+      return expand_fast(p, desc, value_correction, lanes, party, elements_per_leaf * esz, s);
+    if (lanes <= 16 && desc->elements_per_block * esz <= 16)
+      return dispatch_expand(
+          p, make_swar_leaf(desc, value_correction, lanes, party, elements_per_leaf * esz), true, s);
   }
   int b = 0;
   if (elements_per_leaf == 1 && mod32_eligible(desc, &b)) {
-    // Tuples of IntModN<uint32_t, N>: Moller-Granlund sampling.
-    auto fill = [&](auto& m) {
-      memset(&m, 0, sizeof(m));
-      m.vcw_elems = value_correction;
-      m.nl = desc->num_leaves;
-      m.b = b;
-      m.party = party;
-      for (int k = 0; k < desc->num_leaves; ++k) m.div[k] = make_div32((uint32_t)desc->mod_low[k]);
-    };
-    if (desc->num_leaves <= 2) {
-      Mod32Leaf<2> m;
-      fill(m);
-      const char* off = getenv("DPF_EXPAND_NO_OCTET");
-      if (try_small(p, m, s)) {
-        HIP_TRY(hipGetLastError());
-        return kOk;
-      }
-      if (p.S >= 3 && !(off && off[0] == '1')) {
-        // Octet form (the half's four leaves hashed as two ILP4 groups).
-        note_expand<Mod32Leaf<2>>(p, true);
-        TopScratch top;
-        int grid = 0, blk = 0;
-        if (int st = octet_shape<Mod32Leaf<2>>(p, s, top, &grid, &blk)) return st;
-        launch_octet_kernel(grid, blk, s, p, m);
-        HIP_TRY(hipGetLastError());
-        return kOk;
-      }
-      return launch_expand(p, m, s);
-    }
-    if (desc->num_leaves <= 4) {   // no spills (Mod32Leaf<5> in expand_kernel: 36 B)
-      Mod32Leaf<4> m;
-      fill(m);
-      return launch_expand(p, m, s);
-    }
-    Mod32Leaf<kMod32MaxLeaves> m;
-    fill(m);
-    return launch_expand(p, m, s);
+    if (desc->num_leaves <= 2)
+      return dispatch_expand(p, make_mod32_leaf<2>(desc, value_correction, b, party), true, s);
+    if (desc->num_leaves <= 4)   // no spills (Mod32Leaf<5> in expand_kernel: 36 B)
+      return dispatch_expand(p, make_mod32_leaf<4>(desc, value_correction, b, party), true, s);
+    return dispatch_expand(p, make_mod32_leaf<kMod32MaxLeaves>(desc, value_correction, b, party),
+                           true, s);
   }
-  GenericLeaf g;
-  g.d = *desc;
-  g.vcw = value_correction;
-  g.party = party;
-  g.elements_per_leaf = elements_per_leaf;
-  g.esz = esz;
-  return launch_expand(p, g, s);
+  return dispatch_expand(p, make_generic_leaf(desc, value_correction, party, elements_per_leaf),
+                         true, s);
 }
 
 int dpf_hip_eval_points(int64_t num_points, int64_t points_per_key, int num_levels,
@@ -2672,8 +1795,7 @@ int dpf_hip_eval_points_sum(int64_t num_keys, int64_t num_points, int num_levels
     // Enough (chunk, pair) items to fill every CU's 1024 threads a few times
     // (16 times when the waves take them dynamically: enough chunks per wave
     // for take_chunk; each item then sums fewer keys before its atomics).
-    const char* dyn = std::getenv("DPF_POINTS_DYNAMIC");
-    const int64_t want = (int64_t)num_cus() * kBlock * (dyn && dyn[0] == '0' ? 4 : 16);
+    const int64_t want = (int64_t)num_cus() * kBlock * (hook_is("DPF_POINTS_DYNAMIC", '0') ? 4 : 16);
     int64_t chunks = (want + p.half - 1) / p.half;
     if (chunks > num_keys) chunks = num_keys;
     p.chunk_keys = (num_keys + chunks - 1) / chunks;
@@ -2739,24 +1861,6 @@ int dpf_hip_sum_shares_u64(int64_t num_keys, int64_t row_len, int bits, int xor_
   hipLaunchKernelGGL(sum_shares_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
                      num_keys, row_len, bits, xor_mode, (const char*)shares, sums);
   HIP_TRY(hipGetLastError());
-  return kOk;
-}
-
-int dpf_hip_event_create(void** ev) {
-  HIP_TRY(hipEventCreate((hipEvent_t*)ev));
-  return kOk;
-}
-int dpf_hip_event_destroy(void* ev) {
-  HIP_TRY(hipEventDestroy((hipEvent_t)ev));
-  return kOk;
-}
-int dpf_hip_event_record(void* ev, void* stream) {
-  HIP_TRY(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream));
-  return kOk;
-}
-int dpf_hip_event_elapsed_ms(void* start, void* stop, float* ms) {
-  HIP_TRY(hipEventSynchronize((hipEvent_t)stop));
-  HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
   return kOk;
 }
 

@@ -1,9 +1,11 @@
 // dpf_runtime.h -- host-side plumbing shared by the kernel translation units:
 // absl status codes, the thread-local last-error message
-// behind dpf_hip_last_error(), and launch-shape helpers.
+// behind dpf_hip_last_error() (defined in dpf_kernels.hip), the launch hooks,
+// and the launch-shape helpers (dpf_kernels.hip, dpf_expand_plan.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 
@@ -18,7 +20,28 @@ constexpr int kOk = 0, kInvalidArgument = 3, kResourceExhausted = 8, kFailedPrec
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
 
+// Launch hooks: the DPF_* environment variables, read at every call (nothing
+// is cached).  hook_is: the hook's first character is `c` (unset or empty: no).
+inline bool hook_is(const char* name, char c) {
+  const char* v = getenv(name);
+  return v && v[0] == c;
+}
+inline bool hook_set(const char* name) { return getenv(name) != nullptr; }
+// The hook as a number; unset or empty: `dflt`.  hook_int clamps to [lo, hi].
+inline long long hook_long(const char* name, long long dflt) {
+  const char* v = getenv(name);
+  return v && *v ? strtoll(v, nullptr, 10) : dflt;
+}
+inline int hook_int(const char* name, int dflt, int lo = INT32_MIN, int hi = INT32_MAX) {
+  const char* v = getenv(name);
+  if (!v || !*v) return dflt;
+  const int k = atoi(v);
+  return k < lo ? lo : (k > hi ? hi : k);
+}
+
 int num_cus();                                 // compute units of the current device
+int max_block();                               // kBlock and kSMax (dpf_device.h), for the
+int max_subtree_depth();                       // files that include no device header
 int block_for(int64_t work_items);             // threads per workgroup: kBlock, or fewer
                                                // (multiple of 64) to spread a small launch over more CUs
 int grid_for(int64_t work_items, int block);   // workgroups of `block` threads, <= one per CU
@@ -28,7 +51,7 @@ int grid_for(int64_t work_items, int block);   // workgroups of `block` threads,
 int64_t dynamic_chunks_per_wg(int64_t items, int grid, int block, const char* env);
 // Chunk schedule of a full-domain expand launch of `num_items` subtrees of
 // depth S, each k0 levels below its start seed, on `cus` workgroups of 16
-// waves (dpf_kernels.hip, "Who takes which chunk"; reads the DPF_OCTET_*
+// waves (dpf_expand_plan.hip, "Who takes which chunk"; reads the DPF_OCTET_*
 // hooks).  shift == 0: a static launch, nothing else is set.  Else phase j
 // (taken in order) is chunks[j] chunks of 64 items of shape (k0[j], S[j]),
 // the first of them item first_item[j] in that shape; absent phases have no
@@ -42,6 +65,20 @@ struct ChunkPlan {
 };
 // sched_ok false: the counter per launch and the taper only where the hooks ask.
 ChunkPlan plan_chunks(int64_t num_items, int k0, int S, int min_S, int64_t cus, bool sched_ok);
+// The plan as the 15 words of dpf_hip_octet_schedule / dpf_hip_last_expand_schedule.
+void write_plan(const ChunkPlan& c, int64_t* out);
+// The rest of the launch plan of a full-domain expansion (dpf_expand_plan.hip):
+// pure functions of the shape, the CU count and the hooks; they launch nothing.
+constexpr int kSmallMaxD = 11;   // levels expand_small_kernel takes breadth-first through LDS
+// Depth-first subtree depth S of an expansion of `num_levels` below `num_starts` seeds.
+int choose_subtree_depth(int64_t num_starts, int num_levels);
+// Shape (t levels walked, D breadth-first) of the small-tree launch; false: not that shape.
+bool small_shape(int64_t num_starts, int num_levels, int* t, int* D);
+// Shape of the tree-top pass above `num_items` items k0 levels below their
+// start seeds; false: no pass.
+bool top_shape(int64_t num_items, int k0, int* t, int* D);
+// Levels each dynamically taken item walks below the tree-top pass's roots.
+int octet_walk_levels();
 int validate_desc(const dpf_value_desc* d);    // kOk or the failure code
 int packed_size(const dpf_value_desc* d);      // bytes of one packed element
 bool fast_int(const dpf_value_desc* d);        // one plain/XOR integer leaf, direct, b == 1

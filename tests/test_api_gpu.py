@@ -409,7 +409,7 @@ def test_large_host_output_matches_device(log, vt):
 def test_pipelined_host_output_and_its_fallbacks(env, monkeypatch):
     """A fresh host output of >= 512 MiB is mapped and registered in 256 MiB
     pieces by a helper thread while the DMA fills the pieces already
-    registered (dpf_kernels.hip: pipelined_d2h).  A 1 GiB output (five pieces:
+    registered (dpf_host_copies.hip: pipelined_d2h).  A 1 GiB output (five pieces:
     the vector starts off a 2 MiB boundary) equals the device output byte for
     byte by default, when the registration of piece 1 or 0 and every later one
     is refused (the rest of the range through the bounce buffers), and with

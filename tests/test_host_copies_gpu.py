@@ -2,7 +2,7 @@
 from several host threads at once.
 
 Pageable copies of >= DPF_HIP_REGISTER_MIN_BYTES (512 MiB) register the host
-range for the copy's duration (dpf_kernels.hip: acquire_host / release_host);
+range for the copy's duration (dpf_host_copies.hip: acquire_host / release_host);
 smaller ones go through the page-locked staging buffers.  Two threads copying from or
 into the same range must share one reference-counted registration: the first
 thread to finish must not unregister pages the other thread's DMA is still

@@ -403,7 +403,7 @@ def test_eval_points_shapes(hip, vt, num_keys, ppk, levels, partials):
                  from_partials=partials)
 
 
-# Dynamic distribution in the octet kernel (dpf_kernels.hip octet_shape):
+# Dynamic distribution in the octet kernel (dpf_kernels.hip subtree_shape):
 # launches with >= 4 items per thread of the chip take 2 or 4 levels off the
 # subtrees and let each wave take 64 items at a time from its workgroup's
 # counter.  At 2^26 leaves both shapes apply; every shape must give the

@@ -1,5 +1,5 @@
 """The chunk schedule of the full-domain expand launches (dpf_hip_octet_schedule,
-plan_chunks in dpf_kernels.hip): a pure function of the launch's shape, the CU
+plan_chunks in dpf_expand_plan.hip): a pure function of the launch's shape, the CU
 count and the DPF_OCTET_* hooks, so it is checked here without a GPU.
 """
 import itertools

@@ -1,5 +1,5 @@
 """The chip-wide chunk counter and the tapered chunks of the full-domain expand
-kernels (dpf_kernels.hip, "Who takes which chunk") give the static launch's
+kernels (dpf_expand_plan.hip, "Who takes which chunk") give the static launch's
 bytes.
 
 Every schedule is compared byte for byte with the static one-item-per-thread
