@@ -17,18 +17,16 @@
 // The host does O(#prefixes) bookkeeping per call; every per-key step runs in
 // one dpf_hip_eval_prefix_batch launch (csrc/kernels/dpf_batch.hip).
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <mutex>
 #include <cstdio>
-#include <cstdlib>
 #include <string>
-#include <unordered_map>
+#include <utility>
+#include <vector>
 
 #include "dpf/distributed_point_function.h"
 #include "dpf/key_batch.h"
 #include "dpf_hip.h"
 #include "host_util.h"
+#include "until_plan.h"
 
 namespace distributed_point_functions {
 
@@ -41,40 +39,26 @@ using dpf_internal::kPrgKeyValue;
 using dpf_internal::MakeDesc;
 using dpf_internal::SetProtoBlock;
 using dpf_internal::ToBlock;
-using dpf_internal::U128Hash;
+using dpf_internal::hook_is;
+using dpf_internal::hook_long;
+using dpf_internal::hook_str;
+using dpf_internal::PhaseTimer;
+using dpf_internal::StartSource;
+using dpf_internal::UntilBatchArgs;
+using dpf_internal::UntilBatchShape;
 
 namespace {
 // Host-phase timing of the batched path, printed at exit when
 // DPF_BATCH_HOST_TIMING is set (diagnostics for config 5a's host-bound levels).
-// Contexts on several threads add into it, so every update takes `mu`.
-struct HostTiming {
-  std::mutex mu;
-  double t[6] = {0, 0, 0, 0, 0, 0};
-  long calls = 0;
-  void add(int phase, double s) {
-    std::lock_guard<std::mutex> g(mu);
-    t[phase] += s;
-  }
-  void call() {
-    std::lock_guard<std::mutex> g(mu);
-    ++calls;
-  }
-  ~HostTiming() {
-    if (calls && std::getenv("DPF_BATCH_HOST_TIMING"))
-      std::fprintf(stderr,
-                   "[batch host timing] calls=%ld dedup=%.3fs lookup=%.3fs tables=%.3fs "
-                   "upload=%.3fs device=%.3fs update=%.3fs\n",
-                   calls, t[0], t[1], t[2], t[3], t[4], t[5]);
-  }
-};
-HostTiming g_timing;
-const bool g_timing_on = std::getenv("DPF_BATCH_HOST_TIMING") != nullptr;
+PhaseTimer g_timing("DPF_BATCH_HOST_TIMING", 0, [](long calls, double, const double* t) {
+  std::fprintf(stderr,
+               "[batch host timing] calls=%ld dedup=%.3fs lookup=%.3fs tables=%.3fs "
+               "upload=%.3fs device=%.3fs update=%.3fs\n",
+               calls, t[0], t[1], t[2], t[3], t[4], t[5]);
+});
 // DPF_BATCH_NO_CACHE=1 turns the expansion cache off (every call walks down
 // from the partial evaluations, as the reference does): an A/B and test hook.
-bool CacheOn() {
-  const char* v = std::getenv("DPF_BATCH_NO_CACHE");
-  return !(v && v[0] == '1');
-}
+bool CacheOn() { return !hook_is("DPF_BATCH_NO_CACHE", '1'); }
 // How a call that reads the expansion cache writes the next one.  Default:
 // into a spare buffer if one fits, else in place through a slot table, else
 // (no slot table possible) in place after gathering the start seeds.
@@ -83,57 +67,26 @@ bool CacheOn() {
 // DPF_BATCH_CACHE_IN_PLACE=1 means gather: test and A/B hooks, read per call.
 enum class CacheMode { kAuto, kSpare, kPermute, kGather };
 CacheMode ForcedCacheMode() {
-  const char* v = std::getenv("DPF_BATCH_CACHE_IN_PLACE");
-  if (v && v[0] == '1') return CacheMode::kGather;
-  const char* m = std::getenv("DPF_BATCH_CACHE_MODE");
-  if (!m) return CacheMode::kAuto;
-  const std::string s(m);
+  if (hook_is("DPF_BATCH_CACHE_IN_PLACE", '1')) return CacheMode::kGather;
+  const std::string s = hook_str("DPF_BATCH_CACHE_MODE");
   if (s == "spare") return CacheMode::kSpare;
   if (s == "permute") return CacheMode::kPermute;
   if (s == "gather") return CacheMode::kGather;
   return CacheMode::kAuto;
 }
 
-// The slot table of an in-place rewrite (dpf_hip_eval_prefix_batch_cached_slots):
-// start node u = (tree index u >> s, sub-node) reads physical slot
-// start_slot[u >> s]; its 2^E leaves go to slot[(u << E) + l].  A slot read by
-// exactly one start node (s == 0) takes that node's leaf 0; every other leaf
-// takes the next slot no start node reads.  False if those run out.
-bool BuildSlotTable(const std::vector<int64_t>& start_slot, int64_t T, int s, int E,
-                    int64_t phys_stride, std::vector<int32_t>* slot) {
-  static thread_local std::vector<uint8_t> tl_read;
-  std::vector<uint8_t>& read = tl_read;
-  read.assign(static_cast<size_t>(phys_stride), 0);
-  for (int64_t i = 0; i < T; ++i) read[start_slot[i]] = 1;
-  const int64_t leaves = (T << s) << E;
-  slot->resize(static_cast<size_t>(leaves));
-  int64_t g = 0;  // next unread slot candidate
-  auto next_free = [&]() -> int64_t {
-    while (g < phys_stride && read[g]) ++g;
-    return g < phys_stride ? g++ : -1;
-  };
-  for (int64_t u = 0; u < (T << s); ++u) {
-    for (int64_t l = 0; l < (int64_t{1} << E); ++l) {
-      int64_t v;
-      if (l == 0 && s == 0) {
-        v = start_slot[u];
-      } else if ((v = next_free()) < 0) {
-        return false;
-      }
-      (*slot)[(u << E) + l] = static_cast<int32_t>(v);
-    }
-  }
-  return true;
-}
-struct PhaseClock {
-  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
-  void mark(int phase) {
-    if (!g_timing_on) return;
-    auto now = std::chrono::steady_clock::now();
-    g_timing.add(phase, std::chrono::duration<double>(now - last).count());
-    last = now;
-  }
-};
+// Host buffers are recycled across calls (per thread): first touches of fresh
+// pages cost more than the bookkeeping itself at 1 M prefixes per level
+// (config 5a).  Not cleared first: every element a call reads it has written
+// before, so vectors kept from an earlier call of about this size
+// value-initialise nothing (clearing them had cost a 1 M-prefix level ~3.8 ms
+// of single-threaded zeroing, r16 DPF_BATCH_HOST_TIMING).
+// Start nodes are indexed by int32 on the device, so 32-bit positions
+// suffice: 8-byte (position, block index) entries.
+thread_local std::vector<std::pair<int32_t, int>> tl_prefix_map;
+thread_local std::vector<int32_t> tl_parent_of;   // position of each tree index's stored prefix
+thread_local std::vector<int64_t> tl_start_slot;  // physical cache slot of each tree index's node
+thread_local std::vector<int32_t> tl_leaf_slot;   // slot table of an in-place rewrite
 }  // namespace
 
 // DPF_BATCH_ALLOC_LIMIT=<bytes>: a test hook that makes a batch context behave
@@ -142,10 +95,7 @@ struct PhaseClock {
 // out-of-memory, and MemInfo reports the limit -- so the expansion cache's
 // fallbacks (no spare, eviction and retry, RESOURCE_EXHAUSTED) run
 // deterministically.  Read per call.
-size_t AllocLimit() {
-  const char* v = std::getenv("DPF_BATCH_ALLOC_LIMIT");
-  return v && *v ? static_cast<size_t>(std::strtoull(v, nullptr, 10)) : 0;
-}
+size_t AllocLimit() { return static_cast<size_t>(hook_long("DPF_BATCH_ALLOC_LIMIT", 0)); }
 
 bool DeviceBatchContext::TryAlloc(void** p, size_t* cap, size_t bytes) {
   *p = nullptr;
@@ -222,9 +172,166 @@ DeviceBatchContext::~DeviceBatchContext() {
   if (tables_pending_) (void)dpf_hip_event_sync(tables_event_);
   if (tables_event_) dpf_hip_event_destroy(tables_event_);
   if (pinned_tables_) dpf_hip_host_free(pinned_tables_);
-  for (void* p : {seeds_, ctrl_, next_seeds_, next_ctrl_, parent_, path_, save_, offsets_,
-                  workspace_, stage_, stage2_, leaf_seeds_, leaf_spare_, slots_, leaf_slot_})
+  for (void* p : {seeds_, ctrl_, next_seeds_, next_ctrl_, parent_, workspace_, stage_, stage2_,
+                  leaf_seeds_, leaf_spare_, slots_, leaf_slot_})
     if (p) dpf_hip_free(p);
+}
+
+bool DeviceBatchContext::Fits(size_t bytes, size_t reserve_div) const {
+  size_t free_b = 0, total_b = 0;
+  MemInfo(&free_b, &total_b);
+  return free_b >= bytes + total_b / reserve_div;
+}
+
+Status DeviceBatchContext::GrowCache(size_t bytes, void* stream) {
+  if (leaf_seeds_cap_ >= bytes) return OkStatus();
+  HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
+  Release(&leaf_seeds_, &leaf_seeds_cap_);
+  if (!Fits(bytes, 8) || !TryAlloc(&leaf_seeds_, &leaf_seeds_cap_, bytes)) ++events_.cache_refused;
+  return OkStatus();
+}
+
+// This call's leaves become the next call's expansion cache (not after the
+// last level).  Preferred: write them to the spare buffer while the kernel
+// reads the start seeds straight from the current cache, then swap.  With
+// no room for a spare, the cache is rewritten in place; a failed allocation
+// only turns the cache off.
+StatusOr<DeviceBatchContext::CacheTarget> DeviceBatchContext::ChooseCacheTarget(
+    bool writes_cache, bool cached, int64_t leaf_stride, const std::vector<int64_t>& start_slot,
+    int64_t T, int s, int E, std::vector<int32_t>* leaf_slot, void* stream) {
+  CacheTarget t;
+  t.stride = leaf_stride;
+  t.cache_in_use = cached;
+  if (!writes_cache) return t;
+  const size_t cache_need = static_cast<size_t>(keys_->num_keys() * leaf_stride) * sizeof(dpf_block);
+  if (!cached) {
+    // The current cache is not read by this call: rewrite (or regrow) it.
+    leaf_level_ = -1;  // until this call has written it
+    DPF_RETURN_IF_ERROR(GrowCache(cache_need, stream));
+    t.leaf_seeds = leaf_seeds_;
+    return t;
+  }
+  const CacheMode mode = ForcedCacheMode();
+  const bool want_spare = mode == CacheMode::kAuto || mode == CacheMode::kSpare;
+  if (want_spare && leaf_spare_cap_ < cache_need) {
+    // The spare may still be read by work in flight on the stream.
+    HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
+    Release(&leaf_spare_, &leaf_spare_cap_);
+    if (!Fits(cache_need, 4) || !TryAlloc(&leaf_spare_, &leaf_spare_cap_, cache_need))
+      ++events_.spare_refused;
+  }
+  if (want_spare && leaf_spare_ && leaf_spare_cap_ >= cache_need) {
+    t.leaf_seeds = leaf_spare_;
+    t.swap = true;
+  } else if (mode != CacheMode::kGather && leaf_stride <= leaf_stride_ &&
+             dpf_internal::BuildSlotTable(start_slot, T, s, E, leaf_stride_, leaf_slot)) {
+    // In place through the slot table: no gather, no second buffer.
+    t.permute = true;
+    t.leaf_seeds = leaf_seeds_;
+    t.stride = leaf_stride_;
+    ++events_.permuted;
+  } else {
+    t.gather = true;  // leaf_seeds is set once the gather is enqueued
+    ++events_.in_place;
+  }
+  return t;
+}
+
+Status DeviceBatchContext::EnsureEvicting(void** p, size_t* cap, size_t bytes, CacheTarget* target,
+                                          void* stream) {
+  Status st = Ensure(p, cap, bytes);
+  for (int step = 0; !st.ok() && step < 2; ++step) {
+    void** victim = step == 0 ? &leaf_spare_ : &leaf_seeds_;
+    size_t* victim_cap = step == 0 ? &leaf_spare_cap_ : &leaf_seeds_cap_;
+    if (!*victim || (step == 1 && target->cache_in_use)) continue;
+    HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
+    if (target->leaf_seeds == *victim) {
+      target->leaf_seeds = nullptr;  // this call writes no cache
+      target->swap = false;
+    }
+    Release(victim, victim_cap);
+    ++(step == 0 ? events_.evicted_spare : events_.evicted_cache);
+    if (step == 1) leaf_level_ = -1;
+    st = Ensure(p, cap, bytes);
+  }
+  return st;
+}
+
+Status DeviceBatchContext::SendTables(size_t bytes, CacheTarget* target, void* stream) {
+  DPF_RETURN_IF_ERROR(EnsureEvicting(&parent_, &parent_cap_, bytes, target, stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d_async(parent_, pinned_tables_, bytes, stream));
+  return TablesSent(stream);
+}
+
+Status DeviceBatchContext::GatherStartSeeds(const std::vector<int64_t>& start_slot, int64_t T,
+                                            int64_t leaf_stride, CacheTarget* target,
+                                            void* stream) {
+  const int64_t K = keys_->num_keys();
+  DPF_RETURN_IF_ERROR(EnsureEvicting(&slots_, &slots_cap_, T * sizeof(int64_t), target, stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(slots_, start_slot.data(), T * sizeof(int64_t), stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_gather_seeds_layout(
+      K, T, static_cast<const int64_t*>(slots_), static_cast<const dpf_block*>(leaf_seeds_),
+      leaf_stride_, static_cast<dpf_block*>(next_seeds_), static_cast<uint8_t*>(next_ctrl_),
+      index_major_ ? 1 : 0, stream));
+  target->cache_in_use = false;  // copied out; from here on only the write target
+  leaf_level_ = -1;              // rewritten in place by this call's kernel
+  // Regrow once the gather has read the old cache.
+  DPF_RETURN_IF_ERROR(
+      GrowCache(static_cast<size_t>(K * leaf_stride) * sizeof(dpf_block), stream));
+  target->leaf_seeds = leaf_seeds_;
+  return OkStatus();
+}
+
+Status DeviceBatchContext::SendSlotTable(const std::vector<int32_t>& leaf_slot, CacheTarget* target,
+                                         void* stream) {
+  const size_t bytes = leaf_slot.size() * sizeof(int32_t);
+  DPF_RETURN_IF_ERROR(EnsureEvicting(&leaf_slot_, &leaf_slot_cap_, bytes, target, stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(leaf_slot_, leaf_slot.data(), bytes, stream));
+  leaf_level_ = -1;  // rewritten in place by this call's kernel
+  return OkStatus();
+}
+
+void DeviceBatchContext::CommitCache(const CacheTarget& target, int hierarchy_level, int de,
+                                     bool last_level, const std::vector<int32_t>& leaf_slot) {
+  if (target.swap) {
+    std::swap(leaf_seeds_, leaf_spare_);
+    std::swap(leaf_seeds_cap_, leaf_spare_cap_);
+  }
+  leaf_level_ = target.leaf_seeds ? hierarchy_level : -1;
+  leaf_de_ = de;
+  leaf_stride_ = target.stride;
+  if (target.permute)
+    leaf_phys_.assign(leaf_slot.begin(), leaf_slot.end());
+  else
+    leaf_phys_.clear();  // written in leaf order
+  // After the last level nothing reads the cache; its buffers stay allocated
+  // for the next pass over the hierarchy (Reset()), because giving them back
+  // and regrowing them level by level (4, 16, 64 GiB for 2^20 heavy-hitters
+  // clients) cost 3.7 s per 22 s pass (profiles/r14_ab.txt).  The 1/8-of-HBM
+  // headroom rule (GrowCache) bounds what they take; callers that need the
+  // memory call ReleaseExpansionCache() (or Reset(true)).
+  if (last_level) leaf_level_ = -1;
+}
+
+void DeviceBatchContext::CommitPartials(int hierarchy_level, int prev_level, bool has_prefixes,
+                                        bool update, bool ascending,
+                                        std::vector<uint128>* tree_indices) {
+  previous_hierarchy_level_ = hierarchy_level;
+  if (has_prefixes) {
+    if (update) {
+      std::swap(partial_prefixes_, *tree_indices);
+      partial_sorted_ = ascending;
+      std::swap(seeds_, next_seeds_);
+      std::swap(seeds_cap_, next_seeds_cap_);
+      std::swap(ctrl_, next_ctrl_);
+      std::swap(ctrl_cap_, next_ctrl_cap_);
+    } else {
+      partial_prefixes_.clear();
+      partial_sorted_ = false;
+    }
+    partial_evaluations_level_ = prev_level;
+  }
+  spare_prefixes_ = std::move(*tree_indices);
 }
 
 Status DeviceBatchContext::StageTables(size_t bytes) {
@@ -260,8 +367,7 @@ StatusOr<std::unique_ptr<DeviceBatchContext>> DistributedPointFunction::CreateBa
   std::unique_ptr<DeviceBatchContext> ctx(new DeviceBatchContext(&keys));
   // DPF_BATCH_KEY_MAJOR=1 (read at creation: one layout per context) keeps
   // the r15 key-major tables and lanes = start nodes (A/B and test hook).
-  const char* km = std::getenv("DPF_BATCH_KEY_MAJOR");
-  ctx->index_major_ = !(km && km[0] == '1');
+  ctx->index_major_ = !hook_is("DPF_BATCH_KEY_MAJOR", '1');
   return ctx;
 }
 
@@ -279,504 +385,294 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchSumToDevice(
                                 stream);
 }
 
-StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchCore(
-    int hierarchy_level, Span<const uint128> prefixes, DeviceBatchContext& ctx, bool sum,
-    void* device_out, int64_t capacity_bytes, void* stream) const {
+// EvaluateUntil's argument checks (h:655-700), in the reference's order.
+Status DistributedPointFunction::CheckUntilBatchArgs(int hierarchy_level,
+                                                     Span<const uint128> prefixes,
+                                                     const DeviceBatchContext& ctx) const {
   const DeviceKeyBatch& keys = ctx.keys();
   const int H = static_cast<int>(parameters().size());
   if (keys.num_levels() != tree_levels_needed() - 1 || keys.num_hierarchy_levels() != H)
     return InvalidArgumentError("key batch does not match this DistributedPointFunction");
-  // h:655-700, in the reference's order.
   if (hierarchy_level < 0 || hierarchy_level >= H)
     return InvalidArgumentError(
         "`hierarchy_level` must be non-negative and less than parameters_.size()");
-  if (hierarchy_level <= ctx.previous_hierarchy_level_)
+  const int prev = ctx.previous_hierarchy_level_;
+  if (hierarchy_level <= prev)
     return InvalidArgumentError(
         "`hierarchy_level` must be greater than `ctx.previous_hierarchy_level`");
-  if ((ctx.previous_hierarchy_level_ < 0) != prefixes.empty())
+  if ((prev < 0) != prefixes.empty())
     return InvalidArgumentError(
         "`prefixes` must be empty if and only if this is the first call with `ctx`.");
-  const int prev = ctx.previous_hierarchy_level_;
   int prev_log = 0;
   if (!prefixes.empty()) {
     prev_log = parameters()[prev].log_domain_size();
-    if (prev_log < 128) {
-      const uint128 limit = static_cast<uint128>(1) << prev_log;
-      const int64_t np = static_cast<int64_t>(prefixes.size());
-      std::atomic<int64_t> bad{np};
-      dpf_internal::ParallelFor(np, [&](int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i)
-          if (prefixes[i] >= limit) {
-            int64_t cur = bad.load();
-            while (i < cur && !bad.compare_exchange_weak(cur, i)) {
-            }
-            return;
-          }
-      });
-      if (bad.load() < np)
-        return InvalidArgumentError("Index " + Uint128ToString(prefixes[bad.load()]) +
-                                    " out of range for hierarchy level " + std::to_string(prev));
-    }
+    const int64_t bad = dpf_internal::FirstOutOfRangePrefix(prefixes, prev_log);
+    if (bad < static_cast<int64_t>(prefixes.size()))
+      return InvalidArgumentError("Index " + Uint128ToString(prefixes[bad]) +
+                                  " out of range for hierarchy level " + std::to_string(prev));
   }
-  const int log = parameters()[hierarchy_level].log_domain_size();
-  if (log - prev_log > 62)
+  if (parameters()[hierarchy_level].log_domain_size() - prev_log > 62)
     return InvalidArgumentError(
         "Output size would be larger than 2**62. Please evaluate fewer hierarchy levels at once.");
+  return OkStatus();
+}
 
-  PhaseClock clk;
-  if (g_timing_on) g_timing.call();
+// What one batched call works out on the host before it touches the device.
+struct DistributedPointFunction::BatchCall {
+  std::vector<uint128> tree_indices;  // unique, first-seen order (the root alone without prefixes)
+  bool indices_ascending = false;     // tree_indices strictly ascending
+  std::vector<std::pair<int32_t, int>>& prefix_map = tl_prefix_map;
+  std::vector<int32_t>& parent_of = tl_parent_of;
+  std::vector<int64_t>& start_slot = tl_start_slot;
+  std::vector<int32_t>& leaf_slot = tl_leaf_slot;
+  bool cache_on = false;
+  int start_level = 0;  // tree depth of the stored partial evaluations the call starts from
+  StartSource source = StartSource::kRoot;
+  dpf_value_desc desc;
+  bool native_sum = false;  // the kernel sums over the keys itself
+  UntilBatchShape shape;
+  DeviceBatchContext::CacheTarget target;  // where the call's leaves go
+  dpf_internal::TableLayout tables;        // the start-node table image
+};
+
+// Where each of the call's tree indices (c->tree_indices, of P prefixes)
+// starts -- a stored partial evaluation or the root (ExpandAndUpdateContext
+// cc:455-498, ComputePartialEvaluations cc:351-453) -- and the call's shape.
+Status DistributedPointFunction::PlanBatchCall(int hierarchy_level, int64_t P,
+                                               const DeviceBatchContext& ctx, bool sum,
+                                               BatchCall* c) const {
+  const int prev = ctx.previous_hierarchy_level_;
+  const int prev_log = P > 0 ? parameters()[prev].log_domain_size() : 0;
+  const std::vector<uint128>& tree_indices = c->tree_indices;
+  UntilBatchArgs a;
+  a.P = P;
+  a.T = static_cast<int64_t>(tree_indices.size());
+  a.K = ctx.keys().num_keys();
+  a.Dh = hierarchy_to_tree()[hierarchy_level];
+  const std::vector<uint128>& q = ctx.partial_prefixes_;
+  if (P > 0) {
+    a.Dprev = hierarchy_to_tree()[prev];
+    if (ctx.partial_evaluations_level_ >= 0 && !q.empty() &&
+        hierarchy_to_tree()[ctx.partial_evaluations_level_] <= a.Dprev) {
+      a.start_level = hierarchy_to_tree()[ctx.partial_evaluations_level_];
+      c->source = StartSource::kPartial;
+    }
+  }
+  c->start_level = a.start_level;
+  const auto& f = flat_[hierarchy_level];
+  c->desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
+  a.max_e = dpf_hip_prefix_batch_max_expand(&c->desc, sum ? 1 : 0);
+  c->native_sum = sum && a.max_e >= 0;
+  if (a.max_e < 0) a.max_e = dpf_hip_prefix_batch_max_expand(&c->desc, 0);
+  a.log_bits = parameters()[hierarchy_level].log_domain_size() - prev_log;
+  a.cepb = corrected_elements_per_block(hierarchy_level);
+  a.esz = f.packed_size;
+  a.sum = sum;
+  a.last_level = hierarchy_level == static_cast<int>(parameters().size()) - 1;
+  a.cache_on = c->cache_on = CacheOn();
+  a.cache_level = ctx.leaf_seeds_ ? ctx.leaf_level_ : -1;
+  a.prev_level = prev;
+  a.cache_de = ctx.leaf_de_;
+  a.cache_stride = ctx.leaf_stride_;
+  const UntilBatchShape& sh = c->shape = dpf_internal::PlanUntilBatch(a, c->prefix_map);
+
+  // A cached call's start slots come out of the lookup's own pass (one read
+  // of tree_indices instead of two).
+  const bool cached = sh.cached;
+  const dpf_internal::StartSlotOf slot_of(cached ? sh.W1 : 0, ctx.leaf_phys_);
+  if (cached) c->start_slot.resize(sh.T);
+  int64_t* start_slot = c->start_slot.data();
+  if (c->source == StartSource::kPartial) {
+    c->parent_of.resize(sh.T);
+    int32_t* parent_of = c->parent_of.data();
+    const int64_t missing = dpf_internal::LookupStoredPrefixes(
+        q, ctx.partial_sorted_, tree_indices.data(), sh.T, sh.W1, [&](int64_t i, int64_t j) {
+          parent_of[i] = static_cast<int32_t>(j);
+          if (cached) start_slot[i] = slot_of(j, tree_indices[i]);
+        });
+    if (missing < sh.T)
+      return InvalidArgumentError("Prefix not present in ctx.partial_evaluations at hierarchy level " +
+                                  std::to_string(prev));
+  } else if (cached) {
+    dpf_internal::ParallelFor(sh.T, [&](int64_t lo, int64_t hi) {
+      for (int64_t i = lo; i < hi; ++i) start_slot[i] = slot_of(0, tree_indices[i]);
+    });
+  }
+  if (a.max_e < 0) return UnimplementedError("value type not supported by the batched GPU path");
+  if (sh.U < 0)
+    return ResourceExhaustedError(
+        "Too many start nodes for one batched evaluation; evaluate fewer levels at once.");
+  if (cached) c->source = StartSource::kCache;
+  return OkStatus();
+}
+
+// The kernel launch and what follows it, by output mode.  The kernel writes
+// `rows` rows of n_blk elements: the caller's buffer when nothing follows,
+// else stage_.
+//   native key sum: kernel sums (sum flag 1, workspace_), 1 row;
+//   per-key rows + row sum: K rows into stage_, dpf_hip_sum_rows into the
+//     caller's buffer (stage2_ when a gather follows);
+//   store: K rows.
+// A non-identity gather (dpf_hip_gather for one row, dpf_hip_gather_batched
+// for K) then writes the caller's buffer.
+Status DistributedPointFunction::LaunchBatchCall(int hierarchy_level, BatchCall& c,
+                                                 DeviceBatchContext& ctx, bool sum,
+                                                 void* device_out, void* stream) const {
+  DeviceBatchContext::CacheTarget* target = &c.target;
+  const dpf_internal::TableLayout& tab = c.tables;
+  const DeviceKeyBatch& keys = ctx.keys();
+  const UntilBatchShape& sh = c.shape;
+  const int64_t K = keys.num_keys();
+  const int esz = flat_[hierarchy_level].packed_size;
+  const bool row_sum = sum && !c.native_sum;
+  const int64_t rows = c.native_sum ? 1 : K;
+  const bool gather_out = !sh.identity;
+  const char* dtab = static_cast<const char*>(ctx.parent_);
+  const int64_t* d_offsets =
+      gather_out ? reinterpret_cast<const int64_t*>(dtab + tab.off_offsets) : nullptr;
+  auto ensure = [&](void** p, size_t* cap, size_t bytes) {
+    return ctx.EnsureEvicting(p, cap, bytes, target, stream);
+  };
+
+  void* kernel_out = device_out;
+  if (row_sum || gather_out) {
+    DPF_RETURN_IF_ERROR(ensure(&ctx.stage_, &ctx.stage_cap_, rows * sh.n_blk * esz));
+    kernel_out = ctx.stage_;
+  }
+  if (c.native_sum)
+    DPF_RETURN_IF_ERROR(
+        ensure(&ctx.workspace_, &ctx.workspace_cap_,
+               sh.n_blk * flat_[hierarchy_level].leaves.size() * 3 * sizeof(uint64_t)));
+
+  // Start seeds by source; cached ones carry their control bit in bit 0
+  // (control_in NULL).
+  const dpf_block* start_seeds = nullptr;
+  const uint8_t* start_ctrl = nullptr;
+  int64_t start_stride = static_cast<int64_t>(ctx.partial_prefixes_.size());
+  if (c.source == StartSource::kCache) {
+    start_seeds = static_cast<const dpf_block*>(ctx.leaf_seeds_);
+    start_stride = ctx.leaf_stride_;
+  } else if (c.source == StartSource::kGathered) {
+    start_seeds = static_cast<const dpf_block*>(ctx.next_seeds_);
+    start_ctrl = static_cast<const uint8_t*>(ctx.next_ctrl_);
+    start_stride = sh.T;
+  } else if (c.source == StartSource::kPartial) {
+    start_seeds = ctx.partial_seeds();
+    start_ctrl = ctx.partial_control();
+  }
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  HIP_RETURN_IF_ERROR(dpf_hip_eval_prefix_batch_layout(
+      K, sh.U, sh.Wk + sh.s, sh.update_ctx && !target->gather ? sh.Wk : -1, sh.E,
+      sh.cached ? hierarchy_to_tree()[ctx.previous_hierarchy_level_] : c.start_level,
+      keys.num_levels(), keys.seed(), keys.party(), start_seeds, start_ctrl, start_stride,
+      reinterpret_cast<const int32_t*>(dtab),
+      tab.need_path ? reinterpret_cast<const dpf_block*>(dtab + tab.off_path) : nullptr,
+      tab.need_save ? reinterpret_cast<const int32_t*>(dtab + tab.off_save) : nullptr,
+      static_cast<dpf_block*>(ctx.next_seeds_), static_cast<uint8_t*>(ctx.next_ctrl_), sh.T,
+      keys.cw_seed(), keys.cw_left(), keys.cw_right(), &kl, &kr, &kv, &c.desc,
+      corrected_elements_per_block(hierarchy_level), keys.value_correction(hierarchy_level),
+      c.native_sum ? 1 : 0, c.native_sum ? static_cast<uint64_t*>(ctx.workspace_) : nullptr,
+      kernel_out, static_cast<dpf_block*>(target->leaf_seeds), target->stride,
+      target->permute ? static_cast<const int32_t*>(ctx.leaf_slot_) : nullptr,
+      ctx.index_major_ ? 1 : 0, stream));
+
+  const void* gather_in = kernel_out;
+  if (row_sum) {
+    // Value types without an on-device key sum in the kernel: a group sum
+    // over the per-key rows.
+    void* summed = device_out;
+    if (gather_out) {
+      DPF_RETURN_IF_ERROR(ensure(&ctx.stage2_, &ctx.stage2_cap_, sh.n_blk * esz));
+      summed = ctx.stage2_;
+    }
+    HIP_RETURN_IF_ERROR(dpf_hip_sum_rows(K, sh.n_blk, &c.desc, ctx.stage_, summed, stream));
+    gather_in = summed;
+  }
+  if (gather_out && sum)
+    HIP_RETURN_IF_ERROR(dpf_hip_gather(sh.P, sh.cnt, esz, d_offsets, gather_in, device_out, stream));
+  if (gather_out && !sum)
+    HIP_RETURN_IF_ERROR(dpf_hip_gather_batched(K, sh.n_blk, sh.P, sh.cnt, esz, d_offsets, gather_in,
+                                               device_out, stream));
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchCore(
+    int hierarchy_level, Span<const uint128> prefixes, DeviceBatchContext& ctx, bool sum,
+    void* device_out, int64_t capacity_bytes, void* stream) const {
+  DPF_RETURN_IF_ERROR(CheckUntilBatchArgs(hierarchy_level, prefixes, ctx));
+  PhaseTimer::Clock clk(g_timing);
+  g_timing.count_call();
+  // Start nodes are indexed by int32 on the device.
+  if (prefixes.size() > static_cast<size_t>(INT32_MAX))
+    return ResourceExhaustedError(
+        "Too many start nodes for one batched evaluation; evaluate fewer levels at once.");
+  const int H = static_cast<int>(parameters().size());
+  const int prev = ctx.previous_hierarchy_level_;
+
   // Unique tree indices in first-seen order and each prefix's (tree index,
   // block index) (h:718-742).
-  const int64_t P = static_cast<int64_t>(prefixes.size());
-  // Host buffers are recycled across calls: first touches of fresh pages cost
-  // more than the bookkeeping itself at 1 M prefixes per level (config 5a).
-  // Not cleared first: DedupTreeIndices overwrites every element, so vectors
-  // kept from an earlier call of about this size value-initialise nothing
-  // (clearing them had cost a 1 M-prefix level ~3.8 ms of single-threaded
-  // zeroing, r16 DPF_BATCH_HOST_TIMING).
-  // Start nodes are indexed by int32 on the device (checked below), so 32-bit
-  // positions suffice: 8-byte (position, block index) entries.
-  if (P > INT32_MAX)
-    return ResourceExhaustedError(
-        "Too many start nodes for one batched evaluation; evaluate fewer levels at once.");
-  std::vector<uint128> tree_indices = std::move(ctx.spare_prefixes_);
-  static thread_local std::vector<std::pair<int32_t, int>> tl_prefix_map;
-  std::vector<std::pair<int32_t, int>>& prefix_map = tl_prefix_map;
-  bool indices_ascending = false;   // tree_indices strictly ascending
-  if (P > 0) {
-    dpf_internal::DedupTreeIndices(prefixes, prev_log - hierarchy_to_tree()[prev], &tree_indices,
-                                   &prefix_map, &indices_ascending);
+  BatchCall c;
+  c.tree_indices = std::move(ctx.spare_prefixes_);  // recycled storage
+  if (!prefixes.empty()) {
+    dpf_internal::DedupTreeIndices(
+        prefixes, parameters()[prev].log_domain_size() - hierarchy_to_tree()[prev], &c.tree_indices,
+        &c.prefix_map, &c.indices_ascending);
   } else {
-    tree_indices.clear();
-    prefix_map.clear();
+    c.tree_indices.assign(1, 0);  // the root, expanded to depth Dh
+    c.prefix_map.clear();
   }
-
   clk.mark(0);
-  // Where each tree index starts: a stored partial evaluation or the root
-  // (ExpandAndUpdateContext cc:455-498, ComputePartialEvaluations cc:351-453).
-  const int Dh = hierarchy_to_tree()[hierarchy_level];
-  int Dprev = 0, start_level = 0;
-  bool from_root = true;
-  static thread_local std::vector<int32_t> tl_parent_of;   // recycled: no per-call zeroing
-  std::vector<int32_t>& parent_of = tl_parent_of;
-  // Physical cache slot of each tree index's node (cached calls; see `cached`
-  // below), filled in the parent lookup's own pass when there is one.
-  static thread_local std::vector<int64_t> tl_start_slot;
-  std::vector<int64_t>& start_slot = tl_start_slot;
-  const bool g_cache_on = CacheOn();
-  bool slots_done = false;
-  if (P == 0) {
-    tree_indices.assign(1, 0);  // the root, expanded to depth Dh
-  } else {
-    Dprev = hierarchy_to_tree()[prev];
-    const auto& q = ctx.partial_prefixes_;
-    if (ctx.partial_evaluations_level_ >= 0 && !q.empty() &&
-        hierarchy_to_tree()[ctx.partial_evaluations_level_] <= Dprev) {
-      start_level = hierarchy_to_tree()[ctx.partial_evaluations_level_];
-      from_root = false;
-      const int shift = Dprev - start_level;
-      // Sortedness of the stored prefixes: known when they came from an
-      // ascending dedup (the hierarchical case), else checked in chunks on
-      // host threads.
-      bool sorted = ctx.partial_sorted_;
-      if (!sorted) {
-        const int64_t nq = static_cast<int64_t>(q.size());
-        const int qchunks = dpf_internal::NumChunks(nq);
-        std::vector<char> q_ok(qchunks, 1);
-        dpf_internal::ParallelChunks(nq, qchunks, [&](int c, int64_t lo, int64_t hi) {
-          for (int64_t j = std::max<int64_t>(lo, 1); j < hi; ++j)
-            if (q[j] < q[j - 1]) {
-              q_ok[c] = 0;
-              return;
-            }
-        });
-        sorted = std::all_of(q_ok.begin(), q_ok.end(), [](char x) { return x != 0; });
-      }
-      std::unordered_map<uint128, int32_t, U128Hash> pos;
-      if (!sorted) {
-        pos.reserve(q.size() * 2);
-        for (size_t j = 0; j < q.size(); ++j) pos.emplace(q[j], static_cast<int32_t>(j));
-      }
-      parent_of.resize(tree_indices.size());
-      const int64_t nt = static_cast<int64_t>(tree_indices.size());
-      // The same condition as `cached` below: the start slots come out of
-      // this pass (one read of tree_indices instead of two).
-      const int w1 = Dprev - start_level;
-      slots_done = g_cache_on && ctx.leaf_seeds_ && ctx.leaf_level_ == prev &&
-                   ctx.leaf_de_ == w1 && ctx.leaf_stride_ <= INT32_MAX;
-      if (slots_done) start_slot.resize(nt);
-      const uint128 slot_mask = slots_done ? (uint128{1} << w1) - 1 : 0;  // w1 <= 62 then
-      const std::vector<int32_t>& phys = ctx.leaf_phys_;
-      std::atomic<int64_t> first_missing{nt};
-      dpf_internal::ParallelFor(nt, [&](int64_t lo, int64_t hi) {
-        size_t cursor = 0;  // merge pointer while the lookups ascend too
-        bool fresh = true;
-        for (int64_t i = lo; i < hi; ++i) {
-          const uint128 want = shift < 128 ? tree_indices[i] >> shift : 0;
-          int64_t j = -1;
-          if (sorted) {
-            if (fresh || cursor >= q.size() || q[cursor] > want) {
-              cursor = std::lower_bound(q.begin(), q.end(), want) - q.begin();
-              fresh = false;
-            } else if (want - q[cursor] < 64) {
-              while (cursor < q.size() && q[cursor] < want) ++cursor;
-            } else {
-              cursor = std::lower_bound(q.begin() + cursor, q.end(), want) - q.begin();
-            }
-            if (cursor < q.size() && q[cursor] == want) j = static_cast<int64_t>(cursor);
-          } else {
-            auto it = pos.find(want);
-            if (it != pos.end()) j = it->second;
-          }
-          if (j < 0) {
-            int64_t cur = first_missing.load();
-            while (i < cur && !first_missing.compare_exchange_weak(cur, i)) {
-            }
-            return;
-          }
-          parent_of[i] = static_cast<int32_t>(j);
-          if (slots_done) {
-            const int64_t logical = (j << w1) | static_cast<int64_t>(tree_indices[i] & slot_mask);
-            start_slot[i] = phys.empty() ? logical : phys[logical];
-          }
-        }
-      });
-      if (first_missing.load() < nt)
-        return InvalidArgumentError(
-            "Prefix not present in ctx.partial_evaluations at hierarchy level " +
-            std::to_string(prev));
-    }
-  }
-  const int64_t T = static_cast<int64_t>(tree_indices.size());
-  const int W1 = Dprev - start_level;
-  const int dE = Dh - Dprev;
+  DPF_RETURN_IF_ERROR(
+      PlanBatchCall(hierarchy_level, static_cast<int64_t>(prefixes.size()), ctx, sum, &c));
+  const UntilBatchShape& sh = c.shape;
+  if (!device_out || capacity_bytes < sh.out_bytes)
+    return InvalidArgumentError("device output buffer too small");
 
-  const auto& f = flat_[hierarchy_level];
-  const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
-  int max_e = dpf_hip_prefix_batch_max_expand(&desc, sum ? 1 : 0);
-  const bool native_sum = sum && max_e >= 0;
-  if (max_e < 0) max_e = dpf_hip_prefix_batch_max_expand(&desc, 0);
-  if (max_e < 0) return UnimplementedError("value type not supported by the batched GPU path");
-  const int E = std::min(dE, max_e);
-  const int s = dE - E;  // levels walked per start node below the tree index
-  if (s > 30 || (T << s) > INT32_MAX)
-    return ResourceExhaustedError(
-        "Too many start nodes for one batched evaluation; evaluate fewer levels at once.");
-  const int64_t U = T << s;
-  const int64_t K = keys.num_keys();
-  // The previous call's expansion cache holds this call's tree nodes (its
-  // leaves are the children, W1 levels down, of the tree indices the
-  // partial evaluations stand for): the kernel reads their seeds from it and
-  // the W1-level path walk is skipped.  Outputs and the
-  // partial evaluations are the same either way.
-  const bool cached = g_cache_on && P > 0 && ctx.leaf_seeds_ && ctx.leaf_level_ == prev &&
-                      ctx.leaf_de_ == W1 && ctx.leaf_stride_ <= INT32_MAX;
-  const int Wk = cached ? 0 : W1;  // levels walked above each tree index
-  const int cepb = corrected_elements_per_block(hierarchy_level);
-  const int esz = f.packed_size;
-  const int64_t block = (int64_t{1} << dE) * cepb;   // elements per tree index
-  const int64_t n_blk = T * block;                  // elements per key before the gather
-  const int64_t cnt = int64_t{1} << (log - prev_log);  // elements per prefix
-  const int64_t n = P == 0 ? n_blk : P * cnt;
-  bool identity = P == 0 || (T == P && cnt == block);
-  for (int64_t i = 0; identity && P > 0 && i < P; ++i)
-    identity = prefix_map[i].first == i && prefix_map[i].second == 0;
-  const int64_t need = (sum ? n : K * n) * esz;
-  if (!device_out || capacity_bytes < need) return InvalidArgumentError("device output buffer too small");
-  const bool update_ctx = P > 0 && hierarchy_level < H - 1;
-
-  // This call's leaves become the next call's expansion cache (not after the
-  // last level).  Preferred: write them to the spare buffer while the kernel
-  // reads the start seeds straight from the current cache, then swap.  With
-  // no room for a spare, the start seeds are gathered first and the current
-  // cache is rewritten in place; a failed allocation only turns the cache off.
-  const int64_t leaf_stride = U << E;
-  void* leaf_seeds = nullptr;
-  int64_t cache_stride = leaf_stride;  // physical row stride of the cache written
-  bool swap_cache = false;
-  bool gather = false;
-  bool permute = false;
-  const uint128 leaf_mask = cached ? (uint128{1} << W1) - 1 : 0;  // W1 <= 62 when cached
-  if (cached && !slots_done) {
-    start_slot.resize(T);
-    const std::vector<int32_t>& phys = ctx.leaf_phys_;
-    dpf_internal::ParallelFor(T, [&](int64_t lo, int64_t hi) {
-      for (int64_t i = lo; i < hi; ++i) {
-        const int64_t logical = (static_cast<int64_t>(from_root ? 0 : parent_of[i]) << W1) |
-                                static_cast<int64_t>(tree_indices[i] & leaf_mask);
-        start_slot[i] = phys.empty() ? logical : phys[logical];
-      }
-    });
-  }
-  static thread_local std::vector<int32_t> tl_leaf_slot;
-  std::vector<int32_t>& leaf_slot = tl_leaf_slot;
-  // Headroom left on the device for everything else (the caller's buffers,
-  // a second context): a quarter of it for the spare, an eighth for the cache.
-  auto fits = [&](size_t bytes, size_t reserve_div) {
-    size_t free_b = 0, total_b = 0;
-    ctx.MemInfo(&free_b, &total_b);
-    return free_b >= bytes + total_b / reserve_div;
-  };
-  if (g_cache_on && hierarchy_level < H - 1 && Dh > 0) {
-    const size_t cache_need = static_cast<size_t>(K * leaf_stride) * sizeof(dpf_block);
-    if (!cached) {
-      // The current cache is not read by this call: rewrite (or regrow) it.
-      ctx.leaf_level_ = -1;  // until this call has written it
-      if (ctx.leaf_seeds_cap_ < cache_need) {
-        HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
-        ctx.Release(&ctx.leaf_seeds_, &ctx.leaf_seeds_cap_);
-        if (!fits(cache_need, 8) || !ctx.TryAlloc(&ctx.leaf_seeds_, &ctx.leaf_seeds_cap_, cache_need))
-          ++ctx.events_.cache_refused;
-      }
-      leaf_seeds = ctx.leaf_seeds_;
-    } else {
-      const CacheMode mode = ForcedCacheMode();
-      const bool want_spare = mode == CacheMode::kAuto || mode == CacheMode::kSpare;
-      if (want_spare && ctx.leaf_spare_cap_ < cache_need) {
-        // The spare may still be read by work in flight on the stream.
-        HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
-        ctx.Release(&ctx.leaf_spare_, &ctx.leaf_spare_cap_);
-        if (!fits(cache_need, 4) || !ctx.TryAlloc(&ctx.leaf_spare_, &ctx.leaf_spare_cap_, cache_need))
-          ++ctx.events_.spare_refused;
-      }
-      if (want_spare && ctx.leaf_spare_ && ctx.leaf_spare_cap_ >= cache_need) {
-        leaf_seeds = ctx.leaf_spare_;
-        swap_cache = true;
-      } else if (mode != CacheMode::kGather && leaf_stride <= ctx.leaf_stride_ &&
-                 BuildSlotTable(start_slot, T, s, E, ctx.leaf_stride_, &leaf_slot)) {
-        // In place through the slot table: no gather, no second buffer.
-        permute = true;
-        leaf_seeds = ctx.leaf_seeds_;
-        cache_stride = ctx.leaf_stride_;
-        ++ctx.events_.permuted;
-      } else {
-        gather = true;  // leaf_seeds is set once the gather is enqueued
-        ++ctx.events_.in_place;
-      }
-    }
-  }
-  const bool direct = cached && !gather;  // start seeds read from the cache
-  // The per-call buffers come first: when device memory runs out, the
-  // expansion cache gives way (the spare, then -- unless this call reads it --
-  // the cache itself) and the allocation is retried.
-  bool cache_in_use = cached;  // read by this call's gather or kernel
-  auto ensure = [&](void** p, size_t* cap, size_t bytes) -> Status {
-    Status st = ctx.Ensure(p, cap, bytes);
-    for (int step = 0; !st.ok() && step < 2; ++step) {
-      void** victim = step == 0 ? &ctx.leaf_spare_ : &ctx.leaf_seeds_;
-      size_t* victim_cap = step == 0 ? &ctx.leaf_spare_cap_ : &ctx.leaf_seeds_cap_;
-      if (!*victim || (step == 1 && cache_in_use)) continue;
-      HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
-      if (leaf_seeds == *victim) {
-        leaf_seeds = nullptr;  // this call writes no cache
-        swap_cache = false;
-      }
-      ctx.Release(victim, victim_cap);
-      ++(step == 0 ? ctx.events_.evicted_spare : ctx.events_.evicted_cache);
-      if (step == 1) ctx.leaf_level_ = -1;
-      st = ctx.Ensure(p, cap, bytes);
-    }
-    return st;
-  };
-
+  // Where this call's leaves go: the next call's expansion cache (not after
+  // the last level).
+  const int64_t leaf_stride = sh.U << sh.E;
+  const bool writes_cache =
+      c.cache_on && hierarchy_level < H - 1 && hierarchy_to_tree()[hierarchy_level] > 0;
+  DPF_ASSIGN_OR_RETURN(c.target,
+                       ctx.ChooseCacheTarget(writes_cache, sh.cached, leaf_stride, c.start_slot,
+                                             sh.T, sh.s, sh.E, &c.leaf_slot, stream));
+  DeviceBatchContext::CacheTarget& target = c.target;
+  if (target.gather) c.source = StartSource::kGathered;
   clk.mark(1);
-  // Start-node tables (u = tree index i * 2^s + sub) and the output gather's
-  // offsets, built in ONE page-locked image on host threads and sent with one
-  // asynchronous H2D into one device buffer: parent[U] int32 | save[U] int32
-  // (only with s > 0: with s == 0 start node u IS tree index u, save_index
-  // NULL) | path[U] (only when the kernel walks, Wk + s > 0) | offsets[P]
-  // int64 (non-identity gathers).  Three synchronous pageable copies of
-  // 24 MiB had cost a 1 M-prefix level (config 5a) milliseconds.
-  const bool need_path = Wk + s > 0;
-  const bool need_save = s > 0;
-  auto align = [](size_t b) { return (b + 255) & ~size_t{255}; };
-  const size_t off_save = align(static_cast<size_t>(U) * sizeof(int32_t));
-  const size_t off_path = off_save + (need_save ? align(static_cast<size_t>(U) * sizeof(int32_t)) : 0);
-  const size_t off_offsets = off_path + (need_path ? align(static_cast<size_t>(U) * sizeof(dpf_block)) : 0);
-  const size_t tables_bytes = off_offsets + (identity ? 0 : static_cast<size_t>(P) * sizeof(int64_t));
-  DPF_RETURN_IF_ERROR(ctx.StageTables(tables_bytes));
-  char* img = static_cast<char*>(ctx.pinned_tables_);
-  int32_t* parent = reinterpret_cast<int32_t*>(img);
-  int32_t* save = need_save ? reinterpret_cast<int32_t*>(img + off_save) : nullptr;
-  dpf_block* path = need_path ? reinterpret_cast<dpf_block*>(img + off_path) : nullptr;
-  const uint128 w1_mask = Wk >= 128 ? ~uint128{0} : ((uint128{1} << Wk) - 1);
-  dpf_internal::ParallelFor(T, [&](int64_t lo, int64_t hi) {
-    if (!path && s == 0) {
-      // One start node per tree index and no walk (the cached steady state):
-      // the parents alone, without reading the tree indices.
-      for (int64_t i = lo; i < hi; ++i)
-        parent[i] = direct ? static_cast<int32_t>(start_slot[i])
-                    : gather ? static_cast<int32_t>(i)
-                             : (from_root ? 0 : parent_of[i]);
-      return;
-    }
-    for (int64_t i = lo; i < hi; ++i) {
-      const uint128 low = tree_indices[i] & w1_mask;
-      // Cached: the physical cache slot of tree index i.
-      const int64_t slot = cached ? start_slot[i] : 0;
-      const int32_t start = direct ? static_cast<int32_t>(slot)
-                            : gather ? static_cast<int32_t>(i)
-                                     : (from_root ? 0 : parent_of[i]);
-      for (int64_t sub = 0; sub < (int64_t{1} << s); ++sub) {
-        const int64_t u = (i << s) + sub;
-        parent[u] = start;
-        if (path) path[u] = ToBlock(s ? ((low << s) | static_cast<uint128>(sub)) : low);
-        if (save) save[u] = sub == 0 ? static_cast<int32_t>(i) : -1;
-      }
-    }
-  });
-  if (!identity) {
-    int64_t* offsets = reinterpret_cast<int64_t*>(img + off_offsets);
-    dpf_internal::ParallelFor(P, [&](int64_t lo, int64_t hi) {
-      for (int64_t i = lo; i < hi; ++i)
-        offsets[i] = prefix_map[i].first * block + prefix_map[i].second * cnt;
-    });
-  }
+
+  // The start-node tables and gather offsets: built in one page-locked image,
+  // sent with one copy.  The per-call buffers come before anything else that
+  // allocates: when device memory runs out, the expansion cache gives way.
+  const dpf_internal::TableLayout& tab = c.tables = dpf_internal::PlanTables(sh);
+  DPF_RETURN_IF_ERROR(ctx.StageTables(tab.bytes));
+  dpf_internal::FillTables(sh, tab, c.source, c.tree_indices.data(), c.parent_of.data(),
+                           c.start_slot.data(), c.prefix_map, static_cast<char*>(ctx.pinned_tables_));
   clk.mark(2);
-  DPF_RETURN_IF_ERROR(ensure(&ctx.parent_, &ctx.parent_cap_, tables_bytes));
-  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d_async(ctx.parent_, img, tables_bytes, stream));
-  DPF_RETURN_IF_ERROR(ctx.TablesSent(stream));
-  char* dtab = static_cast<char*>(ctx.parent_);
-  const int32_t* d_parent = reinterpret_cast<const int32_t*>(dtab);
-  const int32_t* d_save = need_save ? reinterpret_cast<const int32_t*>(dtab + off_save) : nullptr;
-  const dpf_block* d_path = need_path ? reinterpret_cast<const dpf_block*>(dtab + off_path) : nullptr;
-  const int64_t* d_offsets = identity ? nullptr : reinterpret_cast<const int64_t*>(dtab + off_offsets);
-  if (update_ctx || gather) {
-    DPF_RETURN_IF_ERROR(ensure(&ctx.next_seeds_, &ctx.next_seeds_cap_,
-                                                   K * T * sizeof(dpf_block)));
-    DPF_RETURN_IF_ERROR(ensure(&ctx.next_ctrl_, &ctx.next_ctrl_cap_, K * T));
+  DPF_RETURN_IF_ERROR(ctx.SendTables(tab.bytes, &target, stream));
+  if (sh.update_ctx || target.gather) {
+    const int64_t K = ctx.keys().num_keys();
+    DPF_RETURN_IF_ERROR(ctx.EnsureEvicting(&ctx.next_seeds_, &ctx.next_seeds_cap_,
+                                           K * sh.T * sizeof(dpf_block), &target, stream));
+    DPF_RETURN_IF_ERROR(
+        ctx.EnsureEvicting(&ctx.next_ctrl_, &ctx.next_ctrl_cap_, K * sh.T, &target, stream));
   }
-  if (gather) {
-    // The start seeds (and, with update_ctx, the new partial evaluations),
-    // read before the kernel rewrites the cache.
-    DPF_RETURN_IF_ERROR(ensure(&ctx.slots_, &ctx.slots_cap_, T * sizeof(int64_t)));
-    HIP_RETURN_IF_ERROR(
-        dpf_hip_memcpy_h2d(ctx.slots_, start_slot.data(), T * sizeof(int64_t), stream));
-    HIP_RETURN_IF_ERROR(dpf_hip_gather_seeds_layout(
-        K, T, static_cast<const int64_t*>(ctx.slots_), static_cast<const dpf_block*>(ctx.leaf_seeds_),
-        ctx.leaf_stride_, static_cast<dpf_block*>(ctx.next_seeds_),
-        static_cast<uint8_t*>(ctx.next_ctrl_), ctx.index_major_ ? 1 : 0, stream));
-    cache_in_use = false;  // copied out; from here on only the write target
-    ctx.leaf_level_ = -1;  // rewritten in place by this call's kernel
-    const size_t cache_need = static_cast<size_t>(K * leaf_stride) * sizeof(dpf_block);
-    if (ctx.leaf_seeds_cap_ < cache_need) {
-      // Regrow once the gather has read the old cache.
-      HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
-      ctx.Release(&ctx.leaf_seeds_, &ctx.leaf_seeds_cap_);
-      if (!fits(cache_need, 8) || !ctx.TryAlloc(&ctx.leaf_seeds_, &ctx.leaf_seeds_cap_, cache_need))
-        ++ctx.events_.cache_refused;
-    }
-    leaf_seeds = ctx.leaf_seeds_;
-  }
-  if (permute) {
-    const size_t bytes = leaf_slot.size() * sizeof(int32_t);
-    DPF_RETURN_IF_ERROR(ensure(&ctx.leaf_slot_, &ctx.leaf_slot_cap_, bytes));
-    HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(ctx.leaf_slot_, leaf_slot.data(), bytes, stream));
-    ctx.leaf_level_ = -1;  // rewritten in place by this call's kernel
-  }
-
+  // The start seeds (and, with update_ctx, the new partial evaluations) are
+  // read before the kernel rewrites the cache.
+  if (target.gather)
+    DPF_RETURN_IF_ERROR(ctx.GatherStartSeeds(c.start_slot, sh.T, leaf_stride, &target, stream));
+  if (target.permute) DPF_RETURN_IF_ERROR(ctx.SendSlotTable(c.leaf_slot, &target, stream));
   clk.mark(3);
-  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
-  // Cached start seeds carry their control bit in bit 0 (control_in NULL).
-  const dpf_block* start_seeds =
-      direct   ? static_cast<const dpf_block*>(ctx.leaf_seeds_)
-      : gather ? static_cast<const dpf_block*>(ctx.next_seeds_)
-               : (from_root ? nullptr : ctx.partial_seeds());
-  const uint8_t* start_ctrl = direct   ? nullptr
-                              : gather ? static_cast<const uint8_t*>(ctx.next_ctrl_)
-                                       : (from_root ? nullptr : ctx.partial_control());
-  const int64_t start_stride = direct   ? ctx.leaf_stride_
-                               : gather ? T
-                                        : static_cast<int64_t>(ctx.partial_prefixes_.size());
-  auto launch = [&](int sum_mode, void* out, uint64_t* workspace) {
-    return FromHip(dpf_hip_eval_prefix_batch_layout(
-        K, U, Wk + s, update_ctx && !gather ? Wk : -1, E, cached ? Dprev : start_level,
-        keys.num_levels(), keys.seed(), keys.party(), start_seeds, start_ctrl, start_stride,
-        d_parent, d_path, d_save, static_cast<dpf_block*>(ctx.next_seeds_),
-        static_cast<uint8_t*>(ctx.next_ctrl_), T, keys.cw_seed(), keys.cw_left(), keys.cw_right(),
-        &kl, &kr, &kv, &desc, cepb, keys.value_correction(hierarchy_level), sum_mode, workspace,
-        out, static_cast<dpf_block*>(leaf_seeds), cache_stride,
-        permute ? static_cast<const int32_t*>(ctx.leaf_slot_) : nullptr, ctx.index_major_ ? 1 : 0,
-        stream));
-  };
-  if (native_sum) {
-    void* target = device_out;
-    if (!identity) {
-      DPF_RETURN_IF_ERROR(ensure(&ctx.stage_, &ctx.stage_cap_, n_blk * esz));
-      target = ctx.stage_;
-    }
-    DPF_RETURN_IF_ERROR(ensure(
-        &ctx.workspace_, &ctx.workspace_cap_, n_blk * f.leaves.size() * 3 * sizeof(uint64_t)));
-    DPF_RETURN_IF_ERROR(launch(1, target, static_cast<uint64_t*>(ctx.workspace_)));
-    if (!identity)
-      HIP_RETURN_IF_ERROR(dpf_hip_gather(P, cnt, esz, d_offsets,
-                                         ctx.stage_, device_out, stream));
-  } else if (sum) {
-    // Value types without an on-device key sum in the kernel: per-key rows,
-    // then a group sum over the rows.
-    DPF_RETURN_IF_ERROR(ensure(&ctx.stage_, &ctx.stage_cap_, K * n_blk * esz));
-    DPF_RETURN_IF_ERROR(launch(0, ctx.stage_, nullptr));
-    void* target = device_out;
-    if (!identity) {
-      DPF_RETURN_IF_ERROR(ensure(&ctx.stage2_, &ctx.stage2_cap_, n_blk * esz));
-      target = ctx.stage2_;
-    }
-    HIP_RETURN_IF_ERROR(dpf_hip_sum_rows(K, n_blk, &desc, ctx.stage_, target, stream));
-    if (!identity)
-      HIP_RETURN_IF_ERROR(dpf_hip_gather(P, cnt, esz, d_offsets,
-                                         ctx.stage2_, device_out, stream));
-  } else {
-    void* target = device_out;
-    if (!identity) {
-      DPF_RETURN_IF_ERROR(ensure(&ctx.stage_, &ctx.stage_cap_, K * n_blk * esz));
-      target = ctx.stage_;
-    }
-    DPF_RETURN_IF_ERROR(launch(0, target, nullptr));
-    if (!identity)
-      HIP_RETURN_IF_ERROR(dpf_hip_gather_batched(K, n_blk, P, cnt, esz,
-                                                 d_offsets,
-                                                 ctx.stage_, device_out, stream));
-  }
 
-  if (swap_cache) {
-    std::swap(ctx.leaf_seeds_, ctx.leaf_spare_);
-    std::swap(ctx.leaf_seeds_cap_, ctx.leaf_spare_cap_);
-  }
-  ctx.leaf_level_ = leaf_seeds ? hierarchy_level : -1;
-  ctx.leaf_de_ = dE;
-  ctx.leaf_stride_ = cache_stride;
-  if (permute)
-    ctx.leaf_phys_.assign(leaf_slot.begin(), leaf_slot.end());
-  else
-    ctx.leaf_phys_.clear();   // written in leaf order
-  // After the last level nothing reads the cache; its buffers stay allocated
-  // for the next pass over the hierarchy (Reset()), because giving them back
-  // and regrowing them level by level (4, 16, 64 GiB for 2^20 heavy-hitters
-  // clients) cost 3.7 s per 22 s pass (profiles/r14_ab.txt).  The 1/8-of-HBM
-  // headroom rule above bounds what they take; callers that need the memory
-  // call ReleaseExpansionCache() (or Reset(true)).
-  if (hierarchy_level == H - 1) ctx.leaf_level_ = -1;
-  if (g_timing_on) dpf_hip_stream_sync(stream);  // attribute device time to its phase
+  DPF_RETURN_IF_ERROR(
+      LaunchBatchCall(hierarchy_level, c, ctx, sum, device_out, stream));
+
+  ctx.CommitCache(target, hierarchy_level, sh.dE, hierarchy_level == H - 1, c.leaf_slot);
+  if (g_timing.on()) dpf_hip_stream_sync(stream);  // attribute device time to its phase
   clk.mark(4);
-  // Context update (cc:435-451, 494-496).
-  ctx.previous_hierarchy_level_ = hierarchy_level;
-  if (P > 0) {
-    if (update_ctx) {
-      std::swap(ctx.partial_prefixes_, tree_indices);
-      ctx.partial_sorted_ = indices_ascending;
-      std::swap(ctx.seeds_, ctx.next_seeds_);
-      std::swap(ctx.seeds_cap_, ctx.next_seeds_cap_);
-      std::swap(ctx.ctrl_, ctx.next_ctrl_);
-      std::swap(ctx.ctrl_cap_, ctx.next_ctrl_cap_);
-    } else {
-      ctx.partial_prefixes_.clear();
-      ctx.partial_sorted_ = false;
-    }
-    ctx.partial_evaluations_level_ = prev;
-  }
-  ctx.spare_prefixes_ = std::move(tree_indices);
+  ctx.CommitPartials(hierarchy_level, prev, sh.P > 0, sh.update_ctx, c.indices_ascending,
+                     &c.tree_indices);
   clk.mark(5);
-  return n;
+  return sh.n;
 }
 
 StatusOr<EvaluationContext> DistributedPointFunction::ExportEvaluationContext(

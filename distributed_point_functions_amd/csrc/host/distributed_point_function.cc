@@ -22,6 +22,7 @@
 
 #include "dpf_hip.h"
 #include "host_util.h"
+#include "until_plan.h"
 
 namespace distributed_point_functions {
 
@@ -315,37 +316,13 @@ PackedCws AddCorrectionWords(const DpfKey& key, int start, int stop, PackedUploa
 // with DPF_HOST_TIMING: the lookup of the stored evaluations, the image and
 // its upload, the walk on the device (with the walked seeds' D2H), and the
 // context rewrite.
-struct WalkTiming {
-  double t[4] = {0, 0, 0, 0};
-  long calls = 0;
-  ~WalkTiming() {
-    if (calls > 0 && std::getenv("DPF_HOST_TIMING"))
+dpf_internal::PhaseTimer g_walk_timing(
+    "DPF_HOST_TIMING", 0, [](long calls, double n, const double* t) {
       std::fprintf(stderr,
                    "[prefix walk host timing] calls=%ld per call: lookup=%.2fus upload=%.2fus "
                    "device=%.2fus context=%.2fus\n",
-                   calls, t[0] * 1e6 / calls, t[1] * 1e6 / calls, t[2] * 1e6 / calls,
-                   t[3] * 1e6 / calls);
-  }
-};
-WalkTiming g_walk_timing;
-std::mutex g_walk_timing_mu;
-const bool g_walk_timing_on = std::getenv("DPF_HOST_TIMING") != nullptr;
-struct WalkClock {
-  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
-  double t[4] = {0, 0, 0, 0};
-  void mark(int phase) {
-    if (!g_walk_timing_on) return;
-    auto now = std::chrono::steady_clock::now();
-    t[phase] += std::chrono::duration<double>(now - last).count();
-    last = now;
-  }
-  ~WalkClock() {
-    if (!g_walk_timing_on) return;
-    std::lock_guard<std::mutex> lock(g_walk_timing_mu);
-    ++g_walk_timing.calls;
-    for (int i = 0; i < 4; ++i) g_walk_timing.t[i] += t[i];
-  }
-};
+                   calls, t[0] * 1e6 / n, t[1] * 1e6 / n, t[2] * 1e6 / n, t[3] * 1e6 / n);
+    });
 }  // namespace
 
 Status DistributedPointFunction::ComputePartialEvaluations(
@@ -357,7 +334,8 @@ Status DistributedPointFunction::ComputePartialEvaluations(
   const int stop_level = hierarchy_to_tree()[hierarchy_level];
   auto* s = scratch_.get();
   std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
-  WalkClock wclk;
+  dpf_internal::PhaseTimer::Clock wclk(g_walk_timing);
+  g_walk_timing.count_call();
   // The walk's inputs -- start seeds, control bits, paths, correction words --
   // go up as ONE packed image (read in place by the kernel when small); the
   // start seeds and control bits are written straight into it.
@@ -531,40 +509,16 @@ namespace {
 // Host-phase timing of EvaluateUntil, printed at exit when DPF_HOST_TIMING is
 // set: where a small call's microseconds go (validation, uploads, launch,
 // output copy).
-struct UntilTiming {
-  double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long calls = 0;
-  ~UntilTiming() {
-    const double n = static_cast<double>(calls - 100);
-    if (calls > 100 && std::getenv("DPF_HOST_TIMING"))
+// The first 100 calls (allocations, page-locked buffers) are not counted.
+dpf_internal::PhaseTimer g_until_timing(
+    "DPF_HOST_TIMING", 100, [](long calls, double n, const double* t) {
       std::fprintf(stderr,
                    "[EvaluateUntil host timing] calls=%ld per call: validate=%.2fus "
                    "dedup=%.2fus walk+vcw=%.2fus pack=%.2fus commit=%.2fus launch=%.2fus "
                    "reserve=%.2fus copy=%.2fus\n",
                    calls, t[7] * 1e6 / n, t[0] * 1e6 / n, t[5] * 1e6 / n, t[6] * 1e6 / n,
                    t[1] * 1e6 / n, t[2] * 1e6 / n, t[3] * 1e6 / n, t[4] * 1e6 / n);
-  }
-};
-UntilTiming g_until_timing;
-std::mutex g_until_timing_mu;  // the counters are process-wide; calls on several objects race
-const bool g_until_timing_on = std::getenv("DPF_HOST_TIMING") != nullptr;
-struct UntilClock {
-  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
-  void count_call() {
-    if (!g_until_timing_on) return;
-    std::lock_guard<std::mutex> lock(g_until_timing_mu);
-    ++g_until_timing.calls;
-  }
-  void mark(int phase) {
-    if (!g_until_timing_on) return;
-    auto now = std::chrono::steady_clock::now();
-    // The first 100 calls (allocations, page-locked buffers) are not counted.
-    std::lock_guard<std::mutex> lock(g_until_timing_mu);
-    if (g_until_timing.calls > 100)
-      g_until_timing.t[phase] += std::chrono::duration<double>(now - last).count();
-    last = now;
-  }
-};
+    });
 }  // namespace
 
 namespace {
@@ -573,10 +527,7 @@ namespace {
 // once: an A/B hook.
 constexpr int kSplitLevels = 3;
 constexpr int kSplitParts = 1 << kSplitLevels;
-bool SplitOn() {
-  const char* v = std::getenv("DPF_EVAL_SPLIT");
-  return !(v && v[0] == '0');
-}
+bool SplitOn() { return !dpf_internal::hook_is("DPF_EVAL_SPLIT", '0'); }
 }  // namespace
 
 Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<const uint128> prefixes,
@@ -586,7 +537,7 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
                                                    void* stream, const HostSink* host_out,
                                                    int64_t* num_elements) const {
   // h:641-837
-  UntilClock clk;
+  dpf_internal::PhaseTimer::Clock clk(g_until_timing);
   DPF_RETURN_IF_ERROR(validator_->ValidateEvaluationContext(ctx));
   const int H = static_cast<int>(parameters().size());
   if (hierarchy_level < 0 || hierarchy_level >= H)
@@ -607,23 +558,13 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
   const int previous_hierarchy_level = ctx.previous_hierarchy_level();
   if (!prefixes.empty()) {
     previous_log_domain_size = parameters()[previous_hierarchy_level].log_domain_size();
-    if (previous_log_domain_size < 128) {
-      // The first out-of-range prefix is the one reported, as the reference's
-      // loop does; the scan runs on host threads.
-      const uint128 limit = static_cast<uint128>(1) << previous_log_domain_size;
-      const int64_t np = static_cast<int64_t>(prefixes.size());
-      const int chunks = dpf_internal::NumChunks(np);
-      std::vector<int64_t> first_bad(chunks, np);
-      dpf_internal::ParallelChunks(np, chunks, [&](int c, int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i)
-          if (prefixes[i] >= limit) { first_bad[c] = i; return; }
-      });
-      const int64_t bad = *std::min_element(first_bad.begin(), first_bad.end());
-      if (bad < np)
-        return InvalidArgumentError("Index " + Uint128ToString(prefixes[bad]) +
-                                    " out of range for hierarchy level " +
-                                    std::to_string(previous_hierarchy_level));
-    }
+    // The first out-of-range prefix is the one reported, as the reference's
+    // loop does.
+    const int64_t bad = dpf_internal::FirstOutOfRangePrefix(prefixes, previous_log_domain_size);
+    if (bad < static_cast<int64_t>(prefixes.size()))
+      return InvalidArgumentError("Index " + Uint128ToString(prefixes[bad]) +
+                                  " out of range for hierarchy level " +
+                                  std::to_string(previous_hierarchy_level));
   }
   const int log_domain_size = parameters()[hierarchy_level].log_domain_size();
   if (log_domain_size - previous_log_domain_size > 62)
@@ -663,7 +604,7 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
 
   // ExpandAndUpdateContext (cc:455-498): starting seeds on the device.  The
   // value correction of this level (h:761-780) is parsed before device work.
-  clk.count_call();
+  g_until_timing.count_call();
   clk.mark(0);
   std::vector<uint128> vcw;
   auto parse_vcw = [&]() -> Status {
@@ -741,16 +682,8 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
   bool identity = true;
   if (num_prefixes > 0) {
     identity = (outputs_per_prefix == blocks_per_tree_prefix * cepb) &&
-               static_cast<int64_t>(tree_indices.size()) == num_prefixes;
-    if (identity) {
-      const int chunks = dpf_internal::NumChunks(num_prefixes);
-      std::vector<char> ok(chunks, 1);
-      dpf_internal::ParallelChunks(num_prefixes, chunks, [&](int c, int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i)
-          if (prefix_map[i].first != i || prefix_map[i].second != 0) { ok[c] = 0; return; }
-      });
-      identity = std::all_of(ok.begin(), ok.end(), [](char x) { return x != 0; });
-    }
+               static_cast<int64_t>(tree_indices.size()) == num_prefixes &&
+               dpf_internal::IsIdentityMap(prefix_map, num_prefixes);
   }
   // A small host result is written by the kernels straight into page-locked
   // memory (PinnedOut): no D2H copy.
@@ -802,11 +735,8 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
   void* result = expand_out;
   if (!identity) {
     std::vector<int64_t> offsets(num_prefixes);
-    dpf_internal::ParallelFor(num_prefixes, [&](int64_t lo, int64_t hi) {
-      for (int64_t i = lo; i < hi; ++i)
-        offsets[i] = prefix_map[i].first * blocks_per_tree_prefix * cepb +
-                     prefix_map[i].second * outputs_per_prefix;
-    });
+    dpf_internal::FillGatherOffsets(prefix_map, num_prefixes, blocks_per_tree_prefix * cepb,
+                                    outputs_per_prefix, offsets.data());
     DPF_RETURN_IF_ERROR(s->Upload(s->offsets, offsets.data(), offsets.size(), stream));
     if (device_out) {
       if (capacity_bytes < total * esz) return InvalidArgumentError("device output buffer too small");
@@ -952,37 +882,14 @@ namespace {
 // device = waiting for the upload and the kernel (timing runs only: the
 // stream is synchronised there), copy = the D2H into the caller's vector
 // (unpacked chunk by chunk).
-struct AtTiming {
-  double t[6] = {0, 0, 0, 0, 0, 0};
-  long calls = 0;
-  ~AtTiming() {
-    const double n = static_cast<double>(calls - 10);
-    if (calls > 10 && std::getenv("DPF_HOST_TIMING"))
+dpf_internal::PhaseTimer g_at_timing(
+    "DPF_HOST_TIMING", 10, [](long calls, double n, const double* t) {
       std::fprintf(stderr,
                    "[EvaluateAt host timing] calls=%ld per call: checks=%.2fus key=%.2fus "
                    "upload=%.2fus launch=%.2fus device=%.2fus copy=%.2fus\n",
                    calls, t[0] * 1e6 / n, t[1] * 1e6 / n, t[2] * 1e6 / n, t[3] * 1e6 / n,
                    t[4] * 1e6 / n, t[5] * 1e6 / n);
-  }
-};
-AtTiming g_at_timing;
-std::mutex g_at_timing_mu;
-struct AtClock {
-  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
-  AtClock() {
-    if (!g_until_timing_on) return;
-    std::lock_guard<std::mutex> lock(g_at_timing_mu);
-    ++g_at_timing.calls;
-  }
-  void mark(int phase) {
-    if (!g_until_timing_on) return;
-    auto now = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lock(g_at_timing_mu);
-    if (g_at_timing.calls > 10)
-      g_at_timing.t[phase] += std::chrono::duration<double>(now - last).count();
-    last = now;
-  }
-};
+    });
 
 // First index in [0, n) whose point exceeds max_point (n if none), found on
 // host threads while `fill(lo, hi)` writes the kernel's per-point arrays.
@@ -1013,7 +920,8 @@ Status DistributedPointFunction::EvaluateAtToHost(const DpfKey& key, int hierarc
                                                   const ValueType* requested_type,
                                                   const HostSink& sink) const {
   // h:839-1010
-  AtClock clk;
+  g_at_timing.count_call();
+  dpf_internal::PhaseTimer::Clock clk(g_at_timing);
   if (ctx != nullptr && &key != &ctx->key())
     return InvalidArgumentError("`key` and `ctx->key()` must refer to the same object");
   if (hierarchy_level < 0) return InvalidArgumentError("`hierarchy_level` must be non-negative");
@@ -1102,7 +1010,7 @@ Status DistributedPointFunction::EvaluateAtToHost(const DpfKey& key, int hierarc
   DPF_RETURN_IF_ERROR(up.MarkUsed(nullptr));
   if (ctx) DPF_RETURN_IF_ERROR(s->packed_pe.MarkUsed(nullptr));   // start seeds read from it
   clk.mark(3);
-  if (g_until_timing_on) {
+  if (g_at_timing.on()) {
     HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(nullptr));
     clk.mark(4);
   }

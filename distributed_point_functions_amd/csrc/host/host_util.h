@@ -5,11 +5,14 @@
 #define DPF_HOST_HOST_UTIL_H_
 
 #include <algorithm>
+#include <chrono>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <unordered_map>
 #include <utility>
@@ -37,6 +40,84 @@ inline Status FromHip(int code) {
   return Status(static_cast<StatusCode>(code), dpf_hip_last_error());
 }
 #define HIP_RETURN_IF_ERROR(expr) DPF_RETURN_IF_ERROR(::distributed_point_functions::dpf_internal::FromHip(expr))
+
+// Hooks: the DPF_* environment variables, read when called (nothing is
+// cached; a site that reads one at load or at creation keeps the result
+// itself).  The host-side twins of csrc/kernels/dpf_runtime.h's readers.
+// hook_is: the hook's first character is `c` (unset or empty: no).
+inline bool hook_is(const char* name, char c) {
+  const char* v = std::getenv(name);
+  return v && v[0] == c;
+}
+inline bool hook_set(const char* name) { return std::getenv(name) != nullptr; }
+// The hook's text; unset: "".
+inline std::string hook_str(const char* name) {
+  const char* v = std::getenv(name);
+  return v ? v : "";
+}
+// The hook as a number; unset or empty: `dflt`.  hook_int clamps to [lo, hi].
+inline long long hook_long(const char* name, long long dflt) {
+  const char* v = std::getenv(name);
+  return v && *v ? std::strtoll(v, nullptr, 10) : dflt;
+}
+inline int hook_int(const char* name, int dflt, int lo = INT32_MIN, int hi = INT32_MAX) {
+  const char* v = std::getenv(name);
+  if (!v || !*v) return dflt;
+  const int k = std::atoi(v);
+  return k < lo ? lo : (k > hi ? hi : k);
+}
+
+// Host-phase timing of one call path, a diagnostic: a process-wide
+// PhaseTimer adds up the seconds its calls spend in each phase and, at exit,
+// hands the totals to `report` -- when `hook` is set and more than `skip`
+// calls were counted.  Phases are only added while the call count is above
+// `skip` (the first calls pay for allocations and page-locked buffers).
+// Whether timing is on is read once, when the timer is constructed (at
+// load).  Calls on several threads share a timer, so updates take `mu_`.
+class PhaseTimer {
+ public:
+  static constexpr int kMaxPhases = 8;
+  // `counted` = calls - skip, the calls whose phases were added.
+  using Report = void (*)(long calls, double counted, const double* t);
+  PhaseTimer(const char* hook, long skip, Report report)
+      : hook_(hook), skip_(skip), report_(report), on_(hook_set(hook)) {}
+  ~PhaseTimer() {
+    if (calls_ > skip_ && hook_set(hook_)) report_(calls_, static_cast<double>(calls_ - skip_), t_);
+  }
+  bool on() const { return on_; }
+  void count_call() {
+    if (!on_) return;
+    std::lock_guard<std::mutex> lock(mu_);
+    ++calls_;
+  }
+  // A call's clock: mark(phase) adds the time since the previous mark (or the
+  // clock's construction) to `phase`.
+  class Clock {
+   public:
+    explicit Clock(PhaseTimer& timer) : timer_(timer) {}
+    void mark(int phase) {
+      if (!timer_.on_) return;
+      auto now = std::chrono::steady_clock::now();
+      std::lock_guard<std::mutex> lock(timer_.mu_);
+      if (timer_.calls_ > timer_.skip_)
+        timer_.t_[phase] += std::chrono::duration<double>(now - last_).count();
+      last_ = now;
+    }
+
+   private:
+    PhaseTimer& timer_;
+    std::chrono::steady_clock::time_point last_ = std::chrono::steady_clock::now();
+  };
+
+ private:
+  const char* hook_;
+  const long skip_;
+  const Report report_;
+  const bool on_;
+  std::mutex mu_;
+  double t_[kMaxPhases] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long calls_ = 0;
+};
 
 // Events marking how much of a device output produced in parts on one stream
 // is complete: part j = [0, ends[j]) once events[j] has completed.
@@ -79,10 +160,7 @@ class PartEvents {
 // before (A/B and test hook).
 constexpr size_t kOverlapGrowMin = size_t{4} << 20;
 constexpr size_t kOverlapGrowLimit = size_t{32} << 20;
-inline bool OverlapGrowOn() {
-  const char* v = std::getenv("DPF_OVERLAP_GROW");
-  return !(v && v[0] == '0');
-}
+inline bool OverlapGrowOn() { return !hook_is("DPF_OVERLAP_GROW", '0'); }
 
 // Copies `bytes` of device output into the storage `dst` a HostSink reserved,
 // letting its grow() initialise each chunk right before that chunk's DMA
@@ -195,8 +273,7 @@ struct U128Hash {
 // per GPU.
 inline int HostThreads() {
   static const int n = [] {
-    const char* e = std::getenv("DPF_HOST_THREADS");
-    const int v = e ? std::atoi(e) : 0;
+    const int v = hook_int("DPF_HOST_THREADS", 0);
     if (v >= 1) return v;
     return static_cast<int>(std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency())));
   }();
@@ -513,10 +590,7 @@ class PackedUploads {
  private:
   static constexpr size_t kMaxPinned = size_t{64} << 20;
   static constexpr size_t kZeroCopyMax = size_t{128} << 10;
-  static bool ZeroCopyOn() {
-    const char* v = std::getenv("DPF_UPLOAD_ZERO_COPY");
-    return !(v && v[0] == '0');
-  }
+  static bool ZeroCopyOn() { return !hook_is("DPF_UPLOAD_ZERO_COPY", '0'); }
   char* base() { return pageable_ ? image_.get() : static_cast<char*>(pinned_); }
   // Pageable image of at least `end` bytes holding [0, size_) of the current one
   // (uninitialised beyond: no value-initialisation pass over a large image).
@@ -623,8 +697,7 @@ class PinnedOut {
   }
   // Page-locked room for `bytes`, or nullptr (too large, off, or no memory).
   void* Get(size_t bytes) {
-    const char* v = std::getenv("DPF_OUTPUT_ZERO_COPY");
-    if (bytes == 0 || bytes > kMax || (v && v[0] == '0')) return nullptr;
+    if (bytes == 0 || bytes > kMax || hook_is("DPF_OUTPUT_ZERO_COPY", '0')) return nullptr;
     if (!p_ && dpf_hip_host_alloc(&p_, kMax) != 0) p_ = nullptr;
     return p_;
   }

@@ -840,6 +840,158 @@ int check_slot_table(int64_t num_starts, int expand_levels, const int32_t* paren
   }
   return kOk;
 }
+
+// The checks of dpf_hip_eval_prefix_batch* that read no pointer but `desc`:
+// the value type and the level arithmetic.
+int check_batch_levels(const dpf_value_desc* desc, int sum, int64_t num_keys, int64_t num_starts,
+                       int walk_levels, int save_after, int expand_levels, int cw_first,
+                       int cw_stride, int elements_per_leaf) {
+  int st = validate_desc(desc);
+  if (st) return st;
+  const int max_e = dpf_hip_prefix_batch_max_expand(desc, sum);
+  if (max_e < 0)
+    return fail(kUnimplemented, "no on-device key sum for this value type (use store mode)");
+  if (num_keys < 0 || num_starts < 0 || num_starts > INT32_MAX || walk_levels < 0 ||
+      expand_levels < 0 || expand_levels > max_e || save_after < -1 || save_after > walk_levels ||
+      cw_first < 0 || cw_first + walk_levels + expand_levels > cw_stride ||
+      walk_levels > 128 || cw_stride > 4096)
+    return fail(kInvalidArgument, "level arguments out of range");
+  if (elements_per_leaf < 1 || elements_per_leaf > desc->elements_per_block)
+    return fail(kInvalidArgument, "elements_per_leaf must be in [1, elements_per_block]");
+  return kOk;
+}
+
+// The pointers a launch with work to do (keys and start nodes) reads or writes.
+int check_batch_pointers(const BatchLevelParams& p, int sum, const dpf_aes_key* key_left,
+                         const dpf_aes_key* key_right, const dpf_aes_key* key_value) {
+  if (!p.party || !p.vcw || !key_left || !key_right || !key_value || (!sum && !p.out) ||
+      (!p.seeds_in && !p.key_seed) || (p.seeds_in && !p.parent) ||
+      (p.walk_levels > 0 && !p.path) || (p.save_after >= 0 && (!p.seeds_out || !p.ctrl_out)) ||
+      (p.walk_levels + p.expand_levels > 0 && (!p.cw_seed || !p.cw_left || !p.cw_right)))
+    return fail(kInvalidArgument, "NULL pointer");
+  return kOk;
+}
+
+// Key chunks: a wave task is 64 start nodes of one chunk of keys.  ~4 wave
+// tasks per wave slot, 16 when they are taken dynamically.
+void plan_key_chunks(BatchLevelParams* p) {
+  p->waves_per_chunk = (p->num_starts + 63) / 64;
+  const int64_t want_waves =
+      (int64_t)num_cus() * (kBlock / 64) * (hook_is("DPF_BATCH_DYNAMIC", '0') ? 4 : 16);
+  int64_t chunks = (want_waves + p->waves_per_chunk - 1) / p->waves_per_chunk;
+  if (chunks > p->num_keys) chunks = p->num_keys;
+  if (chunks < 1) chunks = 1;
+  p->chunk_keys = (p->num_keys + chunks - 1) / chunks;
+  chunks = (p->num_keys + p->chunk_keys - 1) / p->chunk_keys;
+  p->num_threads = chunks * p->waves_per_chunk * 64;
+}
+
+// The expansion cache the launch writes: room for every leaf, and no overlap
+// with the start seeds except in place through a slot table.
+int attach_leaf_cache(BatchLevelParams* p, dpf_block* leaf_cache, int64_t leaf_stride,
+                      const int32_t* leaf_slot, hipStream_t s) {
+  if (leaf_stride < (p->num_starts << p->expand_levels))
+    return fail(kInvalidArgument, "expansion cache too small");
+  // In place (leaf_cache == seeds_in) only through a slot table, whose
+  // contract (include/dpf_hip.h) keeps every entry's read before its write.
+  const bool in_place =
+      leaf_slot && leaf_cache == p->seeds_in && p->in_stride == leaf_stride && !p->ctrl_in;
+  if (p->seeds_in && !in_place &&
+      (const void*)leaf_cache < (const void*)(p->seeds_in + p->num_keys * p->in_stride) &&
+      (const void*)p->seeds_in < (const void*)(leaf_cache + p->num_keys * leaf_stride))
+    return fail(kInvalidArgument, "expansion cache overlaps the start seeds");
+  p->leaf_seeds = leaf_cache;
+  p->leaf_stride = leaf_stride;
+  p->leaf_slot = leaf_slot;
+  if (leaf_slot && p->seeds_in && hook_is("DPF_HIP_CHECK_SLOTS", '1')) {
+    HIP_TRY(hipStreamSynchronize(s));
+    return check_slot_table(p->num_starts, p->expand_levels, p->parent, leaf_slot, leaf_stride);
+  }
+  return kOk;
+}
+
+// The lean kernels' arguments (dpf_batch_hh.hip) for a launch that walks no
+// level and expands two: `b` bytes per IntModN<uint32_t> leaf.
+HHLevelArgs hh_args(const BatchLevelParams& p, const dpf_value_desc* desc, int b,
+                    const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+                    const dpf_aes_key* key_value) {
+  HHLevelArgs a;
+  memset(&a, 0, sizeof(a));
+  a.num_keys = p.num_keys;
+  a.num_starts = p.num_starts;
+  a.cw_level = p.cw_first;
+  a.cw_stride = p.cw_stride;
+  a.seeds_in = p.seeds_in;
+  a.ctrl_in = p.ctrl_in;
+  a.in_stride = p.in_stride;
+  a.parent = p.parent;
+  a.save = p.save_after == 0 && p.seeds_out;
+  a.save_index = p.save_index;
+  a.seeds_out = p.seeds_out;
+  a.ctrl_out = p.ctrl_out;
+  a.out_stride = p.out_stride;
+  a.cw_seed = p.cw_seed;
+  a.cw_left = p.cw_left;
+  a.cw_right = p.cw_right;
+  a.vcw = p.vcw;
+  a.vcw_stride = p.vcw_stride;
+  a.party = p.party;
+  a.wide = p.wide;
+  a.leaf_seeds = p.leaf_seeds;
+  a.leaf_stride = p.leaf_stride;
+  a.leaf_slot = p.leaf_slot;
+  a.nl = p.nl;
+  a.b = b;
+  a.index_major = p.index_major;
+  for (int k = 0; k < p.nl; ++k) a.mod[k] = (uint32_t)desc->mod_low[k];
+  a.key_left = key_left;
+  a.key_right = key_right;
+  a.key_value = key_value;
+  return a;
+}
+
+// Picks the kernel by value type and shape and launches it.  *sum_words: the
+// uint64 words per summed element the kernel left in the workspace.
+int dispatch_batch(const BatchLevelParams& p, const dpf_value_desc* desc, int sum,
+                   const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+                   const dpf_aes_key* key_value, hipStream_t s, int* sum_words) {
+  int b = 0;
+  // The steady state of heavy hitters (start seeds from the expansion cache
+  // or a gather, no walk, two expanded levels, IntModN<uint32_t> sums): the
+  // lean kernel of dpf_batch_hh.hip.  DPF_BATCH_NO_LEAN=1 keeps the general
+  // kernel (A/B and test hook).
+  const bool no_lean = hook_is("DPF_BATCH_NO_LEAN", '1');
+  if (sum && !no_lean && p.walk_levels == 0 && p.expand_levels == 2 && p.seeds_in && p.epl == 1 &&
+      mod32_eligible(desc, &b) && p.nl <= 2 && (p.nl == 1 || b == 2)) {
+    const HHLevelArgs a = hh_args(p, desc, b, key_left, key_right, key_value);
+    const int st = launch_hh_level(a, s);
+    if (a.index_major) *sum_words = 1;   // hh_keys_kernel sums into one uint64 per element
+    g_last_batch_kernel = a.index_major ? "hh_keys" : "hh_level";
+    return st;
+  }
+  if (fast_int(desc)) {
+    g_last_batch_kernel = "batch_level/fast";
+    const int xm = desc->kind[0] == DPF_LEAF_XOR;
+    return sum ? launch_batch_fast<true>(p, desc->bits[0], xm, s)
+               : launch_batch_fast<false>(p, desc->bits[0], xm, s);
+  }
+  if (mod32_eligible(desc, &b)) {
+    // Leaf pairs hash their four blocks as one ILP4 group (r05: +0.8% over
+    // two ILP2 pairs on heavy hitters); tuples of <= 2 leaves use 2-wide
+    // accumulators (117 instead of 128 VGPRs).
+    const int st = p.nl <= 2 ? launch_mod32<2, true>(p, desc, b, sum, s)
+                             : launch_mod32<4, true>(p, desc, b, sum, s);
+    g_last_batch_kernel = "batch_level/mod32";
+    return st;
+  }
+  g_last_batch_kernel = "batch_level/generic";
+  GenericV v;
+  memset(&v, 0, sizeof(v));
+  v.g.d = *desc;
+  v.g.elements_per_leaf = p.epl;
+  v.g.esz = p.esz;
+  return launch_batch<GenericV, 3, false>(p, v, s);
+}
 }  // namespace
 
 int dpf_hip_eval_prefix_batch_layout(
@@ -853,46 +1005,22 @@ int dpf_hip_eval_prefix_batch_layout(
     const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
     dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
     void* stream) {
-  int st = validate_desc(desc);
-  if (st) return st;
-  const int max_e = dpf_hip_prefix_batch_max_expand(desc, sum);
-  if (max_e < 0)
-    return fail(kUnimplemented, "no on-device key sum for this value type (use store mode)");
-  if (num_keys < 0 || num_starts < 0 || num_starts > INT32_MAX || walk_levels < 0 ||
-      expand_levels < 0 || expand_levels > max_e || save_after < -1 || save_after > walk_levels ||
-      cw_first < 0 || cw_first + walk_levels + expand_levels > cw_stride ||
-      walk_levels > 128 || cw_stride > 4096)
-    return fail(kInvalidArgument, "level arguments out of range");
-  if (elements_per_leaf < 1 || elements_per_leaf > desc->elements_per_block)
-    return fail(kInvalidArgument, "elements_per_leaf must be in [1, elements_per_block]");
+  if (int st = check_batch_levels(desc, sum, num_keys, num_starts, walk_levels, save_after,
+                                  expand_levels, cw_first, cw_stride, elements_per_leaf))
+    return st;
   hipStream_t s = (hipStream_t)stream;
   const int64_t slots = (num_starts << expand_levels) * elements_per_leaf;
   const int nl = desc->num_leaves;
-  int sum_words = 3;   // hh_keys_kernel (index-major) sums into one uint64 per element
+  int sum_words = 3;   // the 192-bit [slot][leaf][3] accumulators
   if (sum) {
     if (!workspace || !out) return fail(kInvalidArgument, "NULL pointer");
     HIP_TRY(hipMemsetAsync(workspace, 0, (size_t)slots * nl * 3 * sizeof(uint64_t), s));
   }
   if (num_keys > 0 && num_starts > 0) {
-    if (!party || !value_correction || !key_left || !key_right || !key_value ||
-        (!sum && !out) || (!seeds_in && !key_seed) || (seeds_in && !parent) ||
-        (walk_levels > 0 && !path) || (save_after >= 0 && (!seeds_out || !control_out)) ||
-        (walk_levels + expand_levels > 0 && (!cw_seed || !cw_left || !cw_right)))
-      return fail(kInvalidArgument, "NULL pointer");
     BatchLevelParams p;
     memset(&p, 0, sizeof(p));
     p.num_keys = num_keys;
     p.num_starts = num_starts;
-    p.waves_per_chunk = (num_starts + 63) / 64;
-    // ~4 wave tasks per wave slot, 16 when they are taken dynamically.
-    const int64_t want_waves =
-        (int64_t)num_cus() * (kBlock / 64) * (hook_is("DPF_BATCH_DYNAMIC", '0') ? 4 : 16);
-    int64_t chunks = (want_waves + p.waves_per_chunk - 1) / p.waves_per_chunk;
-    if (chunks > num_keys) chunks = num_keys;
-    if (chunks < 1) chunks = 1;
-    p.chunk_keys = (num_keys + chunks - 1) / chunks;
-    chunks = (num_keys + p.chunk_keys - 1) / p.chunk_keys;
-    p.num_threads = chunks * p.waves_per_chunk * 64;
     p.walk_levels = walk_levels;
     p.save_after = save_after;
     p.expand_levels = expand_levels;
@@ -922,94 +1050,16 @@ int dpf_hip_eval_prefix_batch_layout(
     p.out = (char*)out;
     p.wide = reinterpret_cast<unsigned long long*>(workspace);
     p.index_major = index_major ? 1 : 0;
-    if (leaf_cache) {
-      if (leaf_stride < (num_starts << expand_levels))
-        return fail(kInvalidArgument, "expansion cache too small");
-      // In place (leaf_cache == seeds_in) only through a slot table, whose
-      // contract (include/dpf_hip.h) keeps every entry's read before its write.
-      const bool in_place =
-          leaf_slot && leaf_cache == seeds_in && in_stride == leaf_stride && !control_in;
-      if (seeds_in && !in_place &&
-          (const void*)leaf_cache < (const void*)(seeds_in + num_keys * in_stride) &&
-          (const void*)seeds_in < (const void*)(leaf_cache + num_keys * leaf_stride))
-        return fail(kInvalidArgument, "expansion cache overlaps the start seeds");
-      p.leaf_seeds = leaf_cache;
-      p.leaf_stride = leaf_stride;
-      p.leaf_slot = leaf_slot;
-      if (leaf_slot && seeds_in && hook_is("DPF_HIP_CHECK_SLOTS", '1')) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (int e = check_slot_table(num_starts, expand_levels, parent, leaf_slot, leaf_stride))
-          return e;
-      }
-    }
+    if (int st = check_batch_pointers(p, sum, key_left, key_right, key_value)) return st;
+    plan_key_chunks(&p);
+    if (leaf_cache)
+      if (int st = attach_leaf_cache(&p, leaf_cache, leaf_stride, leaf_slot, s)) return st;
     p.rkl = expand_key(key_left);
     p.rkr = expand_key(key_right);
     p.rkv = expand_key(key_value);
     p.rkd = xor_keys(p.rkl, p.rkr);
-    int b = 0;
-    // The steady state of heavy hitters (start seeds from the expansion cache
-    // or a gather, no walk, two expanded levels, IntModN<uint32_t> sums): the
-    // lean kernel of dpf_batch_hh.hip.  DPF_BATCH_NO_LEAN=1 keeps the general
-    // kernel (A/B and test hook).
-    const bool no_lean = hook_is("DPF_BATCH_NO_LEAN", '1');
-    if (sum && !no_lean && walk_levels == 0 && expand_levels == 2 && seeds_in &&
-        elements_per_leaf == 1 && mod32_eligible(desc, &b) && nl <= 2 && (nl == 1 || b == 2)) {
-      HHLevelArgs a;
-      memset(&a, 0, sizeof(a));
-      a.num_keys = num_keys;
-      a.num_starts = num_starts;
-      a.cw_level = cw_first;
-      a.cw_stride = cw_stride;
-      a.seeds_in = seeds_in;
-      a.ctrl_in = control_in;
-      a.in_stride = in_stride;
-      a.parent = parent;
-      a.save = save_after == 0 && seeds_out;
-      a.save_index = save_index;
-      a.seeds_out = seeds_out;
-      a.ctrl_out = control_out;
-      a.out_stride = out_stride;
-      a.cw_seed = cw_seed;
-      a.cw_left = cw_left;
-      a.cw_right = cw_right;
-      a.vcw = value_correction;
-      a.vcw_stride = p.vcw_stride;
-      a.party = party;
-      a.wide = p.wide;
-      a.leaf_seeds = p.leaf_seeds;
-      a.leaf_stride = p.leaf_stride;
-      a.leaf_slot = p.leaf_slot;
-      a.nl = nl;
-      a.b = b;
-      a.index_major = p.index_major;
-      for (int k = 0; k < nl; ++k) a.mod[k] = (uint32_t)desc->mod_low[k];
-      a.key_left = key_left;
-      a.key_right = key_right;
-      a.key_value = key_value;
-      st = launch_hh_level(a, s);
-      if (a.index_major) sum_words = 1;
-      g_last_batch_kernel = a.index_major ? "hh_keys" : "hh_level";
-    } else if (fast_int(desc)) {
-      g_last_batch_kernel = "batch_level/fast";
-      const int xm = desc->kind[0] == DPF_LEAF_XOR;
-      st = sum ? launch_batch_fast<true>(p, desc->bits[0], xm, s)
-               : launch_batch_fast<false>(p, desc->bits[0], xm, s);
-    } else if (mod32_eligible(desc, &b)) {
-      // Leaf pairs hash their four blocks as one ILP4 group (r05: +0.8% over
-      // two ILP2 pairs on heavy hitters); tuples of <= 2 leaves use 2-wide
-      // accumulators (117 instead of 128 VGPRs).
-      st = nl <= 2 ? launch_mod32<2, true>(p, desc, b, sum, s) : launch_mod32<4, true>(p, desc, b, sum, s);
-      g_last_batch_kernel = "batch_level/mod32";
-    } else {
-      g_last_batch_kernel = "batch_level/generic";
-      GenericV v;
-      memset(&v, 0, sizeof(v));
-      v.g.d = *desc;
-      v.g.elements_per_leaf = elements_per_leaf;
-      v.g.esz = p.esz;
-      st = launch_batch<GenericV, 3, false>(p, v, s);
-    }
-    if (st) return st;
+    if (int st = dispatch_batch(p, desc, sum, key_left, key_right, key_value, s, &sum_words))
+      return st;
   }
   if (sum && slots > 0) {
     int64_t g = (slots + 255) / 256;

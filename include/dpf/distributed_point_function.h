@@ -386,10 +386,19 @@ class DistributedPointFunction {
   // Sizes `b` for n keys, and fills row k from `key` (validated).
   void ResizeKeyBatch(int64_t n, KeyBatch* b) const;
   Status FillKeyBatchRow(const DpfKey& key, int64_t k, KeyBatch* b) const;
-  // Shared core of the two batched EvaluateUntil entry points.
+  // Shared core of the two batched EvaluateUntil entry points, and its steps
+  // (csrc/host/batch_context.cc): the argument checks, the host-side plan of
+  // the call, and the kernel launch with the output gather.
   StatusOr<int64_t> EvaluateUntilBatchCore(int hierarchy_level, Span<const uint128> prefixes,
                                            DeviceBatchContext& ctx, bool sum, void* device_out,
                                            int64_t capacity_bytes, void* stream) const;
+  struct BatchCall;
+  Status CheckUntilBatchArgs(int hierarchy_level, Span<const uint128> prefixes,
+                             const DeviceBatchContext& ctx) const;
+  Status PlanBatchCall(int hierarchy_level, int64_t num_prefixes, const DeviceBatchContext& ctx,
+                       bool sum, BatchCall* call) const;
+  Status LaunchBatchCall(int hierarchy_level, BatchCall& call, DeviceBatchContext& ctx, bool sum,
+                         void* device_out, void* stream) const;
 
   std::unique_ptr<dpf_internal::ProtoValidator> validator_;
   std::vector<int> blocks_needed_;

@@ -156,6 +156,54 @@ class DeviceBatchContext {
   // Free and total device memory as this context sees it (DPF_BATCH_ALLOC_LIMIT
   // replaces the device's figures with the limit, as a test hook).
   void MemInfo(size_t* free_bytes, size_t* total_bytes) const;
+  // True when `bytes` more fit with total / reserve_div of the device left
+  // over for everything else (the caller's buffers, a second context): a
+  // quarter of it for the spare, an eighth for the cache.
+  bool Fits(size_t bytes, size_t reserve_div) const;
+
+  // Where one call's leaves go, and what the call does to the cache it reads.
+  struct CacheTarget {
+    void* leaf_seeds = nullptr;  // buffer the kernel writes its leaves to (null: none)
+    int64_t stride = 0;          // its physical row stride
+    bool swap = false;           // leaf_seeds is the spare: swapped in at commit
+    bool gather = false;         // start seeds gathered first, cache rewritten in place
+    bool permute = false;        // cache rewritten in place through a slot table
+    bool cache_in_use = false;   // this call's gather or kernel still reads the cache
+  };
+  // Decides where the leaves of a call with `leaf_stride` leaves per key go
+  // (`writes_cache`: the call is to leave a cache; `cached`: it reads the
+  // current one, at `start_slot`).  Not read: the current cache is rewritten
+  // (or regrown).  Read: the spare if one fits, else in place through a slot
+  // table (built into *leaf_slot), else in place after a gather; `gather`
+  // leaves leaf_seeds null until GrowCache after the gather.  Invalidates the
+  // cache (leaf_level_ = -1) before a rewrite and bumps the event counters.
+  StatusOr<CacheTarget> ChooseCacheTarget(bool writes_cache, bool cached, int64_t leaf_stride,
+                                          const std::vector<int64_t>& start_slot, int64_t T, int s,
+                                          int E, std::vector<int32_t>* leaf_slot, void* stream);
+  // Makes leaf_seeds_ hold `bytes`, once the work on `stream` that still
+  // reads it is done; without room the cache is refused (leaf_seeds_ null).
+  Status GrowCache(size_t bytes, void* stream);
+  // Ensure() for a per-call buffer; when device memory runs out, the
+  // expansion cache gives way -- the spare, then, unless this call still
+  // reads it, the cache itself -- and the allocation is retried.
+  Status EnsureEvicting(void** p, size_t* cap, size_t bytes, CacheTarget* target, void* stream);
+  // The table image StageTables made room for (`bytes` of it), into parent_.
+  Status SendTables(size_t bytes, CacheTarget* target, void* stream);
+  // target->gather: the start seeds at `start_slot` (T of them per key) are
+  // copied out of the cache into next_seeds_ / next_ctrl_ before the kernel
+  // rewrites it; the cache is then regrown for `leaf_stride` leaves per key.
+  Status GatherStartSeeds(const std::vector<int64_t>& start_slot, int64_t T, int64_t leaf_stride,
+                          CacheTarget* target, void* stream);
+  // target->permute: the slot table of the in-place rewrite, into leaf_slot_.
+  Status SendSlotTable(const std::vector<int32_t>& leaf_slot, CacheTarget* target, void* stream);
+  // After a call's last launch: the cache the call wrote becomes current.
+  void CommitCache(const CacheTarget& target, int hierarchy_level, int de, bool last_level,
+                   const std::vector<int32_t>& leaf_slot);
+  // The context update (cc:435-451, 494-496): `tree_indices` become the stored
+  // prefixes (with `update`: the seeds the kernel saved are swapped in), and
+  // the storage not kept is recycled for the next call's dedup.
+  void CommitPartials(int hierarchy_level, int prev_level, bool has_prefixes, bool update,
+                      bool ascending, std::vector<uint128>* tree_indices);
 
   const DeviceKeyBatch* keys_;
   int previous_hierarchy_level_ = -1;
@@ -204,14 +252,10 @@ class DeviceBatchContext {
   // Per-call scratch: start-node tables (parent_: the device copy of the
   // whole table image), sums workspace, staging output.
   void* parent_ = nullptr;
-  void* path_ = nullptr;
-  void* save_ = nullptr;
-  void* offsets_ = nullptr;
   void* workspace_ = nullptr;
   void* stage_ = nullptr;
   void* stage2_ = nullptr;
-  size_t parent_cap_ = 0, path_cap_ = 0, save_cap_ = 0, offsets_cap_ = 0, workspace_cap_ = 0,
-         stage_cap_ = 0, stage2_cap_ = 0;
+  size_t parent_cap_ = 0, workspace_cap_ = 0, stage_cap_ = 0, stage2_cap_ = 0;
 };
 
 }  // namespace distributed_point_functions

@@ -3,11 +3,16 @@ plan_chunks in dpf_expand_plan.hip): a pure function of the launch's shape, the 
 count and the DPF_OCTET_* hooks, so it is checked here without a GPU.
 """
 import itertools
+import json
+import os
+import subprocess
+import sys
 
 import pytest
 
 from distributed_point_functions_amd import hip_abi as H
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOOKS = ("DPF_OCTET_DYNAMIC", "DPF_OCTET_TAPER", "DPF_OCTET_GLOBAL", "DPF_OCTET_TAPER_AT",
          "DPF_OCTET_WALK")
 WAVES_PER_WG = 16
@@ -188,7 +193,16 @@ def test_dynamic_off_is_static(monkeypatch):
 
 
 def test_last_expand_schedule_before_any_launch():
-    assert H.last_expand_schedule() == {"shift": 0, "global": False, "counters": 0, "phases": []}
+    """Process-wide state, so a fresh process is asked: it loads the library,
+    launches nothing and prints last_expand_schedule()."""
+    code = ("import json, sys; sys.path.insert(0, sys.argv[1]); "
+            "from distributed_point_functions_amd import hip_abi as H; "
+            "print(json.dumps(H.last_expand_schedule()))")
+    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == {
+        "shift": 0, "global": False, "counters": 0, "phases": []}
 
 
 def test_rejects_bad_shapes():
