@@ -105,12 +105,6 @@ __device__ __forceinline__ int64_t tab_at(const BatchLevelParams& p, int64_t k, 
   return p.index_major ? j * p.num_keys + k : k * stride + j;
 }
 
-__device__ __forceinline__ uint4 cw_block(const dpf_block* p) {
-  const dpf_block c = *p;
-  return make_uint4((uint32_t)c.low, (uint32_t)(c.low >> 32), (uint32_t)c.high,
-                    (uint32_t)(c.high >> 32));
-}
-
 // Two path steps of two different keys (own correction words), interleaved.
 __device__ __forceinline__ void path_step2k(const LdsLookup& lk, KeyRef rkl,
                                             KeyRef rkd, Block4& s0, uint32_t& t0,
@@ -240,13 +234,6 @@ struct Mod32V {
     for (int i = 0; i < NLMAX; ++i) c[i] = i < nl ? (uint32_t)v[i].low : 0u;
   }
   __device__ __forceinline__ void convert(const uint32_t* w, uint32_t t, Val& out) const {
-#if defined(DPF_PROBE_NO_CONVERT)
-    // Probe build only (tools/): the sampling's divisions left out, so a run
-    // measures what the rest of the kernel costs.  Outputs are NOT the DPF's.
-#pragma unroll
-    for (int i = 0; i < NLMAX; ++i) out.x[i] = (w[i] + (t ? c[i] : 0u)) ^ (uint32_t)party;
-    return;
-#endif
     uint32_t blk[4] = {w[0], w[1], w[2], w[3]};
 #pragma unroll
     for (int i = 0; i < NLMAX; ++i) {
@@ -391,7 +378,7 @@ __device__ __forceinline__ void expand_and_convert(const LdsLookup& lk, const Ba
 #pragma unroll
   for (int d = 0; d < MAXE; ++d) {
     if (d < E) {
-      const uint4 cs = cw_block(cws + d);
+      const uint4 cs = cw_u4(cws[d]);
       const uint32_t cc = (uint32_t)(cl[d] & 1) | ((uint32_t)(cr[d] & 1) << 1);
       if (d == 0) {
         Block4 c0, c1;
@@ -534,7 +521,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void batch_level_kernel(
         const uint32_t bit = path_bit(path, W - 1 - j);
         const uint32_t cca = (uint32_t)(la[j] & 1) | ((uint32_t)(ra[j] & 1) << 1);
         const uint32_t ccb = (uint32_t)(lb[j] & 1) | ((uint32_t)(rb[j] & 1) << 1);
-        path_step2k(lk, lk.ks.l, lk.ks.d, sa, ta, cw_block(ca + j), cca, sb, tb, cw_block(cb + j), ccb,
+        path_step2k(lk, lk.ks.l, lk.ks.d, sa, ta, cw_u4(ca[j]), cca, sb, tb, cw_u4(cb[j]), ccb,
                     bit);
       }
       // 2.-4. expansion, conversion and sum/store, one key at a time.

@@ -21,41 +21,18 @@
 
 using namespace dpf_rt;
 
-// Waves per SIMD: 4 = 1024-thread workgroups at <= 128 VGPRs (the other
-// kernels' shape); 3 = 768 threads at <= 168 VGPRs (more lookups in flight
-// per wave, fewer waves).
-#ifndef DPF_HH_WAVES
-#define DPF_HH_WAVES 4
-#endif
-// 1: the MMO feed-forward sigma(x) is recomputed from the leaf seed after the
-// encryption instead of being held through it (8 fewer live VGPRs per leaf pair).
-#ifndef DPF_HH_RESIGMA
-#define DPF_HH_RESIGMA 1
-#endif
-
-// 1: the second leaf pair waits in LDS (32 B per thread beside the 128 KiB of
-// tables) while the first pair is hashed, instead of in 10 VGPRs.
-// DPF_HH_PREFETCH=1: the next key's start seed is loaded before this key's
-// value hashes (the start seeds come from scattered rows of the expansion
-// cache since the slot-table rewrite).  Measured slower (128 VGPRs; 2^20
-// clients 20.68 vs 20.52 s per pass, 2^18 5.41 vs 5.33 s, profiles/r15_ab.txt
-// part 17): the other 15 waves of the CU already hide the load.  Off.
-#ifndef DPF_HH_PREFETCH
-#define DPF_HH_PREFETCH 0
-#endif
-#ifndef DPF_HH_STASH
-#define DPF_HH_STASH 1
-#endif
-
 namespace {
 
-constexpr int kHHBlock = 256 * DPF_HH_WAVES;
+// Both kernels run 4 waves per SIMD: 1024-thread workgroups at <= 128 VGPRs
+// (the other kernels' shape).
+constexpr int kHHWaves = 4;
+constexpr int kHHBlock = 256 * kHHWaves;
 
+// The second leaf pair waits in LDS (32 B per thread beside the 128 KiB of
+// tables) while the first pair is hashed, instead of in 10 VGPRs.
 struct HHLds {
   uint32_t tab[kTabWords];
-#if DPF_HH_STASH
   uint4 stash[2][kHHBlock];  // [leaf 2 / 3][thread]: seed | control bit
-#endif
 };
 
 struct HHParams {
@@ -94,23 +71,8 @@ struct HHParams {
 
 // value = sampled IntModN elements of one leaf (value_type_helpers.h:286-311):
 // r0 = block mod N0; r1 = ((block / N0) << 32 | next 4 bytes) mod N1.
-__device__ __forceinline__ void sample2(const HHParams& p, const Div32 (&div)[2], const Block4& h0,
+__device__ __forceinline__ void sample2(int nl, const Div32& d0, const Div32& d1, const Block4& h0,
                                         uint32_t w4, uint32_t out[2]) {
-  const uint32_t blk[4] = {h0.w0, h0.w1, h0.w2, h0.w3};
-  uint32_t q[3];
-  out[0] = divmod128(blk, div[0], q);
-  if (p.nl > 1) {
-    const uint32_t nb[4] = {w4, q[0], q[1], q[2]};
-    uint32_t q2[3];
-    out[1] = divmod128(nb, div[1], q2);
-  } else {
-    out[1] = 0;
-  }
-}
-
-// sample2 with the divisors passed directly (hh_keys_kernel).
-__device__ __forceinline__ void sample2_nl(int nl, const Div32& d0, const Div32& d1,
-                                           const Block4& h0, uint32_t w4, uint32_t out[2]) {
   const uint32_t blk[4] = {h0.w0, h0.w1, h0.w2, h0.w3};
   uint32_t q[3];
   out[0] = divmod128(blk, d0, q);
@@ -130,6 +92,9 @@ __device__ __forceinline__ void sample2_nl(int nl, const Div32& d0, const Div32&
 // LDS lookups in flight (party / leaf_seeds / leaf_stride were reloaded 10x
 // per key, r15 ISA).  Measured slower (2^20 clients 20.57 vs 20.45 s per
 // pass, 2^18 5.39 / 5.37 vs 5.32 / 5.33 s; profiles/r15_ab.txt part 18): off.
+// The switch stays in the source because dropping the copies is not neutral:
+// with plain locals in their place one s_and_b64 of hh_level_kernel gets its
+// two sources exchanged (profiles/CHANGELOG.md r20).
 #ifndef DPF_HH_PIN_DIV
 #define DPF_HH_PIN_DIV 0
 #endif
@@ -162,10 +127,11 @@ __device__ __forceinline__ uint32_t mod_add(uint32_t a, uint32_t b, uint32_t n) 
 }
 
 // MMO hashes of two leaves' blocks x0, x0 + 1, x1, x1 + 1 (cc:500-524), ILP4.
+// The feed-forward sigma(x) is recomputed from the leaf seed after the
+// encryption instead of being held through it (8 fewer live VGPRs per leaf pair).
 __device__ __forceinline__ void hash_leaf_pair(const LdsLookup& lk, KeyRef rkv, Block4 x0,
                                                Block4 x1, Block4 h[4]) {
   const UniformRK rk[4] = {UniformRK{rkv}, UniformRK{rkv}, UniformRK{rkv}, UniformRK{rkv}};
-#if DPF_HH_RESIGMA
   h[0] = dpf_aes::sigma(x0);
   h[1] = dpf_aes::sigma(add_small(x0, 1u));
   h[2] = dpf_aes::sigma(x1);
@@ -176,16 +142,9 @@ __device__ __forceinline__ void hash_leaf_pair(const LdsLookup& lk, KeyRef rkv, 
 #pragma unroll
   for (int i = 0; i < 4; ++i)
     h[i] = Block4{h[i].w0 ^ s[i].w0, h[i].w1 ^ s[i].w1, h[i].w2 ^ s[i].w2, h[i].w3 ^ s[i].w3};
-#else
-  h[0] = x0;
-  h[1] = add_small(x0, 1u);
-  h[2] = x1;
-  h[3] = add_small(x1, 1u);
-  dpf_aes::mmo_hashN<4>(h, lk, rk);
-#endif
 }
 
-__global__ __launch_bounds__(kHHBlock) __attribute__((amdgpu_waves_per_eu(DPF_HH_WAVES, DPF_HH_WAVES)))
+__global__ __launch_bounds__(kHHBlock) __attribute__((amdgpu_waves_per_eu(kHHWaves, kHHWaves)))
 void hh_level_kernel(HHParams p) {
   __shared__ HHLds lds;
   fill_tables(lds.tab);
@@ -237,24 +196,11 @@ void hh_level_kernel(HHParams p) {
     int4 sl = make_int4((int)(u << 2), (int)(u << 2) + 1, (int)(u << 2) + 2, (int)(u << 2) + 3);
     if (p.leaf_slot && leaf_seeds && valid)
       sl = *reinterpret_cast<const int4*>(p.leaf_slot + (u << 2));
-#if DPF_HH_PREFETCH
-    Block4 s_next{};
-    uint32_t c_next = 0;
-    if (k_begin < k_end) {
-      s_next = load_block(p.seeds_in + k_begin * p.in_stride + par);
-      if (p.ctrl_in) c_next = p.ctrl_in[k_begin * p.in_stride + par];
-    }
-#endif
     for (int64_t k = k_begin; k < k_end; ++k) {
-#if DPF_HH_PREFETCH
-      Block4 s = s_next;
-      const uint32_t c_in = c_next;
-#else
       // Padding lanes (u clamped to U - 1) read nothing: that node's own
       // lane may be rewriting the slot in place.
       Block4 s = valid ? load_block(p.seeds_in + k * p.in_stride + par) : Block4{0, 0, 0, 0};
       const uint32_t c_in = p.ctrl_in && valid ? p.ctrl_in[k * p.in_stride + par] : 0u;
-#endif
       uint32_t t;
       if (p.ctrl_in) {
         t = c_in & 1u;
@@ -269,15 +215,12 @@ void hh_level_kernel(HHParams p) {
       // Two tree levels (cc:304-347): the node's children (ILP2), then both
       // children's children (ILP4); leaf order 0..3 = LL, LR, RL, RR.
       const int64_t cwi = k * p.cw_stride + p.cw_level;
-      const uint4 cs0 = make_uint4((uint32_t)p.cw_seed[cwi].low, (uint32_t)(p.cw_seed[cwi].low >> 32),
-                                   (uint32_t)p.cw_seed[cwi].high, (uint32_t)(p.cw_seed[cwi].high >> 32));
+      const uint4 cs0 = cw_u4(p.cw_seed[cwi]);
       const uint32_t cc0 = (uint32_t)(p.cw_left[cwi] & 1) | ((uint32_t)(p.cw_right[cwi] & 1) << 1);
       Block4 c0, c1;
       uint32_t t0, t1;
       children_step(lk, lk.ks.l, lk.ks.r, s, t, cs0, cc0, c0, t0, c1, t1);
-      const uint4 cs1 = make_uint4(
-          (uint32_t)p.cw_seed[cwi + 1].low, (uint32_t)(p.cw_seed[cwi + 1].low >> 32),
-          (uint32_t)p.cw_seed[cwi + 1].high, (uint32_t)(p.cw_seed[cwi + 1].high >> 32));
+      const uint4 cs1 = cw_u4(p.cw_seed[cwi + 1]);
       const uint32_t cc1 =
           (uint32_t)(p.cw_left[cwi + 1] & 1) | ((uint32_t)(p.cw_right[cwi + 1] & 1) << 1);
       Block4 L[4];
@@ -302,22 +245,10 @@ void hh_level_kernel(HHParams p) {
       const uint32_t corr[2] = {(uint32_t)vc[0].low, p.nl > 1 ? (uint32_t)vc[1].low : 0u};
       const UniformRK rk[4] = {UniformRK{lk.ks.v}, UniformRK{lk.ks.v}, UniformRK{lk.ks.v},
                                UniformRK{lk.ks.v}};
-#if DPF_HH_PREFETCH
-      {
-        // In-place rewrites are safe: the next key's row is not written until
-        // that key's own iteration (leaf stores go to row k only).
-        const int64_t kn = k + 1 < k_end ? k + 1 : k;
-        s_next = load_block(p.seeds_in + kn * p.in_stride + par);
-        if (p.ctrl_in) c_next = p.ctrl_in[kn * p.in_stride + par];
-      }
-#endif
-#if DPF_HH_STASH
       lds.stash[0][threadIdx.x] = make_uint4(L[2].w0 | tl[2], L[2].w1, L[2].w2, L[2].w3);
       lds.stash[1][threadIdx.x] = make_uint4(L[3].w0 | tl[3], L[3].w1, L[3].w2, L[3].w3);
-#endif
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {
-#if DPF_HH_STASH
         if (pr == 1) {
           // Same thread wrote these: no barrier needed.
           const uint4 a = lds.stash[0][threadIdx.x], c = lds.stash[1][threadIdx.x];
@@ -326,7 +257,6 @@ void hh_level_kernel(HHParams p) {
           L[2] = Block4{a.x & ~1u, a.y, a.z, a.w};
           L[3] = Block4{c.x & ~1u, c.y, c.z, c.w};
         }
-#endif
         Block4 h[4];
         if (p.b == 2) {
           hash_leaf_pair(lk, lk.ks.v, L[2 * pr], L[2 * pr + 1], h);
@@ -343,7 +273,7 @@ void hh_level_kernel(HHParams p) {
         for (int j = 0; j < 2; ++j) {
           const int leaf = 2 * pr + j;
           uint32_t v[2];
-          sample2(p, div, h[2 * j], h[2 * j + 1].w0, v);
+          sample2(p.nl, div[0], div[1], h[2 * j], h[2 * j + 1].w0, v);
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             if (e < p.nl) {
@@ -412,7 +342,7 @@ struct HHKeysParams {
   const dpf_block* vcw;
   int vcw_stride;
   const uint8_t* party;
-  const uint4* key_tab;        // DPF_HH_KEYS_MODE 2: [3][K], hh_key_table_kernel
+  const uint4* key_tab;        // [3][K], hh_key_table_kernel
   unsigned long long* sums;    // [(u << 2 | leaf) * nl + e]
   dpf_block* leaf_seeds;       // [slot][K]; NULL: no expansion cache written
   const int32_t* leaf_slot;    // NULL: leaf i of start node u at slot (u << 2) + i
@@ -450,66 +380,39 @@ __device__ __forceinline__ uint32_t wave_sum8_mod(uint32_t v[8], uint32_t n0, ui
   return x;
 }
 
-// Where hh_keys_kernel gets each key's two levels of correction words, its
-// value correction and its party (DPF_HH_KEYS_MODE):
-//   2 (default): a per-call key table built by hh_key_table_kernel, [3][K]
-//     uint4 (cs0, cs1, {cc bits | party << 4, corr0, corr1}), re-read for
-//     every start node next to its use as three coalesced 1 KiB loads per
-//     wave (L2 hits), at 4 waves per SIMD;
-//   1: loaded ONCE per wave into 11 VGPRs (135 VGPRs: 3 waves per SIMD):
-//     22.8 vs 20.3 s per 2^20-client pass (profiles/r16/hh_ab.txt);
-//   0: re-read for every start node straight from the key batch's
-//     [key][level] rows (scattered 16-byte reads, ~60 TB of fetches per
-//     2^20 pass), 4 waves per SIMD.
-#ifndef DPF_HH_KEYS_MODE
-#define DPF_HH_KEYS_MODE 2
-#endif
-#define DPF_HH_KEYS_HOIST (DPF_HH_KEYS_MODE == 1)
-#ifndef DPF_HH_KEYS_WAVES
-#define DPF_HH_KEYS_WAVES (DPF_HH_KEYS_HOIST ? 3 : 4)
-#endif
-constexpr int kHHKeysBlock = 256 * DPF_HH_KEYS_WAVES;
+// hh_keys_kernel gets each key's two levels of correction words, its value
+// correction and its party from a per-call key table built by
+// hh_key_table_kernel, [3][K] uint4 (cs0, cs1, {cc bits | party << 4, corr0,
+// corr1}), re-read for every start node next to its use as three coalesced
+// 1 KiB loads per wave (L2 hits), at 4 waves per SIMD.  Loading them once per
+// wave into 11 VGPRs (135 VGPRs: 3 waves per SIMD) measured 22.8 vs 20.3 s
+// per 2^20-client pass (profiles/r16/hh_ab.txt); re-reading them straight
+// from the key batch's [key][level] rows is scattered 16-byte reads, ~60 TB
+// of fetches per 2^20 pass.
+constexpr int kHHKeysBlock = kHHBlock;
 struct HHKeysLds {
   uint32_t tab[kTabWords];
-#if DPF_HH_STASH
   uint4 stash[2][kHHKeysBlock];  // [leaf 2 / 3][thread]: seed | control bit
-#endif
 };
 
-// DPF_HH_NT=1 (default): the streamed start seeds, cache leaves and partial
-// evaluations are non-temporal (they are not read again within the call),
-// leaving L2 to the waves' key tables: 2^20-client pass 19.03 / 19.23 /
-// 19.25 vs 19.16 / 19.37 / 19.34 s with temporal accesses, three same-box
-// pairs (profiles/r16/hh_nt_ab.txt).
-#ifndef DPF_HH_NT
-#define DPF_HH_NT 1
-#endif
+// The streamed start seeds, cache leaves and partial evaluations are
+// non-temporal (they are not read again within the call), leaving L2 to the
+// waves' key tables: 2^20-client pass 19.03 / 19.23 / 19.25 vs 19.16 / 19.37 /
+// 19.34 s with temporal accesses, three same-box pairs
+// (profiles/r16/hh_nt_ab.txt).
 __device__ __forceinline__ Block4 stream_load(const dpf_block* p) {
-#if DPF_HH_NT
   typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
   return Block4{v.x, v.y, v.z, v.w};
-#else
-  return load_block(p);
-#endif
 }
 __device__ __forceinline__ void stream_store(dpf_block* p, Block4 b) {
-#if DPF_HH_NT
   typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   const v4u v = {b.w0, b.w1, b.w2, b.w3};
   __builtin_nontemporal_store(v, reinterpret_cast<v4u*>(p));
-#else
-  store_block(p, b);
-#endif
-}
-
-__device__ __forceinline__ uint4 cw_u4(const dpf_block& c) {
-  return make_uint4((uint32_t)c.low, (uint32_t)(c.low >> 32), (uint32_t)c.high,
-                    (uint32_t)(c.high >> 32));
 }
 
 __global__ __launch_bounds__(kHHKeysBlock)
-__attribute__((amdgpu_waves_per_eu(DPF_HH_KEYS_WAVES, DPF_HH_KEYS_WAVES)))
+__attribute__((amdgpu_waves_per_eu(kHHWaves, kHHWaves)))
 void hh_keys_kernel(HHKeysParams p) {
   __shared__ HHKeysLds lds;
   fill_tables(lds.tab);
@@ -545,17 +448,6 @@ void hh_keys_kernel(HHKeysParams p) {
     const int64_t k_raw = grp * 64 + lane;
     const bool valid = k_raw < K;
     const int64_t k = valid ? k_raw : K - 1;
-    const int64_t cwi = k * p.cw_stride + p.cw_level;
-    const dpf_block* vc = p.vcw + k * p.vcw_stride;
-#if DPF_HH_KEYS_HOIST
-    // The key's two levels of correction words, value correction and party.
-    const uint4 key_cs0 = cw_u4(p.cw_seed[cwi]), key_cs1 = cw_u4(p.cw_seed[cwi + 1]);
-    const uint32_t key_cc = (uint32_t)(p.cw_left[cwi] & 1) | ((uint32_t)(p.cw_right[cwi] & 1) << 1) |
-                            ((uint32_t)(p.cw_left[cwi + 1] & 1) << 2) |
-                            ((uint32_t)(p.cw_right[cwi + 1] & 1) << 3) |
-                            ((uint32_t)(p.party[k] & 1) << 4);
-    const uint32_t key_corr0 = (uint32_t)vc[0].low, key_corr1 = nl > 1 ? (uint32_t)vc[1].low : 0u;
-#endif
     const int64_t u_begin = rng * p.u_per_range;
     const int64_t u_end = u_begin + p.u_per_range < U ? u_begin + p.u_per_range : U;
     const int64_t len = u_end - u_begin;
@@ -585,32 +477,15 @@ void hh_keys_kernel(HHKeysParams p) {
       Block4 c0, c1;
       uint32_t t0, t1;
       {
-#if DPF_HH_KEYS_HOIST
-        const uint4 cs0 = key_cs0;
-        const uint32_t cc0 = key_cc & 3u;
-#elif DPF_HH_KEYS_MODE == 2
         const uint4 cs0 = p.key_tab[k];
         const uint32_t cc0 = p.key_tab[2 * K + k].x & 3u;
-#else
-        const uint4 cs0 = cw_u4(p.cw_seed[cwi]);
-        const uint32_t cc0 = (uint32_t)(p.cw_left[cwi] & 1) | ((uint32_t)(p.cw_right[cwi] & 1) << 1);
-#endif
         children_step(lk, lk.ks.l, lk.ks.r, s, t, cs0, cc0, c0, t0, c1, t1);
       }
       Block4 L[4];
       uint32_t tl[4];
       {
-#if DPF_HH_KEYS_HOIST
-        const uint4 cs1 = key_cs1;
-        const uint32_t cc1 = (key_cc >> 2) & 3u;
-#elif DPF_HH_KEYS_MODE == 2
         const uint4 cs1 = p.key_tab[K + k];
         const uint32_t cc1 = (p.key_tab[2 * K + k].x >> 2) & 3u;
-#else
-        const uint4 cs1 = cw_u4(p.cw_seed[cwi + 1]);
-        const uint32_t cc1 =
-            (uint32_t)(p.cw_left[cwi + 1] & 1) | ((uint32_t)(p.cw_right[cwi + 1] & 1) << 1);
-#endif
         children_step_x2(lk, lk.ks.l, lk.ks.r, c0, t0, c1, t1, cs1, cc1, L, tl);
       }
       if (p.leaf_seeds && valid) {
@@ -624,10 +499,8 @@ void hh_keys_kernel(HHKeysParams p) {
           stream_store(p.leaf_seeds + slot[j] * K + k, c);
         }
       }
-#if DPF_HH_STASH
       lds.stash[0][threadIdx.x] = make_uint4(L[2].w0 | tl[2], L[2].w1, L[2].w2, L[2].w3);
       lds.stash[1][threadIdx.x] = make_uint4(L[3].w0 | tl[3], L[3].w1, L[3].w2, L[3].w3);
-#endif
       // Value hashes (cc:500-524), sampling, correction, party negation.
       uint32_t v[8];   // [leaf * 2 + element]
       // Leaves 0 and 1 are sampled before leaves 2 and 3 are hashed; the
@@ -639,7 +512,6 @@ void hh_keys_kernel(HHKeysParams p) {
                                UniformRK{lk.ks.v}};
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {
-#if DPF_HH_STASH
         if (pr == 1) {
           // Same thread wrote these: no barrier needed.
           const uint4 a = lds.stash[0][threadIdx.x], c = lds.stash[1][threadIdx.x];
@@ -647,9 +519,6 @@ void hh_keys_kernel(HHKeysParams p) {
           L[2] = Block4{a.x & ~1u, a.y, a.z, a.w};
           L[3] = Block4{c.x & ~1u, c.y, c.z, c.w};
         }
-#else
-        if (pr == 1) tb |= (tl[2] << 2) | (tl[3] << 3);
-#endif
         Block4 h[4];
         if (p.b == 2) {
           hash_leaf_pair(lk, lk.ks.v, L[2 * pr], L[2 * pr + 1], h);
@@ -663,21 +532,13 @@ void hh_keys_kernel(HHKeysParams p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int leaf = 2 * pr + j;
-          sample2_nl(nl, div0, div1, h[2 * j], h[2 * j + 1].w0, &v[leaf * 2]);
+          sample2(nl, div0, div1, h[2 * j], h[2 * j + 1].w0, &v[leaf * 2]);
         }
       }
       {
-#if DPF_HH_KEYS_HOIST
-        const uint32_t corr[2] = {key_corr0, key_corr1};
-        const bool neg = (key_cc & 16u) != 0;
-#elif DPF_HH_KEYS_MODE == 2
         const uint4 meta = p.key_tab[2 * K + k];
         const uint32_t corr[2] = {meta.y, meta.z};
         const bool neg = (meta.x & 16u) != 0;
-#else
-        const uint32_t corr[2] = {(uint32_t)vc[0].low, nl > 1 ? (uint32_t)vc[1].low : 0u};
-        const bool neg = (p.party[k] & 1u) != 0;
-#endif
 #pragma unroll
         for (int leaf = 0; leaf < 4; ++leaf) {
 #pragma unroll
@@ -698,7 +559,7 @@ void hh_keys_kernel(HHKeysParams p) {
   }
 }
 
-// The per-call key table of hh_keys_kernel (DPF_HH_KEYS_MODE 2): key k's
+// The per-call key table of hh_keys_kernel: key k's
 // correction words of levels cw_level, cw_level + 1 and its control-bit
 // corrections, value correction and party, index-major so that a wave of 64
 // keys reads each part as one 1 KiB access.
@@ -774,32 +635,28 @@ int launch_hh_keys(const HHLevelArgs& a, hipStream_t s) {
   if (grid < 1) grid = 1;
   if (p.num_waves > (int64_t)UINT32_MAX / 2) return fail(kInvalidArgument, "too many tasks");
   void* tab = nullptr;
-  if (DPF_HH_KEYS_MODE == 2) {
-    // Stream-ordered scratch (48 B per key), freed behind the kernel; the
-    // device's default pool keeps it for the next level's call.
-    static const bool pool_kept = [] {
-      int dev = 0;
-      hipMemPool_t pool;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetDefaultMemPool(&pool, dev) != hipSuccess)
-        return false;
-      uint64_t keep = UINT64_MAX;
-      return hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep) == hipSuccess;
-    }();
-    (void)pool_kept;
-    // The key table, then the dynamic task counter.
-    HIP_TRY(hipMallocAsync(&tab, (size_t)a.num_keys * 3 * sizeof(uint4) + 256, s));
-    int64_t g = (a.num_keys + 255) / 256;
-    if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(hh_key_table_kernel, dim3((unsigned)g), dim3(256), 0, s, a.num_keys,
-                       a.cw_level, a.cw_stride, a.cw_seed, a.cw_left, a.cw_right, a.vcw,
-                       a.vcw_stride, a.nl, a.party, static_cast<uint4*>(tab));
-    p.key_tab = static_cast<const uint4*>(tab);
-  } else {
-    HIP_TRY(hipMallocAsync(&tab, 256, s));
-  }
+  // Stream-ordered scratch (48 B per key), freed behind the kernel; the
+  // device's default pool keeps it for the next level's call.
+  static const bool pool_kept = [] {
+    int dev = 0;
+    hipMemPool_t pool;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetDefaultMemPool(&pool, dev) != hipSuccess)
+      return false;
+    uint64_t keep = UINT64_MAX;
+    return hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep) == hipSuccess;
+  }();
+  (void)pool_kept;
+  // The key table, then the dynamic task counter.
+  HIP_TRY(hipMallocAsync(&tab, (size_t)a.num_keys * 3 * sizeof(uint4) + 256, s));
+  int64_t g = (a.num_keys + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(hh_key_table_kernel, dim3((unsigned)g), dim3(256), 0, s, a.num_keys,
+                     a.cw_level, a.cw_stride, a.cw_seed, a.cw_left, a.cw_right, a.vcw,
+                     a.vcw_stride, a.nl, a.party, static_cast<uint4*>(tab));
+  p.key_tab = static_cast<const uint4*>(tab);
   if (dynamic) {
     p.task_counter = reinterpret_cast<unsigned int*>(
-        static_cast<char*>(tab) + (DPF_HH_KEYS_MODE == 2 ? (size_t)a.num_keys * 3 * sizeof(uint4) : 0));
+        static_cast<char*>(tab) + (size_t)a.num_keys * 3 * sizeof(uint4));
     HIP_TRY(hipMemsetAsync(p.task_counter, 0, sizeof(unsigned int), s));
   }
   hipLaunchKernelGGL(hh_keys_kernel, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s, p);

@@ -120,9 +120,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_eval_kernel(
         }
       }
       if (d == dmax) break;
-      const dpf_block c = cws[d];
-      const uint4 cs = make_uint4((uint32_t)c.low, (uint32_t)(c.low >> 32), (uint32_t)c.high,
-                                  (uint32_t)(c.high >> 32));
+      const uint4 cs = cw_u4(cws[d]);
       const uint32_t cctl = (uint32_t)(cl[d] & 1) | ((uint32_t)(cr[d] & 1) << 1);
       if (FAST) {
         const uint32_t m = 0u - t;

@@ -47,10 +47,7 @@ constexpr int kWgPerCu = 1;              // one 128 KiB-table workgroup per CU
 constexpr int kTabWords = 4 * 256 * 32;  // 4 tables x 256 entries x 32 bank copies = 128 KiB
 #define DPF_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 constexpr int kMaxCwLevels = 128;
-#ifndef DPF_SMAX
-#define DPF_SMAX 12
-#endif
-constexpr int kSMax = DPF_SMAX;          // max subtree depth handled per thread
+constexpr int kSMax = 12;                // max subtree depth handled per thread
 constexpr int kGMax = kSMax - 1;         // max depth of the DFS stack above leaf pairs
 constexpr int kBMax = 8;                 // max AES blocks hashed per leaf (generic path)
 
@@ -91,51 +88,33 @@ __device__ __forceinline__ void fill_tables(uint32_t* tab) {
   }
 }
 
+// A correction word's seed as the block's four little-endian columns.
+__device__ __forceinline__ uint4 cw_u4(const dpf_block& c) {
+  return make_uint4((uint32_t)c.low, (uint32_t)(c.low >> 32), (uint32_t)c.high,
+                    (uint32_t)(c.high >> 32));
+}
+
 __device__ __forceinline__ void fill_cws(LdsImage& lds, const dpf_block* cw_seed,
                                          const uint8_t* cw_left, const uint8_t* cw_right,
                                          int num_levels) {
   for (int i = threadIdx.x; i < num_levels; i += blockDim.x) {
-    dpf_block b = cw_seed[i];
-    lds.cw_seed[i] = make_uint4((uint32_t)b.low, (uint32_t)(b.low >> 32), (uint32_t)b.high,
-                                (uint32_t)(b.high >> 32));
+    lds.cw_seed[i] = cw_u4(cw_seed[i]);
     lds.cw_ctrl[i] = (uint32_t)(cw_left[i] & 1) | ((uint32_t)(cw_right[i] & 1) << 1);
   }
 }
 
-// Round keys of one AES key held as ONE VGPR: lane i keeps word i (i < 44),
-// read as a wave-uniform value with v_readlane (an SGPR; no memory access).
-// The kernel-argument form (DPF_RK_LANES=0) reloads a round's words with
-// s_load inside the rolled round loops, and SMEM returns out of order behind
-// the same lgkmcnt as the table lookups, so every first use of a reloaded
-// word waited lgkmcnt(0) for all lookups in flight.
-// key_ref must run where all lanes 0..43 of the wave are active (kernel
-// entry; workgroups are whole waves).
-#ifndef DPF_RK_LANES
-#define DPF_RK_LANES 0
-#endif
-#if DPF_RK_LANES
-struct KeyRef {
-  uint32_t v;
-};
-__device__ __forceinline__ KeyRef key_ref(const RoundKeys& rk) {
-  const int l = threadIdx.x & 63;
-  uint32_t v = rk.k[l < 44 ? l : 43];
-  // Pins the load at kernel entry (every lane active): without it the
-  // compiler sank it into divergent code, where inactive lanes never loaded
-  // their word and v_readlane read garbage (wrong outputs, r15).
-  asm volatile("" : "+v"(v));
-  return KeyRef{v};
-}
-__device__ __forceinline__ uint32_t rk_word(KeyRef k, int i) {
-  return __builtin_amdgcn_readlane(k.v, i);
-}
-#else
+// Round keys of one AES key: a pointer into the kernel arguments, so a
+// round's words are reloaded with s_load inside the rolled round loops.  SMEM
+// returns out of order behind the same lgkmcnt as the table lookups, so every
+// first use of a reloaded word waits lgkmcnt(0) for all lookups in flight;
+// holding the 44 words in the lanes of one VGPR and reading them with
+// v_readlane avoided that wait and still measured 0.84-0.97x (DESIGN.md
+// section 9).
 struct KeyRef {
   const uint32_t* k;
 };
 __device__ __forceinline__ KeyRef key_ref(const RoundKeys& rk) { return KeyRef{rk.k}; }
 __device__ __forceinline__ uint32_t rk_word(KeyRef k, int i) { return k.k[i]; }
-#endif
 
 // The four keys of a launch (left, right, value, left ^ right) as KeyRefs.
 struct KeySet {
@@ -159,12 +138,9 @@ struct LdsLookup {
   template <int T, int K>
   __device__ __forceinline__ uint32_t lookup(uint32_t w) const {
     uint32_t off;
-#if !defined(DPF_NO_BYTE1_BITOP3)
     if constexpr (K == 1) {
       off = __builtin_amdgcn_bitop3_b32(w, m1, lt[T], 0xEA);  // (S0 & S1) | S2
-    } else
-#endif
-    {
+    } else {
       constexpr uint32_t sel = 0x0c020000u | ((4u + K) << 8);
       off = __builtin_amdgcn_perm(w, lt[T], sel);
     }
@@ -172,14 +148,6 @@ struct LdsLookup {
   }
   __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) const {
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-  }
-  // The same lookup through the vector memory pipe (aes_core.h DPF_L1_ROUNDS):
-  // T0 from a 1 KiB constant table (L1-resident after the first touches),
-  // T1..T3 as its byte rotations.
-  template <int T, int K>
-  __device__ __forceinline__ uint32_t l1(uint32_t w) const {
-    const uint32_t v = c_t0.v[(w >> (8 * K)) & 0xffu];
-    return T == 0 ? v : __builtin_amdgcn_alignbit(v, v, 32 - 8 * T);
   }
 };
 
@@ -693,9 +661,6 @@ inline bool mod32_eligible(const dpf_value_desc* d, int* blocks_read) {
 // block with lanes of the leaves' widths -- SWAR on one u128: carries stop at
 // the lane top bits `top`, XorWrapper lanes (`xmask`) take a ^ b.  Tuples whose
 // leaves all have one width and kind go to FastIntLeaf instead.
-#ifndef DPF_SWAR_ILP4
-#define DPF_SWAR_ILP4 1
-#endif
 struct SwarLeaf {
   const dpf_block* vcw_elems;  // lanes = E * num_leaves values (device)
   int lanes;
@@ -750,16 +715,11 @@ struct SwarLeaf {
   // profiles/r11_ws_ab.txt).
   __device__ __forceinline__ void emit4(const LdsLookup& lk, KeyRef rkv, Block4* s,
                                         const uint32_t* t, int64_t leaf, char* out) const {
-#if DPF_SWAR_ILP4
     const UniformRK rk[4] = {UniformRK{rkv}, UniformRK{rkv}, UniformRK{rkv}, UniformRK{rkv}};
     dpf_aes::mmo_hashN<4>(s, lk, rk);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       store_packed(out + (leaf + j) * (int64_t)store_bytes, correct(s[j], t[j]), store_bytes);
-#else
-    emit2(lk, rkv, s[0], t[0], s[1], t[1], leaf, out);
-    emit2(lk, rkv, s[2], t[2], s[3], t[3], leaf + 2, out);
-#endif
   }
 };
 
@@ -1057,15 +1017,12 @@ __device__ __forceinline__ uint32_t sigma(uint32_t x) {
   return column() < 2 ? y : (x ^ y);
 }
 
-// DPF_QUAD_LOOKUP_FIRST=1: lane c looks up all four bytes of its OWN column
+// Lookup first: lane c looks up all four bytes of its OWN column
 // (T0[b0(w_c)], T1[b1(w_c)], T2[b2(w_c)], T3[b3(w_c)]) and the quad permutes
 // the looked-up words instead of the state: n_c = A_c ^ B_c+1 ^ C_c+2 ^ D_c+3.
 // The lookups' addresses then depend on w directly (no DPP move and its
-// wait states ahead of the LDS reads), and the moves fold into the XORs
-// after them.  =0: permute the state, then look up (r15 first version).
-#ifndef DPF_QUAD_LOOKUP_FIRST
-#define DPF_QUAD_LOOKUP_FIRST 1
-#endif
+// wait states ahead of the LDS reads, as permuting the state first had: r15
+// first version), and the moves fold into the XORs after them.
 // from_next for a value the next instruction XORs: bound_ctrl set and no
 // `old` operand, so the compiler can fold the move into that XOR as its DPP
 // source (every lane of a quad_perm is valid, so bound_ctrl changes nothing).
@@ -1078,29 +1035,16 @@ __device__ __forceinline__ uint32_t xfrom_next(uint32_t v) {
 }
 // One middle round of column c; k: this column's round-key word.
 __device__ __forceinline__ uint32_t round_mid(uint32_t w, const LdsLookup& lk, uint32_t k) {
-#if DPF_QUAD_LOOKUP_FIRST
   const uint32_t a = lk.template lookup<0, 0>(w), b = lk.template lookup<1, 1>(w);
   const uint32_t c = lk.template lookup<2, 2>(w), d = lk.template lookup<3, 3>(w);
   return ((a ^ k) ^ xfrom_next<1>(b)) ^ xfrom_next<2>(c) ^ xfrom_next<3>(d);
-#else
-  const uint32_t b = from_next<1>(w), c = from_next<2>(w), d = from_next<3>(w);
-  return lk.xor3(lk.xor3(lk.template lookup<0, 0>(w), lk.template lookup<1, 1>(b),
-                         lk.template lookup<2, 2>(c)),
-                 lk.template lookup<3, 3>(d), k);
-#endif
 }
 // The last round of column c (SubBytes + ShiftRows), without the round key.
 __device__ __forceinline__ uint32_t round_last(uint32_t w, const LdsLookup& lk) {
-#if DPF_QUAD_LOOKUP_FIRST
   const uint32_t x = lk.template lookup<2, 0>(w);
   const uint32_t y = xfrom_next<1>(lk.template lookup<3, 1>(w));
   const uint32_t z = xfrom_next<2>(lk.template lookup<0, 2>(w));
   const uint32_t u = xfrom_next<3>(lk.template lookup<1, 3>(w));
-#else
-  const uint32_t b = from_next<1>(w), c = from_next<2>(w), d = from_next<3>(w);
-  const uint32_t x = lk.template lookup<2, 0>(w), y = lk.template lookup<3, 1>(b);
-  const uint32_t z = lk.template lookup<0, 2>(c), u = lk.template lookup<1, 3>(d);
-#endif
   const uint32_t xy = (x & 0x000000ffu) | (y & 0xffffff00u);
   const uint32_t zu = (z & 0x00ff0000u) | (u & 0xff00ffffu);
   return (xy & 0x0000ffffu) | (zu & 0xffff0000u);

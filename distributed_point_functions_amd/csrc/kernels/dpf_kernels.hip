@@ -240,9 +240,6 @@ __device__ __forceinline__ void octet_half(const Leaf& leaf, const LdsLookup& lk
                                            int64_t first_leaf, char* out, Block4* park) {
   leaf.emit4(lk, rkv, l, lt, first_leaf, out);
 }
-#ifndef DPF_MOD32_PARK
-#define DPF_MOD32_PARK 1
-#endif
 // Tuples of IntModN<uint32_t>: the half's second leaf pair (seed | control
 // bit in bit 0) waits in two scratch slots beside the DFS stack while the
 // first pair's four value hashes run, instead of in 8 + 2 VGPRs -- that group
@@ -252,7 +249,6 @@ template <int NL>
 __device__ __forceinline__ void octet_half(const Mod32Leaf<NL>& leaf, const LdsLookup& lk,
                                            KeyRef rkv, Block4* l, const uint32_t* lt,
                                            int64_t first_leaf, char* out, Block4* park) {
-#if DPF_MOD32_PARK
   static_assert(OctetStash<Mod32Leaf<NL>>::value >= 2, "park slots hold the octet stash");
   park[0] = Block4{l[2].w0 | lt[2], l[2].w1, l[2].w2, l[2].w3};
   park[1] = Block4{l[3].w0 | lt[3], l[3].w1, l[3].w2, l[3].w3};
@@ -274,35 +270,28 @@ __device__ __forceinline__ void octet_half(const Mod32Leaf<NL>& leaf, const LdsL
     leaf.convert(w1, b.w0 & 1u, x[3]);
   }
   leaf.store4(x, first_leaf, out);
-#else
-  leaf.emit4(lk, rkv, l, lt, first_leaf, out);
-#endif
 }
 
 // Where the octet keeps its second half's two grandchildren during the first
-// half: 0 = both in scratch beside the DFS stack, 1 = q[3] in LDS (16 B per
-// lane), 2 = also q[2]'s upper 12 bytes in LDS, its low word in a VGPR -- the
+// half: 1 = q[3] in LDS (16 B per lane), q[2] in scratch beside the DFS
+// stack, 2 = also q[2]'s upper 12 bytes in LDS, its low word in a VGPR -- the
 // LDS left over by the T-tables and correction words (150 + 12 KiB of 160).
-// Config 2: 17.21 -> 17.08 (1) -> 16.96 ms (2), WRITE_SIZE 1.30 -> 1.21 -> 1.18x
-// the 8 GiB written; SwarLeaf runs out of VGPRs at 2 (profiles/r11_ws_ab.txt).
-#ifndef DPF_OCTET_LDS_STASH
-#define DPF_OCTET_LDS_STASH 2
-#endif
-template <class Leaf> struct OctetStash { static constexpr int value = DPF_OCTET_LDS_STASH; };
-template <> struct OctetStash<SwarLeaf> {
-  static constexpr int value = DPF_OCTET_LDS_STASH < 1 ? DPF_OCTET_LDS_STASH : 1;
-};
+// Config 2, from both in scratch: 17.21 -> 17.08 (1) -> 16.96 ms (2),
+// WRITE_SIZE 1.30 -> 1.21 -> 1.18x the 8 GiB written; SwarLeaf runs out of
+// VGPRs at 2 (profiles/r11_ws_ab.txt).
+template <class Leaf> struct OctetStash { static constexpr int value = 2; };
+template <> struct OctetStash<SwarLeaf> { static constexpr int value = 1; };
 
 template <class Leaf, bool SCHED = false>   // SCHED: as expand_kernel's
 __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(ExpandParams p,
                                                                              Leaf leaf) {
   __shared__ LdsImage lds;
   constexpr int kStash = OctetStash<Leaf>::value;
-  __shared__ uint4 stash[kStash >= 1 ? kBlock : 1];
+  __shared__ uint4 stash[kBlock];
   __shared__ uint3 stash2[kStash >= 2 ? kBlock : 1];
   __shared__ int next_chunk;   // dynamic distribution: the workgroup's own chunk counter
-  static_assert(sizeof(LdsImage) + (kStash >= 1 ? 16 * kBlock : 0) +
-                    (kStash >= 2 ? 12 * kBlock : 0) + 16 <= 160 * 1024, "LDS over 160 KiB");
+  static_assert(sizeof(LdsImage) + 16 * kBlock + (kStash >= 2 ? 12 * kBlock : 0) + 16 <= 160 * 1024,
+                "LDS over 160 KiB");
   leaf.init();
   fill_tables(lds.tab);
   fill_cws(lds, p.cw_seed, p.cw_left, p.cw_right, p.num_levels);
@@ -384,8 +373,8 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(Exp
       children_step_x2(lk, lk.ks.l, lk.ks.r, c[0], ct[0], c[1], ct[1], lds.cw_seed[lvl + 1],
                        lds.cw_ctrl[lvl + 1], q, qt);
       // The second half's two grandchildren wait outside the VGPRs during the
-      // first half (OctetStash: lane-private LDS slots, else scratch beside
-      // the DFS stack) instead of 8 VGPRs: 128 VGPRs with 37 spilled -> 110
+      // first half (OctetStash: lane-private LDS slots, for SwarLeaf's
+      // q[2] scratch beside the DFS stack) instead of 8 VGPRs: 128 VGPRs with 37 spilled -> 110
       // with none, +3.5%, HBM traffic 17.7 -> 12.1 GB per config-2 launch in
       // scratch, 10.9 GB in LDS (profiles/r11_ws_ab.txt).  The DFS uses
       // sib[0 .. S-4], S <= kSMax.  Each lane reads back only its own slot.
@@ -397,10 +386,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(Exp
       } else {
         sib[kGMax - 2] = q[2];
       }
-      if constexpr (kStash >= 1)
-        stash[threadIdx.x] = make_uint4(q[3].w0, q[3].w1, q[3].w2, q[3].w3);
-      else
-        sib[kGMax - 1] = q[3];
+      stash[threadIdx.x] = make_uint4(q[3].w0, q[3].w1, q[3].w2, q[3].w3);
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         Block4 l[4];
@@ -412,12 +398,8 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(Exp
           } else {
             q[2] = sib[kGMax - 2];
           }
-          if constexpr (kStash >= 1) {
-            const uint4 v = stash[threadIdx.x];
-            q[3] = Block4{v.x, v.y, v.z, v.w};
-          } else {
-            q[3] = sib[kGMax - 1];
-          }
+          const uint4 v = stash[threadIdx.x];
+          q[3] = Block4{v.x, v.y, v.z, v.w};
         }
         children_step_x2(lk, lk.ks.l, lk.ks.r, q[2 * hf], qt[2 * hf], q[2 * hf + 1],
                          qt[2 * hf + 1], lds.cw_seed[lvl + 2], lds.cw_ctrl[lvl + 2], l, lt);
@@ -668,10 +650,8 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void eval_points_kernel(Poin
       const uint8_t* cr = p.cw_right + k * p.cw_stride;
       for (int j = 0; j < L; ++j) {
         const uint32_t b0 = path_bit(path0, L - 1 - j + bb), b1 = path_bit(path1, L - 1 - j + bb);
-        const dpf_block c = cws[j];
+        const uint4 cs = cw_u4(cws[j]);
         const uint32_t cctl = (uint32_t)(cl[j] & 1) | ((uint32_t)(cr[j] & 1) << 1);
-        const uint4 cs = make_uint4((uint32_t)c.low, (uint32_t)(c.low >> 32), (uint32_t)c.high,
-                                    (uint32_t)(c.high >> 32));
         if constexpr (PAIRED)
           path_step2(lk, lk.ks.l, lk.ks.d, s0, t0, b0, s1, t1, b1, cs, cctl);
         else

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void probe_kernel(
 #else
     for (int j = 0; j < k0; ++j) {
       const uint32_t bit = (uint32_t)((item >> (k0 - 1 - j)) & 1);
-      path_step(lk, p.rkl, p.rkd, s, t, bit, lds.cw_seed[j], lds.cw_ctrl[j]);
+      path_step(lk, key_ref(p.rkl), key_ref(p.rkd), s, t, bit, lds.cw_seed[j], lds.cw_ctrl[j]);
     }
 #endif
     const int64_t leaf_base = item << S;
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void probe_kernel(
       for (int d = ds; d < G; ++d) {
         Block4 c0, c1;
         uint32_t t0, t1;
-        children_step(lk, p.rkl.k, p.rkr.k, node, nt, lds.cw_seed[k0 + d], lds.cw_ctrl[k0 + d],
+        children_step(lk, key_ref(p.rkl), key_ref(p.rkr), node, nt, lds.cw_seed[k0 + d], lds.cw_ctrl[k0 + d],
                       c0, t0, c1, t1);
         sib[d] = c1;
         tb = (tb & ~(1u << (d + 1))) | (t1 << (d + 1));
@@ -79,16 +79,16 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void probe_kernel(
 #endif
       Block4 c[2], q[4];
       uint32_t ct[2], qt[4];
-      children_step(lk, p.rkl.k, p.rkr.k, node, nt, lds.cw_seed[lvl], lds.cw_ctrl[lvl], c[0],
+      children_step(lk, key_ref(p.rkl), key_ref(p.rkr), node, nt, lds.cw_seed[lvl], lds.cw_ctrl[lvl], c[0],
                     ct[0], c[1], ct[1]);
-      children_step_x2(lk, p.rkl.k, p.rkr.k, c[0], ct[0], c[1], ct[1], lds.cw_seed[lvl + 1],
+      children_step_x2(lk, key_ref(p.rkl), key_ref(p.rkr), c[0], ct[0], c[1], ct[1], lds.cw_seed[lvl + 1],
                        lds.cw_ctrl[lvl + 1], q, qt);
       uint4* o = reinterpret_cast<uint4*>(p.out + (leaf_base + 8 * g) * 16);
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         Block4 l[4];
         uint32_t lt[4];
-        children_step_x2(lk, p.rkl.k, p.rkr.k, q[2 * hf], qt[2 * hf], q[2 * hf + 1],
+        children_step_x2(lk, key_ref(p.rkl), key_ref(p.rkr), q[2 * hf], qt[2 * hf], q[2 * hf + 1],
                          qt[2 * hf + 1], lds.cw_seed[lvl + 2], lds.cw_ctrl[lvl + 2], l, lt);
 #if defined(PROBE_NODFS)
         if (hf == 1) { next = l[3]; nextt = lt[3]; }

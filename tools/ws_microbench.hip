@@ -54,15 +54,15 @@ void ws_kernel(RoundKeys rkl, RoundKeys rkr, RoundKeys rkv, int t_iters, int b_i
 #endif
       Block4 c[2], q[4];
       uint32_t ct[2], qt[4];
-      children_step(lk, rkl.k, rkr.k, node, nt, lds.cw_seed[lvl], lds.cw_ctrl[lvl], c[0], ct[0],
+      children_step(lk, key_ref(rkl), key_ref(rkr), node, nt, lds.cw_seed[lvl], lds.cw_ctrl[lvl], c[0], ct[0],
                     c[1], ct[1]);
-      children_step_x2(lk, rkl.k, rkr.k, c[0], ct[0], c[1], ct[1], lds.cw_seed[lvl + 1],
+      children_step_x2(lk, key_ref(rkl), key_ref(rkr), c[0], ct[0], c[1], ct[1], lds.cw_seed[lvl + 1],
                        lds.cw_ctrl[lvl + 1], q, qt);
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         Block4 l[4];
         uint32_t lt[4];
-        children_step_x2(lk, rkl.k, rkr.k, q[2 * hf], qt[2 * hf], q[2 * hf + 1], qt[2 * hf + 1],
+        children_step_x2(lk, key_ref(rkl), key_ref(rkr), q[2 * hf], qt[2 * hf], q[2 * hf + 1], qt[2 * hf + 1],
                          lds.cw_seed[lvl + 2], lds.cw_ctrl[lvl + 2], l, lt);
         if (hf == 1) { node = l[3]; nt = lt[3]; }
         dpf_aes::mmo_hashN<4>(l, lk, rv);
