@@ -13,11 +13,17 @@
 #include <vector>
 
 #include "dcf/distributed_comparison_function.h"
+#include "dcf/fss_gates/multiple_interval_containment.h"
 #include "dpf/distributed_point_function.h"
 #include "synthetic_data_benchmarks.h"
 
 namespace py = pybind11;
 using namespace distributed_point_functions;
+using fss_gates::DeviceMicKeyBatch;
+using fss_gates::MicKey;
+using fss_gates::MicKeyBatch;
+using fss_gates::MicParameters;
+using fss_gates::MultipleIntervalContainmentGate;
 
 namespace {
 
@@ -444,6 +450,97 @@ class PyDcf {
   std::shared_ptr<DistributedComparisonFunction> dcf_;
 };
 
+py::array_t<uint64_t> FromU128(const std::vector<uint128>& v) {
+  py::array_t<uint64_t> a({static_cast<py::ssize_t>(v.size()), py::ssize_t{2}});
+  auto w = a.mutable_unchecked<2>();
+  for (size_t i = 0; i < v.size(); ++i) {
+    w(i, 0) = Uint128Low64(v[i]);
+    w(i, 1) = Uint128High64(v[i]);
+  }
+  return a;
+}
+
+struct PyDeviceMicKeyBatch {
+  std::shared_ptr<DeviceMicKeyBatch> d;
+  int64_t NumKeys() const { return d->num_keys(); }
+  int NumIntervals() const { return d->num_intervals(); }
+};
+
+struct PyMicKeyBatch {
+  std::shared_ptr<MicKeyBatch> b;
+  int64_t NumKeys() const { return b->dcf.num_keys; }
+  int NumIntervals() const { return b->num_intervals; }
+  PyKeyBatch Dcf() const {
+    return PyKeyBatch{std::shared_ptr<KeyBatch>(b, &b->dcf)};
+  }
+  py::array_t<uint64_t> MaskShares() const {
+    py::array_t<uint64_t> a({static_cast<py::ssize_t>(b->mask_share.size()), py::ssize_t{2}});
+    if (!b->mask_share.empty())
+      std::memcpy(a.mutable_data(), b->mask_share.data(), b->mask_share.size() * 16);
+    return a;
+  }
+};
+
+class PyMic {
+ public:
+  static PyMic Create(const py::bytes& params) {
+    PyMic r;
+    r.mic_ = std::shared_ptr<MultipleIntervalContainmentGate>(
+        Take(MultipleIntervalContainmentGate::Create(Parse<MicParameters>(params))).release());
+    return r;
+  }
+  py::tuple Gen(const py::int_& r_in,
+                const py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& r_out,
+                const py::object& s0, const py::object& s1, const py::object& z0) {
+    std::pair<MicKey, MicKey> keys;
+    if (s0.is_none()) {
+      keys = Take(mic_->Gen(IntToU128(r_in), ToU128(r_out)));
+    } else {
+      auto z = ToU128(z0.cast<py::array_t<uint64_t, py::array::c_style | py::array::forcecast>>());
+      keys = Take(mic_->GenWithSeeds(IntToU128(r_in), ToU128(r_out), IntToU128(s0.cast<py::int_>()),
+                                     IntToU128(s1.cast<py::int_>()), MakeConstSpan(z)));
+    }
+    return py::make_tuple(Ser(keys.first), Ser(keys.second));
+  }
+  py::array_t<uint64_t> Eval(const py::bytes& key, const py::int_& x) {
+    return FromU128(Take(mic_->Eval(Parse<MicKey>(key), IntToU128(x))));
+  }
+  py::array_t<uint64_t> EvalBatch(const std::vector<py::bytes>& keys,
+                                  const py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& xs) {
+    std::vector<MicKey> k;
+    k.reserve(keys.size());
+    for (const auto& b : keys) k.push_back(Parse<MicKey>(b));
+    std::vector<const MicKey*> ptrs;
+    for (const auto& x : k) ptrs.push_back(&x);
+    auto x = ToU128(xs);
+    return FromU128(Take(mic_->EvalBatch(MakeConstSpan(ptrs), MakeConstSpan(x))));
+  }
+  PyMicKeyBatch MakeKeyBatch(const std::vector<py::bytes>& keys) {
+    std::vector<MicKey> k;
+    k.reserve(keys.size());
+    for (const auto& b : keys) k.push_back(Parse<MicKey>(b));
+    std::vector<const MicKey*> ptrs;
+    for (const auto& x : k) ptrs.push_back(&x);
+    return PyMicKeyBatch{std::make_shared<MicKeyBatch>(Take(mic_->MakeKeyBatch(MakeConstSpan(ptrs))))};
+  }
+  int64_t EvalBatchToDevice(const PyDeviceMicKeyBatch& keys, uintptr_t x, uintptr_t out,
+                            int64_t capacity, uintptr_t stream) {
+    py::gil_scoped_release nogil;
+    auto r = mic_->EvalBatchToDevice(*keys.d, reinterpret_cast<const void*>(x),
+                                     reinterpret_cast<void*>(out), capacity,
+                                     reinterpret_cast<void*>(stream));
+    if (!r.ok()) {
+      py::gil_scoped_acquire g;
+      throw StatusError(r.status());
+    }
+    return *r;
+  }
+  int NumUniqueOffsets() const { return mic_->num_unique_offsets(); }
+
+ private:
+  std::shared_ptr<MultipleIntervalContainmentGate> mic_;
+};
+
 }  // namespace
 
 PYBIND11_MODULE(_dpf_host, m) {
@@ -526,6 +623,27 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_batch_to_device", &PyDcf::EvaluateBatchToDevice)
       .def("packed_size", &PyDcf::PackedSize)
       .def("hierarchy_to_tree", &PyDcf::HierarchyToTree);
+  py::class_<PyDeviceMicKeyBatch>(m, "DeviceMicKeyBatch")
+      .def_property_readonly("num_keys", &PyDeviceMicKeyBatch::NumKeys)
+      .def_property_readonly("num_intervals", &PyDeviceMicKeyBatch::NumIntervals);
+  py::class_<PyMicKeyBatch>(m, "MicKeyBatch")
+      .def_property_readonly("num_keys", &PyMicKeyBatch::NumKeys)
+      .def_property_readonly("num_intervals", &PyMicKeyBatch::NumIntervals)
+      .def("dcf", &PyMicKeyBatch::Dcf)
+      .def("mask_shares", &PyMicKeyBatch::MaskShares)
+      .def("upload", [](const PyMicKeyBatch& b, uintptr_t stream) {
+        auto d = Take(DeviceMicKeyBatch::Upload(*b.b, reinterpret_cast<void*>(stream)));
+        return PyDeviceMicKeyBatch{std::shared_ptr<DeviceMicKeyBatch>(d.release())};
+      });
+  py::class_<PyMic>(m, "MultipleIntervalContainmentGate")
+      .def_static("create", &PyMic::Create)
+      .def("gen", &PyMic::Gen, py::arg("r_in"), py::arg("r_out"), py::arg("seed_0") = py::none(),
+           py::arg("seed_1") = py::none(), py::arg("z_0") = py::none())
+      .def("eval", &PyMic::Eval)
+      .def("eval_batch", &PyMic::EvalBatch)
+      .def("make_key_batch", &PyMic::MakeKeyBatch)
+      .def("eval_batch_to_device", &PyMic::EvalBatchToDevice)
+      .def("num_unique_offsets", &PyMic::NumUniqueOffsets);
   m.def("synthetic_levels", [](int log, int64_t count, double concentration, uint64_t seed, int mef) {
     auto nz = experiments::MakeSyntheticNonzeros(count, log, concentration, seed);
     auto prefixes = experiments::ComputePrefixes(nz, log);
@@ -588,6 +706,11 @@ PYBIND11_MODULE(_dpf_host, m) {
     if (name == "CorrectionWord") return Ser(Parse<CorrectionWord>(b));
     if (name == "PartialEvaluation") return Ser(Parse<PartialEvaluation>(b));
     if (name == "Block") return Ser(Parse<Block>(b));
+    if (name == "DcfParameters") return Ser(Parse<DcfParameters>(b));
+    if (name == "DcfKey") return Ser(Parse<DcfKey>(b));
+    if (name == "Interval") return Ser(Parse<fss_gates::Interval>(b));
+    if (name == "MicParameters") return Ser(Parse<MicParameters>(b));
+    if (name == "MicKey") return Ser(Parse<MicKey>(b));
     throw std::invalid_argument("unknown message " + name);
   });
   m.def("debug_string", [](const std::string& name, const py::bytes& b) -> std::string {
@@ -595,6 +718,9 @@ PYBIND11_MODULE(_dpf_host, m) {
     if (name == "EvaluationContext") return Parse<EvaluationContext>(b).DebugString();
     if (name == "ValueType") return Parse<ValueType>(b).DebugString();
     if (name == "Value") return Parse<Value>(b).DebugString();
+    if (name == "Interval") return Parse<fss_gates::Interval>(b).DebugString();
+    if (name == "MicParameters") return Parse<MicParameters>(b).DebugString();
+    if (name == "MicKey") return Parse<MicKey>(b).DebugString();
     throw std::invalid_argument("unknown message " + name);
   });
   m.def("validate_context", [](const std::vector<py::bytes>& params, const py::bytes& ctx) {

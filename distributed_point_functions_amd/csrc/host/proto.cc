@@ -1,5 +1,6 @@
 // proto.cc -- proto3 binary wire format for the DPF messages
-// (dpf/distributed_point_function.proto:25-171).  Field numbers and wire types
+// (dpf/distributed_point_function.proto:25-171), the DCF messages and the
+// multiple-interval-containment gate's.  Field numbers and wire types
 // follow the .proto exactly; serialisation is in field-number order with
 // proto3 implicit presence (zero scalars omitted, set oneof members and present
 // sub-messages always written), which is byte-identical to the canonical
@@ -10,6 +11,7 @@
 
 #include "dpf/distributed_point_function.pb.h"
 #include "dcf/distributed_comparison_function.pb.h"
+#include "dcf/fss_gates/multiple_interval_containment.pb.h"
 
 namespace distributed_point_functions {
 namespace {
@@ -616,6 +618,91 @@ std::string DcfKey::DebugString() const {
 }
 bool DcfKey::operator==(const DcfKey& o) const { return has_key_ == o.has_key_ && key_ == o.key_; }
 
+// ============================================================== MIC gate messages
+// dcf/fss_gates/multiple_interval_containment.proto: Interval{lower_bound = 1,
+// upper_bound = 2}, MicParameters{log_group_size = 1, intervals = 2},
+// MicKey{dcfkey = 1, output_mask_share = 2}.
+namespace fss_gates {
+bool Interval::SerializeToString(std::string* out) const {
+  out->clear();
+  Writer w{out};
+  if (has_lower_) w.msg(1, lower_);
+  if (has_upper_) w.msg(2, upper_);
+  return true;
+}
+bool Interval::ParseFromArray(const void* d, int n) {
+  BeginParse(this);
+  return ParseFields(d, n, [&](int f, int wt, Reader& r) {
+    if (f == 1 && wt == kLen) return ParseSub(r.len(), mutable_lower_bound());
+    if (f == 2 && wt == kLen) return ParseSub(r.len(), mutable_upper_bound());
+    r.skip(wt);
+    return r.ok;
+  });
+}
+std::string Interval::DebugString() const {
+  Text t;
+  if (has_lower_) t.msg("lower_bound", lower_);
+  if (has_upper_) t.msg("upper_bound", upper_);
+  return t.os.str();
+}
+bool Interval::operator==(const Interval& o) const {
+  return has_lower_ == o.has_lower_ && has_upper_ == o.has_upper_ && lower_ == o.lower_ &&
+         upper_ == o.upper_;
+}
+
+bool MicParameters::SerializeToString(std::string* out) const {
+  out->clear();
+  Writer w{out};
+  w.i32(1, log_group_size_);
+  for (const Interval& i : intervals_) w.msg(2, i);
+  return true;
+}
+bool MicParameters::ParseFromArray(const void* d, int n) {
+  BeginParse(this);
+  return ParseFields(d, n, [&](int f, int wt, Reader& r) {
+    if (f == 1 && wt == kVarint) log_group_size_ = static_cast<int32_t>(r.varint());
+    else if (f == 2 && wt == kLen) return ParseSub(r.len(), add_intervals());
+    else r.skip(wt);
+    return r.ok;
+  });
+}
+std::string MicParameters::DebugString() const {
+  Text t;
+  if (log_group_size_) t.scalar("log_group_size", std::to_string(log_group_size_));
+  for (const Interval& i : intervals_) t.msg("intervals", i);
+  return t.os.str();
+}
+bool MicParameters::operator==(const MicParameters& o) const {
+  return log_group_size_ == o.log_group_size_ && intervals_ == o.intervals_;
+}
+
+bool MicKey::SerializeToString(std::string* out) const {
+  out->clear();
+  Writer w{out};
+  if (has_dcfkey_) w.msg(1, dcfkey_);
+  for (const Value_Integer& v : shares_) w.msg(2, v);
+  return true;
+}
+bool MicKey::ParseFromArray(const void* d, int n) {
+  BeginParse(this);
+  return ParseFields(d, n, [&](int f, int wt, Reader& r) {
+    if (f == 1 && wt == kLen) return ParseSub(r.len(), mutable_dcfkey());
+    if (f == 2 && wt == kLen) return ParseSub(r.len(), add_output_mask_share());
+    r.skip(wt);
+    return r.ok;
+  });
+}
+std::string MicKey::DebugString() const {
+  Text t;
+  if (has_dcfkey_) t.msg("dcfkey", dcfkey_);
+  for (const Value_Integer& v : shares_) t.msg("output_mask_share", v);
+  return t.os.str();
+}
+bool MicKey::operator==(const MicKey& o) const {
+  return has_dcfkey_ == o.has_dcfkey_ && dcfkey_ == o.dcfkey_ && shares_ == o.shares_;
+}
+}  // namespace fss_gates
+
 #define DPF_PARSE_FROM_STRING(Name) \
   bool Name::ParseFromString(const std::string& s) { \
     return ParseFromArray(s.data(), static_cast<int>(s.size())); \
@@ -635,5 +722,8 @@ DPF_PARSE_FROM_STRING(PartialEvaluation)
 DPF_PARSE_FROM_STRING(EvaluationContext)
 DPF_PARSE_FROM_STRING(DcfParameters)
 DPF_PARSE_FROM_STRING(DcfKey)
+DPF_PARSE_FROM_STRING(fss_gates::Interval)
+DPF_PARSE_FROM_STRING(fss_gates::MicParameters)
+DPF_PARSE_FROM_STRING(fss_gates::MicKey)
 
 }  // namespace distributed_point_functions

@@ -97,12 +97,14 @@ def load(require_gpu: bool = False):
         L.dpf_hip_clock_probe_read.argtypes = [ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_int64),
                                                ctypes.POINTER(ctypes.c_double)]
-        # Diagnostics a parent build swapped in for an A/B (tools/ab.sh lib:<name>)
+        # Entry points a parent build swapped in for an A/B (tools/ab.sh lib:<name>)
         # may not have yet; build() checks the in-tree library for every symbol.
         for name, types in (("dpf_hip_clock_probe_exits", [ctypes.POINTER(ctypes.c_double)]),
                             ("dpf_hip_octet_schedule",
                              [I64, I, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
-                            ("dpf_hip_last_expand_schedule", [ctypes.POINTER(ctypes.c_int64)])):
+                            ("dpf_hip_last_expand_schedule", [ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_mic_eval_batch",
+                             [I64, I, P, P, P, P, P, I, P, P, I, P, I] + [P] * 11)):
             if hasattr(L, name):
                 getattr(L, name).argtypes = types
         _lib = L

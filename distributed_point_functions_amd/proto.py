@@ -1,5 +1,6 @@
 """Python protobuf classes for the reference wire format
-(dpf/distributed_point_function.proto:25-171), built from a descriptor
+(dpf/distributed_point_function.proto:25-171, the DCF's and the
+multiple-interval-containment gate's), built from descriptors
 constructed in code (there is no protoc in this image).  Field names, numbers,
 types and oneofs are those of the .proto, so the bytes interoperate with the
 reference and with the C++ codec in csrc/host/proto.cc.
@@ -8,6 +9,7 @@ from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
 
 _F = descriptor_pb2.FieldDescriptorProto
 _PKG = "distributed_point_functions"
+_MIC_PKG = _PKG + ".fss_gates"
 
 
 def _field(msg, name, number, ftype, label=_F.LABEL_OPTIONAL, type_name=None, oneof=None):
@@ -101,10 +103,31 @@ def _build():
     dk = dcf.message_type.add(name="DcfKey")
     _field(dk, "key", 1, M, O, "DpfKey")
 
+    # dcf/fss_gates/multiple_interval_containment.proto
+    mic = descriptor_pb2.FileDescriptorProto()
+    mic.name = "dcf/fss_gates/multiple_interval_containment.proto"
+    mic.package = _MIC_PKG
+    mic.syntax = "proto3"
+    mic.dependency.append(dcf.name)
+    mic.dependency.append(fd.name)
+    iv = mic.message_type.add(name="Interval")
+    _field(iv, "lower_bound", 1, M, O, "Value.Integer")
+    _field(iv, "upper_bound", 2, M, O, "Value.Integer")
+    mp = mic.message_type.add(name="MicParameters")
+    _field(mp, "log_group_size", 1, _F.TYPE_INT32)
+    _field(mp, "intervals", 2, M, R, "fss_gates.Interval")
+    mk = mic.message_type.add(name="MicKey")
+    _field(mk, "dcfkey", 1, M, O, "DcfKey")
+    _field(mk, "output_mask_share", 2, M, R, "Value.Integer")
+
     pool = descriptor_pool.DescriptorPool()
     pool.Add(fd)
     pool.Add(dcf)
+    pool.Add(mic)
     out = {}
+    for name in ("Interval", "MicParameters", "MicKey"):
+        out[name] = message_factory.GetMessageClass(
+            pool.FindMessageTypeByName(f"{_MIC_PKG}.{name}"))
     for name in ("ValueType", "Value", "DpfParameters", "Block", "CorrectionWord", "DpfKey",
                  "PartialEvaluation", "EvaluationContext", "DcfParameters", "DcfKey"):
         out[name] = message_factory.GetMessageClass(pool.FindMessageTypeByName(f"{_PKG}.{name}"))
@@ -122,3 +145,6 @@ PartialEvaluation = _CLASSES["PartialEvaluation"]
 EvaluationContext = _CLASSES["EvaluationContext"]
 DcfParameters = _CLASSES["DcfParameters"]
 DcfKey = _CLASSES["DcfKey"]
+Interval = _CLASSES["Interval"]
+MicParameters = _CLASSES["MicParameters"]
+MicKey = _CLASSES["MicKey"]

@@ -494,6 +494,37 @@ int dpf_hip_dcf_eval_batch(int64_t num_keys, int64_t points_per_key, int shared_
                            const dpf_aes_key* key_value, const dpf_value_desc* desc,
                            void* out, void* stream);
 
+/* ---- batched multiple-interval-containment gate (eprint 2020/1392 Fig. 14) -
+ * MultipleIntervalContainmentGate::Eval (dcf/fss_gates/
+ * multiple_interval_containment.cc:206-275) for num_gates gates over
+ * Z_N, N = 2^log_group_size (1..127), each with its own key and masked input
+ * x[g] < N, all with the same num_intervals public intervals [p_i, q_i]:
+ *   out[g*num_intervals + i] = (party_g ? [x_g > p_i] - [x_g > q'_i] : 0)
+ *                              - DCF(key_g, x_g + N-1 - p_i)
+ *                              + DCF(key_g, x_g + N-1 - q'_i)
+ *                              + mask_share[g*num_intervals + i]      (mod N)
+ * with q'_i = q_i + 1 mod N.  The DCF is the uint128 DCF of log domain
+ * log_group_size; key_seed .. value_correction are its key batch as
+ * dpf_hip_dcf_eval_batch takes them (value_correction: host array of
+ * log_group_size device pointers, one dpf_block per key and level).
+ * `offsets` (device, num_offsets values < N) is the set of distinct p_i and
+ * q'_i; lower_index[i] / upper_index[i] (device) are the positions of p_i and
+ * q'_i in it, lower_bound / upper_bound_next (device) p_i and q'_i themselves.
+ * One DCF walk runs per (gate, offset) -- not per (gate, bound) -- into
+ * `scratch` (device, num_gates * num_offsets blocks, caller-owned), then one
+ * lane per (gate, interval) combines.  Every argument is validated before any
+ * device work. */
+int dpf_hip_mic_eval_batch(int64_t num_gates, int log_group_size, const dpf_block* key_seed,
+                           const uint8_t* party, const dpf_block* cw_seed,
+                           const uint8_t* cw_left, const uint8_t* cw_right, int cw_stride,
+                           const dpf_block* const* value_correction, const dpf_block* x,
+                           int num_offsets, const dpf_block* offsets, int num_intervals,
+                           const int32_t* lower_index, const int32_t* upper_index,
+                           const dpf_block* lower_bound, const dpf_block* upper_bound_next,
+                           const dpf_block* mask_share, dpf_block* scratch,
+                           const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+                           const dpf_aes_key* key_value, dpf_block* out, void* stream);
+
 /* ---- timing helpers (hipEvents on the given stream) ------------------------ */
 int dpf_hip_event_create(void** ev);
 int dpf_hip_event_destroy(void* ev);

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "dcf/distributed_comparison_function.h"
+#include "dcf/fss_gates/multiple_interval_containment.h"
 #include "dpf/distributed_point_function.h"
 #include "dpf/int_mod_n.h"
 #include "dpf/tuple.h"
@@ -409,6 +410,47 @@ void EvaluateDcf(Runner& r, const std::string& tname) {
   }
 }
 
+// BM_MicEval/log/intervals: one MultipleIntervalContainmentGate::Eval(key, x)
+// per iteration -- the single-gate drop-in call -- on a gate whose intervals
+// partition Z_{2^log}, x counting up.  The reference ships no benchmark for
+// its fss_gates, so there is no reference row to compare this one with; it
+// records the per-call latency (two launches and one copy back), and the
+// batched API (EvalBatchToDevice, tools/mic_bench.py) is the throughput path.
+void MicEval(Runner& r) {
+  for (int log : {16, 32, 64, 127}) {
+    for (int intervals : {1, 8, 64}) {
+      const std::string name =
+          "BM_MicEval/" + std::to_string(log) + "/" + std::to_string(intervals);
+      if (!std::regex_search(name, r.filter)) continue;
+      const uint128 N = uint128{1} << log;
+      dpf::fss_gates::MicParameters p;
+      p.set_log_group_size(log);
+      for (int i = 0; i < intervals; ++i) {
+        const uint128 lo = N / intervals * i;
+        const uint128 hi = i + 1 < intervals ? N / intervals * (i + 1) - 1 : N - 1;
+        auto* iv = p.add_intervals();
+        iv->mutable_lower_bound()->mutable_value_uint128()->set_high(dpf::Uint128High64(lo));
+        iv->mutable_lower_bound()->mutable_value_uint128()->set_low(dpf::Uint128Low64(lo));
+        iv->mutable_upper_bound()->mutable_value_uint128()->set_high(dpf::Uint128High64(hi));
+        iv->mutable_upper_bound()->mutable_value_uint128()->set_low(dpf::Uint128Low64(hi));
+      }
+      auto gate = Must(dpf::fss_gates::MultipleIntervalContainmentGate::Create(p), "MIC Create");
+      std::mt19937_64 rng(log * 100 + intervals);
+      const uint128 r_in = dpf::MakeUint128(rng(), rng()) & (N - 1);
+      std::vector<uint128> r_out(intervals);
+      for (auto& v : r_out) v = dpf::MakeUint128(rng(), rng()) & (N - 1);
+      auto keys = Must(gate->Gen(r_in, r_out), "MIC Gen");
+      uint128 x = 0;
+      r.Run(name, [&](int64_t n) {
+        for (int64_t it = 0; it < n; ++it) {
+          Sink(Must(gate->Eval(keys.first, x), "MIC Eval"));
+          x = (x + 1) & (N - 1);
+        }
+      });
+    }
+  }
+}
+
 using MyIntModN = IntModN<uint32_t, 4294967291u>;                 // 2^32 - 5
 using MyIntModN64 = IntModN<uint64_t, 18446744073709551557ull>;   // 2^64 - 59
 
@@ -476,6 +518,7 @@ int main(int argc, char** argv) {
   EvaluateDcf<uint32_t>(r, "uint32_t");
   EvaluateDcf<uint64_t>(r, "uint64_t");
   EvaluateDcf<uint128>(r, "uint128");
+  MicEval(r);
   if (!json.empty()) {
     std::ofstream o(json);
     o << "[\n";
