@@ -37,6 +37,7 @@ namespace dpf_rt {
 thread_local std::string g_last_error;
 thread_local const char* g_last_expand = "";
 thread_local int g_last_expand_s = -1;
+thread_local int64_t g_last_dynamic_chunks = 0;   // dpf_hip_last_dynamic_chunks
 // dpf_hip_clock_probe's device accumulator (NULL: off), read by every
 // dpf_hip_expand launch.
 std::atomic<unsigned long long*> g_clock_acc{nullptr};
@@ -788,10 +789,11 @@ int block_for(int64_t work_items) {
 }
 
 int64_t dynamic_chunks_per_wg(int64_t items, int grid, int block, const char* env) {
+  g_last_dynamic_chunks = 0;
   if (env && hook_is(env, '0')) return 0;
   const int64_t chunks = (items + 63) / 64;
   if (chunks < (int64_t)grid * (block / 64) * 4) return 0;
-  return (chunks + grid - 1) / grid;
+  return g_last_dynamic_chunks = (chunks + grid - 1) / grid;
 }
 
 int grid_for(int64_t work_items, int block) {
@@ -1499,6 +1501,11 @@ int dpf_hip_abi_version(void) { return DPF_HIP_ABI_VERSION; }
 const char* dpf_hip_last_error(void) { return dpf_rt::g_last_error.c_str(); }
 
 const char* dpf_hip_last_points_kernel(void) { return g_last_points_kernel; }
+int dpf_hip_last_dynamic_chunks(int64_t* per_wg) {
+  if (!per_wg) return fail(kInvalidArgument, "per_wg is NULL");
+  *per_wg = dpf_rt::g_last_dynamic_chunks;
+  return kOk;
+}
 const char* dpf_hip_last_expand_kernel(int* subtree_depth) {
   if (subtree_depth) *subtree_depth = dpf_rt::g_last_expand_s;
   return dpf_rt::g_last_expand;

@@ -103,6 +103,7 @@ def load(require_gpu: bool = False):
                             ("dpf_hip_octet_schedule",
                              [I64, I, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_last_expand_schedule", [ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_last_dynamic_chunks", [ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_mic_eval_batch",
                              [I64, I, P, P, P, P, P, I, P, P, I, P, I] + [P] * 11)):
             if hasattr(L, name):
@@ -133,6 +134,15 @@ def last_points_kernel() -> str:
     """Kernel of this thread's last point evaluation, e.g. "points/ilp4" --
     dispatch diagnostics for the tests."""
     return load().dpf_hip_last_points_kernel().decode()
+
+
+def last_dynamic_chunks() -> int:
+    """Chunks of 64 items per workgroup of this thread's last launch that can
+    take its work dynamically (0: the fixed grid-stride share) -- schedule
+    diagnostics for the tests."""
+    n = ctypes.c_int64(-1)
+    check(load().dpf_hip_last_dynamic_chunks(ctypes.byref(n)))
+    return n.value
 
 
 def clock_probe(on: bool) -> None:

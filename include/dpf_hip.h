@@ -251,6 +251,10 @@ const char* dpf_hip_last_batch_kernel(void);
  * (one, for launches below one wave per CU); "" before the first call. */
 const char* dpf_hip_last_points_kernel(void);
 
+/* Chunks of 64 items per workgroup chosen for the calling thread's most recent
+ * launch that can distribute its work dynamically (0: a fixed grid-stride share). */
+int dpf_hip_last_dynamic_chunks(int64_t* per_wg);
+
 /* ---- a11: fused point evaluation for many keys ----------------------------
  * Replaces EvaluateAtImpl's path walk + hash + correction (h:930-1003).
  * Point i belongs to key k = i / points_per_key.  Its walk starts at

@@ -174,14 +174,19 @@ def test_dcf_fast_kernel_uniform_keys(vt, n, shared, quad, monkeypatch):
 
 @pytest.mark.parametrize("vt", [("int", 64), ("xor", 32), ("int", 8)], ids=str)
 def test_dcf_fast_kernel_full_launch(vt, monkeypatch):
-    """A launch that fills the chip twice over (512 keys x 1024 points):
+    """A launch that fills the chip twice over (512 keys x 1024 points = 2^19
+    items) but stays on the grid-stride loop -- chunks are handed out from 4
+    per wave, 2^20 items on 256 CUs (test_dynamic_chunks_gpu.py covers those):
     bit-exact against the general kernel on every output and against the
     oracle on sampled rows."""
+    from distributed_point_functions_amd import hip_abi as H
     nk, ppk, n = 512, 1024, 64
     dcf, P, beta, alphas, pts, run = _batch_case(vt, n, nk, ppk, False, seed=99)
     got = run()
+    assert H.last_dynamic_chunks() == 0
     monkeypatch.setenv("DPF_DCF_GENERAL", "1")
     general = run()
+    assert H.last_dynamic_chunks() == 0
     np.testing.assert_array_equal(got, general)
     for k in (0, 1, nk - 1):
         okeys = O.dcf_generate_keys(P, alphas[k], beta, 2 * k + 1, 2 * k + 2)

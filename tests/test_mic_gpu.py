@@ -201,15 +201,20 @@ def test_gate_without_intervals_returns_empty():
 
 def test_full_launch_equals_the_dcf_route():
     """4096 gates x 8 non-adjacent intervals at n = 32: 65536 walks, above
-    num_cus x 64.  Every output equals the one composed from
-    DistributedComparisonFunction.evaluate_batch_to_device on the 2 m points
-    per key (prepared and combined in numpy); 20 sampled gates match the model."""
+    num_cus x 64 -- every CU has work, but the walks stay on the grid-stride
+    loop (chunks are handed out from 2^20 walks on 256 CUs;
+    test_dynamic_chunks_gpu.py covers those).  Every output equals the one
+    composed from DistributedComparisonFunction.evaluate_batch_to_device on the
+    2 m points per key (prepared and combined in numpy); 20 sampled gates match
+    the model."""
     import torch
+    from distributed_point_functions_amd import hip_abi as H
     n, N, m, gates = 32, 1 << 32, 8, 4096
     c = Case(n, MM.disjoint(n, m, np.random.default_rng(8)), gates, seed=4096)
     assert c.g.num_unique_offsets() == 2 * m
     keys = c.keys(0)
     got = np.array(run_batch(c.g, keys, c.masked), dtype=np.uint64)          # values < 2^32
+    assert H.last_dynamic_chunks() == 0
 
     p = pb.DcfParameters()
     p.parameters.log_domain_size = n
