@@ -113,15 +113,10 @@ __device__ __forceinline__ void path_step2k(const LdsLookup& lk, KeyRef rkl,
   Block4 h0 = s0, h1 = s1;
   const SelectRK rk{rkl, rkd, 0u - bit};
   dpf_aes::mmo_hash2(h0, h1, lk, rk, rk);
-  uint32_t m0 = 0u - t0, m1 = 0u - t1;
-  h0.w0 ^= cs0.x & m0; h0.w1 ^= cs0.y & m0; h0.w2 ^= cs0.z & m0; h0.w3 ^= cs0.w & m0;
-  h1.w0 ^= cs1.x & m1; h1.w1 ^= cs1.y & m1; h1.w2 ^= cs1.z & m1; h1.w3 ^= cs1.w & m1;
-  uint32_t n0 = (h0.w0 & 1u) ^ (t0 & ((cc0 >> bit) & 1u));
-  uint32_t n1 = (h1.w0 & 1u) ^ (t1 & ((cc1 >> bit) & 1u));
-  h0.w0 &= ~1u;
-  h1.w0 &= ~1u;
-  s0 = h0; t0 = n0;
-  s1 = h1; t1 = n1;
+  correct_child(h0, t0, bit, cs0, cc0);
+  correct_child(h1, t1, bit, cs1, cc1);
+  s0 = h0;
+  s1 = h1;
 }
 
 // ---------------------------------------------------------------- leaf policies
@@ -379,7 +374,7 @@ __device__ __forceinline__ void expand_and_convert(const LdsLookup& lk, const Ba
   for (int d = 0; d < MAXE; ++d) {
     if (d < E) {
       const uint4 cs = cw_u4(cws[d]);
-      const uint32_t cc = (uint32_t)(cl[d] & 1) | ((uint32_t)(cr[d] & 1) << 1);
+      const uint32_t cc = cw_ctrl2(cl, cr, d);
       if (d == 0) {
         Block4 c0, c1;
         uint32_t t0, t1;
@@ -452,7 +447,8 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void batch_level_kernel(
   const int W = p.walk_levels;
   const int NL = 1 << p.expand_levels;
   // Wave tasks (key chunk x 64 start nodes) by grid stride, or taken one at a
-  // time per wave (dyn_per_wg > 0).
+  // time per wave (dyn_per_wg > 0).  ItemLoop's loop written out: with the
+  // helper 7 instances changed their register counts (r21).
   const int64_t tasks = p.num_threads >> 6;
   for (int64_t g = p.dyn_per_wg ? take_chunk(&next_chunk, p.dyn_per_wg, tasks, p.num_threads)
                                 : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -662,11 +658,10 @@ __global__ void gather_batched_kernel(int64_t keys, int64_t in_row, int64_t rows
 template <class V, int MAXE, bool SUM>
 int launch_batch(const BatchLevelParams& p0, const V& v, hipStream_t s) {
   BatchLevelParams p = p0;
-  const int blk = block_for(p.num_threads);
-  const int grid = grid_for(p.num_threads, blk);
   // DPF_BATCH_DYNAMIC=0: a fixed share of wave tasks per wave (A/B hook).
-  p.dyn_per_wg = dynamic_chunks_per_wg(p.num_threads, grid, blk, "DPF_BATCH_DYNAMIC");
-  hipLaunchKernelGGL((batch_level_kernel<V, MAXE, SUM>), dim3(grid), dim3(blk), 0, s, p, v);
+  const LaunchShape sh = chunked_shape(p.num_threads, "DPF_BATCH_DYNAMIC");
+  p.dyn_per_wg = sh.dyn_per_wg;
+  hipLaunchKernelGGL((batch_level_kernel<V, MAXE, SUM>), dim3(sh.grid), dim3(sh.block), 0, s, p, v);
   HIP_TRY(hipGetLastError());
   return kOk;
 }
@@ -685,13 +680,10 @@ int launch_mod32(const BatchLevelParams& p, const dpf_value_desc* desc, int b, i
 
 template <bool SUM>
 int launch_batch_fast(const BatchLevelParams& p, int bits, int xor_mode, hipStream_t s) {
-  switch (bits) {
-    case 8: return launch_batch<FastV<8>, 2, SUM>(p, FastV<8>{xor_mode, 0, {}}, s);
-    case 16: return launch_batch<FastV<16>, 2, SUM>(p, FastV<16>{xor_mode, 0, {}}, s);
-    case 32: return launch_batch<FastV<32>, 2, SUM>(p, FastV<32>{xor_mode, 0, {}}, s);
-    case 64: return launch_batch<FastV<64>, 2, SUM>(p, FastV<64>{xor_mode, 0, {}}, s);
-    default: return launch_batch<FastV<128>, 2, SUM>(p, FastV<128>{xor_mode, 0, {}}, s);
-  }
+  return with_bits(bits, [&](auto b) {
+    using V = FastV<decltype(b)::value>;
+    return launch_batch<V, 2, SUM>(p, V{xor_mode, 0, {}}, s);
+  });
 }
 
 }  // namespace

@@ -216,13 +216,12 @@ void hh_level_kernel(HHParams p) {
       // children's children (ILP4); leaf order 0..3 = LL, LR, RL, RR.
       const int64_t cwi = k * p.cw_stride + p.cw_level;
       const uint4 cs0 = cw_u4(p.cw_seed[cwi]);
-      const uint32_t cc0 = (uint32_t)(p.cw_left[cwi] & 1) | ((uint32_t)(p.cw_right[cwi] & 1) << 1);
+      const uint32_t cc0 = cw_ctrl2(p.cw_left, p.cw_right, cwi);
       Block4 c0, c1;
       uint32_t t0, t1;
       children_step(lk, lk.ks.l, lk.ks.r, s, t, cs0, cc0, c0, t0, c1, t1);
       const uint4 cs1 = cw_u4(p.cw_seed[cwi + 1]);
-      const uint32_t cc1 =
-          (uint32_t)(p.cw_left[cwi + 1] & 1) | ((uint32_t)(p.cw_right[cwi + 1] & 1) << 1);
+      const uint32_t cc1 = cw_ctrl2(p.cw_left, p.cw_right, cwi + 1);
       Block4 L[4];
       uint32_t tl[4];
       children_step_x2(lk, lk.ks.l, lk.ks.r, c0, t0, c1, t1, cs1, cc1, L, tl);

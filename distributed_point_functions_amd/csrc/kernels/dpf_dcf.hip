@@ -48,7 +48,7 @@ struct DcfParams {
   const uint8_t* cw_right;
   char* out;
   RoundKeys rkl, rkd, rkv;
-  int64_t dyn_per_wg;  // take_chunk's per_wg (0: grid stride)
+  int64_t dyn_per_wg;  // ItemLoop's per_wg (0: grid stride)
 };
 
 __device__ __forceinline__ u128 shr128(u128 x, int s) { return s >= 128 ? (u128)0 : x >> s; }
@@ -57,20 +57,15 @@ template <int BITS, bool FAST>
 __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_eval_kernel(
     DcfParams p, DcfLevels lv, GenericLeaf g) {
   __shared__ LdsImage lds;
-  __shared__ int next_chunk;   // take_chunk (dpf_device.h)
+  __shared__ int next_chunk;   // ItemLoop (dpf_device.h)
   fill_tables(lds.tab);
   if (threadIdx.x == 0) next_chunk = 0;
   __syncthreads();
   const LdsLookup lk = make_lookup(lds, KeySet{key_ref(p.rkl), KeyRef{}, key_ref(p.rkv), key_ref(p.rkd)});
   const int n = lv.n;
   const int dmax = lv.depth[n - 1];
-  // Items by grid stride, or 64 at a time per wave (dyn_per_wg > 0).
-  const int64_t nch = (p.num_items + 63) / 64;
-  for (int64_t u = p.dyn_per_wg ? take_chunk(&next_chunk, p.dyn_per_wg, nch, p.num_items)
-                                : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       u < p.num_items;
-       u = p.dyn_per_wg ? take_chunk(&next_chunk, p.dyn_per_wg, nch, p.num_items)
-                        : u + (int64_t)gridDim.x * blockDim.x) {
+  const ItemLoop items{&next_chunk, p.dyn_per_wg, (p.num_items + 63) / 64, p.num_items};
+  for (int64_t u = items.first(); u < p.num_items; u = items.next(u)) {
     const int64_t k = u / p.points_per_key, j = u - k * p.points_per_key;
     const u128 x = dpf_u128(p.points[p.shared_points ? j : u]);
     const int party = p.party[k] & 1;
@@ -121,14 +116,10 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_eval_kernel(
       }
       if (d == dmax) break;
       const uint4 cs = cw_u4(cws[d]);
-      const uint32_t cctl = (uint32_t)(cl[d] & 1) | ((uint32_t)(cr[d] & 1) << 1);
+      const uint32_t cctl = cw_ctrl2(cl, cr, d);
       if (FAST) {
-        const uint32_t m = 0u - t;
-        hn.w0 ^= cs.x & m; hn.w1 ^= cs.y & m; hn.w2 ^= cs.z & m; hn.w3 ^= cs.w & m;
-        const uint32_t nt = (hn.w0 & 1u) ^ (t & ((cctl >> bit) & 1u));
-        hn.w0 &= ~1u;
+        correct_child(hn, t, bit, cs, cctl);
         s = hn;
-        t = nt;
       } else {
         path_step(lk, lk.ks.l, lk.ks.d, s, t, bit, cs, cctl);
       }
@@ -198,7 +189,8 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_fast_kernel(DcfFast
   const int n = p.n;
   using Acc = typename std::conditional<BITS == 128, u128, uint64_t>::type;
   // Groups of 64 lanes by grid stride, or taken one at a time per wave
-  // (dyn_per_wg > 0).
+  // (dyn_per_wg > 0).  ItemLoop's loop written out: with the helper the two
+  // <8, *, false, 1> instances changed their register counts (r21).
   const int64_t done = p.num_groups * 64;
   for (int64_t g = p.dyn_per_wg ? take_chunk(&next_chunk, p.dyn_per_wg, p.num_groups, done)
                                 : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -233,8 +225,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_fast_kernel(DcfFast
       for (int j = 0; j < ITEMS; ++j) {
         const int64_t row = k[j] * p.cw_stride + d;
         cw[j] = d + 1 < n ? *reinterpret_cast<const uint4*>(p.cw_seed + row) : make_uint4(0, 0, 0, 0);
-        cc[j] = d + 1 < n ? ((uint32_t)(p.cw_left[row] & 1) | ((uint32_t)(p.cw_right[row] & 1) << 1))
-                          : 0u;
+        cc[j] = d + 1 < n ? cw_ctrl2(p.cw_left, p.cw_right, row) : 0u;
         const dpf_block c = vc.level[d][k[j] * p.vcw_stride];
         if constexpr (BITS == 128) cv[j] = dpf_u128(c); else cv[j] = c.low;
       }
@@ -288,10 +279,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_fast_kernel(DcfFast
         // Step to node d + 1 (distributed_point_function.cc:323-343).
         if (d + 1 < n) {
           Block4 hn = h[ITEMS + j];
-          const uint32_t m = 0u - t[j];
-          hn.w0 ^= cwd[j].x & m; hn.w1 ^= cwd[j].y & m; hn.w2 ^= cwd[j].z & m; hn.w3 ^= cwd[j].w & m;
-          t[j] = (hn.w0 & 1u) ^ (t[j] & ((ccd[j] >> pb[j]) & 1u));
-          hn.w0 &= ~1u;
+          correct_child(hn, t[j], pb[j], cwd[j], ccd[j]);
           s[j] = hn;
         }
       }
@@ -358,7 +346,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void dcf_fast_quad_kernel(Dc
       else acc += (v + tc) & take;
       if (d + 1 < n) {  // step to node d + 1 (distributed_point_function.cc:323-343)
         const uint32_t cs = reinterpret_cast<const uint32_t*>(p.cw_seed + row)[c];
-        const uint32_t cc = (uint32_t)(p.cw_left[row] & 1) | ((uint32_t)(p.cw_right[row] & 1) << 1);
+        const uint32_t cc = cw_ctrl2(p.cw_left, p.cw_right, row);
         hn ^= cs & (0u - t);
         const uint32_t nt = (quad::from_lane0(hn) & 1u) ^ (t & ((cc >> pb) & 1u));
         if (c == 0) hn &= ~1u;
@@ -388,10 +376,10 @@ void launch_dcf_fast(const DcfFastParams& p0, const DcfVcw& vc, hipStream_t s) {
   // 11% slower at the bench size (profiles/r13_ab.txt).
   DcfFastParams p = p0;
   p.num_groups = (p.num_items + 63) / 64;
-  const int blk = block_for(p.num_groups * 64);
-  const dim3 grid(grid_for(p.num_groups * 64, blk)), block(blk);
   // DPF_DCF_DYNAMIC=0: a fixed share of groups per thread (A/B hook).
-  p.dyn_per_wg = dynamic_chunks_per_wg(p.num_groups * 64, (int)grid.x, blk, "DPF_DCF_DYNAMIC");
+  const LaunchShape sh = chunked_shape(p.num_groups * 64, "DPF_DCF_DYNAMIC");
+  const dim3 grid(sh.grid), block(sh.block);
+  p.dyn_per_wg = sh.dyn_per_wg;
   if (p.points_per_key % 64 == 0)
     hipLaunchKernelGGL((dcf_fast_kernel<BITS, XOR, true, 1>), grid, block, 0, s, p, vc);
   else
@@ -493,28 +481,20 @@ extern "C" int dpf_hip_dcf_eval_batch(int64_t num_keys, int64_t points_per_key, 
     DcfVcw vc;
     memset(&vc, 0, sizeof(vc));
     for (int i = 0; i < num_levels; ++i) vc.level[i] = value_correction[i];
-    const bool x = p.xor_mode != 0;
-    switch (desc->bits[0]) {
-      case 8: x ? launch_dcf_fast<8, true>(f, vc, s) : launch_dcf_fast<8, false>(f, vc, s); break;
-      case 16: x ? launch_dcf_fast<16, true>(f, vc, s) : launch_dcf_fast<16, false>(f, vc, s); break;
-      case 32: x ? launch_dcf_fast<32, true>(f, vc, s) : launch_dcf_fast<32, false>(f, vc, s); break;
-      case 64: x ? launch_dcf_fast<64, true>(f, vc, s) : launch_dcf_fast<64, false>(f, vc, s); break;
-      default: x ? launch_dcf_fast<128, true>(f, vc, s) : launch_dcf_fast<128, false>(f, vc, s); break;
-    }
+    with_bits(desc->bits[0], [&](auto bits) {
+      constexpr int B = decltype(bits)::value;
+      p.xor_mode ? launch_dcf_fast<B, true>(f, vc, s) : launch_dcf_fast<B, false>(f, vc, s);
+    });
     HIP_TRY(hipGetLastError());
     return kOk;
   }
-  const int blk = block_for(items);
-  const dim3 grid(grid_for(items, blk)), block(blk);
-  p.dyn_per_wg = dynamic_chunks_per_wg(items, (int)grid.x, blk, "DPF_DCF_DYNAMIC");
+  const LaunchShape sh = chunked_shape(items, "DPF_DCF_DYNAMIC");
+  const dim3 grid(sh.grid), block(sh.block);
+  p.dyn_per_wg = sh.dyn_per_wg;
   if (fast) {
-    switch (desc->bits[0]) {
-      case 8: hipLaunchKernelGGL((dcf_eval_kernel<8, true>), grid, block, 0, s, p, lv, g); break;
-      case 16: hipLaunchKernelGGL((dcf_eval_kernel<16, true>), grid, block, 0, s, p, lv, g); break;
-      case 32: hipLaunchKernelGGL((dcf_eval_kernel<32, true>), grid, block, 0, s, p, lv, g); break;
-      case 64: hipLaunchKernelGGL((dcf_eval_kernel<64, true>), grid, block, 0, s, p, lv, g); break;
-      default: hipLaunchKernelGGL((dcf_eval_kernel<128, true>), grid, block, 0, s, p, lv, g); break;
-    }
+    with_bits(desc->bits[0], [&](auto bits) {
+      hipLaunchKernelGGL((dcf_eval_kernel<decltype(bits)::value, true>), grid, block, 0, s, p, lv, g);
+    });
   } else {
     hipLaunchKernelGGL((dcf_eval_kernel<8, false>), grid, block, 0, s, p, lv, g);
   }

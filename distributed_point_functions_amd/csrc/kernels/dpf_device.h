@@ -1,6 +1,7 @@
 // dpf_device.h -- device-side building blocks shared by the gfx950 kernel
-// translation units (dpf_kernels.hip, dpf_batch.hip, dpf_batch_hh.hip, dpf_dcf.hip): the bank-replicated LDS
-// T-table AES, tree steps (distributed_point_function.cc:315-343,
+// translation units (dpf_kernels.hip, dpf_points.hip, dpf_batch.hip,
+// dpf_batch_hh.hip, dpf_dcf.hip, dpf_mic.hip): the bank-replicated LDS
+// T-table AES, the item loop, tree steps (distributed_point_function.cc:315-343,
 // evaluate_prg_hwy.cc:452-486), leaf conversion/correction (value_type_helpers.h,
 // int_mod_n.h) and the exact wide accumulators of the sum paths.
 // Everything lives in an anonymous namespace: each TU gets private copies of
@@ -94,12 +95,18 @@ __device__ __forceinline__ uint4 cw_u4(const dpf_block& c) {
                     (uint32_t)(c.high >> 32));
 }
 
+// Level j's control corrections as one word (correct_child's cctl): bit 0 for
+// the left child, bit 1 for the right.
+__device__ __forceinline__ uint32_t cw_ctrl2(const uint8_t* l, const uint8_t* r, int64_t j) {
+  return (uint32_t)(l[j] & 1) | ((uint32_t)(r[j] & 1) << 1);
+}
+
 __device__ __forceinline__ void fill_cws(LdsImage& lds, const dpf_block* cw_seed,
                                          const uint8_t* cw_left, const uint8_t* cw_right,
                                          int num_levels) {
   for (int i = threadIdx.x; i < num_levels; i += blockDim.x) {
     lds.cw_seed[i] = cw_u4(cw_seed[i]);
-    lds.cw_ctrl[i] = (uint32_t)(cw_left[i] & 1) | ((uint32_t)(cw_right[i] & 1) << 1);
+    lds.cw_ctrl[i] = cw_ctrl2(cw_left, cw_right, i);
   }
 }
 
@@ -286,6 +293,28 @@ __device__ __forceinline__ int64_t take_chunk(int* counter, int64_t per_wg, int6
   return c < per_wg && g < chunks ? g * 64 + (int64_t)(threadIdx.x & 63) : done;
 }
 
+// The item loop of the kernels launched with chunked_shape (dpf_runtime.h):
+//   for (int64_t u = items.first(); u < n; u = items.next(u))
+// takes the items by grid stride (per_wg == 0), or 64 at a time per wave
+// through take_chunk (per_wg > 0: the launch's `chunks` chunks of 64 items,
+// per_wg of them per workgroup).  `done` is what a wave gets once its
+// workgroup's chunks are used up: a value that fails the loop's condition.  A
+// chunk cut off by the condition is the range's last, after which no lane
+// takes more.  `counter` is a __shared__ int of the kernel, zeroed before the
+// barrier that precedes the loop.
+struct ItemLoop {
+  int* counter;
+  int64_t per_wg, chunks, done;
+  __device__ __forceinline__ int64_t first() const {
+    return per_wg ? take_chunk(counter, per_wg, chunks, done)
+                  : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  }
+  __device__ __forceinline__ int64_t next(int64_t u) const {
+    return per_wg ? take_chunk(counter, per_wg, chunks, done)
+                  : u + (int64_t)gridDim.x * blockDim.x;
+  }
+};
+
 // Stamps of the clock probe: wave-uniform (wave 0 of the workgroup), two
 // reads per workgroup, so the probe costs nothing measurable in a launch of
 // milliseconds (MI355X_MICROARCH.md: in-kernel clock = delta s_memtime /
@@ -362,19 +391,20 @@ __device__ __forceinline__ Block4 add_small(Block4 s, uint32_t j) {
   return Block4{(uint32_t)nlo, (uint32_t)(nlo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
 }
 
-// One tree step for a uniformly chosen child: seed/control correction and
-// control-bit extraction in the order of distributed_point_function.cc:323-343.
-__device__ __forceinline__ void child_step(const LdsLookup& lk, KeyRef rk, Block4 s,
-                                           uint32_t t, uint32_t dir, uint4 cs, uint32_t cctl,
-                                           Block4& out, uint32_t& tout) {
-  Block4 h = dpf_aes::mmo_hash(s, lk, UniformRK{rk});
-  uint32_t m = 0u - t;
+// Seed and control-bit correction of a hashed child
+// (distributed_point_function.cc:323-343): h is the hash of the parent's seed
+// under the key of direction `dir`, t the parent's control bit; cs and cctl
+// are the level's correction seed and packed control pair (cw_ctrl2).  Leaves
+// the child's seed in h and its control bit in t.  The step helpers below
+// (children_step, children_step_x2, path_step) keep it written out: through
+// this function the expand kernels' code changed, and the registers of 20
+// expand_kernel instances (r21).
+__device__ __forceinline__ void correct_child(Block4& h, uint32_t& t, uint32_t dir, uint4 cs,
+                                              uint32_t cctl) {
+  const uint32_t m = 0u - t;
   h.w0 ^= cs.x & m; h.w1 ^= cs.y & m; h.w2 ^= cs.z & m; h.w3 ^= cs.w & m;
-  uint32_t nt = h.w0 & 1u;
+  t = (h.w0 & 1u) ^ (t & ((cctl >> dir) & 1u));
   h.w0 &= ~1u;
-  nt ^= t & ((cctl >> dir) & 1u);
-  out = h;
-  tout = nt;
 }
 
 // Both children of one node: two interleaved MMO hashes (left key, right key).
@@ -1150,15 +1180,10 @@ __device__ __forceinline__ void path_step2(const LdsLookup& lk, KeyRef rkl,
                                            uint4 cs, uint32_t cctl) {
   Block4 h0 = s0, h1 = s1;
   dpf_aes::mmo_hash2(h0, h1, lk, SelectRK{rkl, rkd, 0u - b0}, SelectRK{rkl, rkd, 0u - b1});
-  uint32_t m0 = 0u - t0, m1 = 0u - t1;
-  h0.w0 ^= cs.x & m0; h0.w1 ^= cs.y & m0; h0.w2 ^= cs.z & m0; h0.w3 ^= cs.w & m0;
-  h1.w0 ^= cs.x & m1; h1.w1 ^= cs.y & m1; h1.w2 ^= cs.z & m1; h1.w3 ^= cs.w & m1;
-  uint32_t n0 = (h0.w0 & 1u) ^ (t0 & ((cctl >> b0) & 1u));
-  uint32_t n1 = (h1.w0 & 1u) ^ (t1 & ((cctl >> b1) & 1u));
-  h0.w0 &= ~1u;
-  h1.w0 &= ~1u;
-  s0 = h0; t0 = n0;
-  s1 = h1; t1 = n1;
+  correct_child(h0, t0, b0, cs, cctl);
+  correct_child(h1, t1, b1, cs, cctl);
+  s0 = h0;
+  s1 = h1;
 }
 
 

@@ -43,7 +43,7 @@ struct MicWalkParams {
   const uint8_t* cw_right;
   dpf_block* scratch;              // [gate][|U|]
   RoundKeys rkl, rkd, rkv;
-  int64_t dyn_per_wg;              // take_chunk's per_wg (0: grid stride)
+  int64_t dyn_per_wg;              // ItemLoop's per_wg (0: grid stride)
 };
 
 struct MicVcw {
@@ -62,19 +62,15 @@ template <bool UNIFORM>
 __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void mic_walk_kernel(MicWalkParams p,
                                                                          MicVcw vc) {
   __shared__ LdsImage lds;
-  __shared__ int next_chunk;   // take_chunk (dpf_device.h)
+  __shared__ int next_chunk;   // ItemLoop (dpf_device.h)
   fill_tables(lds.tab);
   if (threadIdx.x == 0) next_chunk = 0;
   __syncthreads();
   const LdsLookup lk = make_lookup(lds, KeySet{key_ref(p.rkl), KeyRef{}, key_ref(p.rkv), key_ref(p.rkd)});
   const int n = p.n;
   const u128 mask = ((u128)1 << n) - 1;   // n <= 127
-  const int64_t done = p.num_groups * 64;
-  for (int64_t g = p.dyn_per_wg ? take_chunk(&next_chunk, p.dyn_per_wg, p.num_groups, done)
-                                : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       (g >> 6) < p.num_groups;
-       g = p.dyn_per_wg ? take_chunk(&next_chunk, p.dyn_per_wg, p.num_groups, done)
-                        : g + (int64_t)gridDim.x * blockDim.x) {
+  const ItemLoop items{&next_chunk, p.dyn_per_wg, p.num_groups, p.num_groups * 64};
+  for (int64_t g = items.first(); (g >> 6) < p.num_groups; g = items.next(g)) {
     const bool valid = g < p.num_items;
     const int64_t u = valid ? g : p.num_items - 1;
     int64_t k = u / p.num_offsets;
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void mic_walk_kernel(MicWalk
     auto load_level = [&](int d) {
       const int64_t row = k * p.cw_stride + d;
       cw = d + 1 < n ? *reinterpret_cast<const uint4*>(p.cw_seed + row) : make_uint4(0, 0, 0, 0);
-      cc = d + 1 < n ? ((uint32_t)(p.cw_left[row] & 1) | ((uint32_t)(p.cw_right[row] & 1) << 1)) : 0u;
+      cc = d + 1 < n ? cw_ctrl2(p.cw_left, p.cw_right, row) : 0u;
       cv = dpf_u128(vc.level[d][k]);
     };
     load_level(0);
@@ -120,10 +116,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void mic_walk_kernel(MicWalk
       acc += (block_u128(h[0]) + tc) & take;
       if (d + 1 < n) {  // step to node d + 1 (distributed_point_function.cc:323-343)
         Block4 hn = h[1];
-        const uint32_t m = 0u - t;
-        hn.w0 ^= cwd.x & m; hn.w1 ^= cwd.y & m; hn.w2 ^= cwd.z & m; hn.w3 ^= cwd.w & m;
-        t = (hn.w0 & 1u) ^ (t & ((ccd >> xb) & 1u));
-        hn.w0 &= ~1u;
+        correct_child(hn, t, xb, cwd, ccd);
         s = hn;
       }
     }
@@ -221,10 +214,10 @@ extern "C" int dpf_hip_mic_eval_batch(
   w.rkd = xor_keys(w.rkl, expand_key(key_right));
   w.rkv = expand_key(key_value);
   {
-    const int blk = block_for(w.num_groups * 64);
-    const dim3 grid(grid_for(w.num_groups * 64, blk)), block(blk);
     // The DCF kernel's hook: DPF_DCF_DYNAMIC=0 gives a fixed share per thread.
-    w.dyn_per_wg = dynamic_chunks_per_wg(w.num_groups * 64, (int)grid.x, blk, "DPF_DCF_DYNAMIC");
+    const LaunchShape sh = chunked_shape(w.num_groups * 64, "DPF_DCF_DYNAMIC");
+    const dim3 grid(sh.grid), block(sh.block);
+    w.dyn_per_wg = sh.dyn_per_wg;
     if (num_offsets % 64 == 0)
       hipLaunchKernelGGL((mic_walk_kernel<true>), grid, block, 0, s, w, vc);
     else

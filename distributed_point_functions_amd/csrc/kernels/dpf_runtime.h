@@ -1,13 +1,16 @@
 // dpf_runtime.h -- host-side plumbing shared by the kernel translation units:
 // absl status codes, the thread-local last-error message
 // behind dpf_hip_last_error() (defined in dpf_kernels.hip), the launch hooks,
-// and the launch-shape helpers (dpf_kernels.hip, dpf_expand_plan.hip).
+// the launch-shape helpers (block_for, grid_for, chunked_shape: dpf_kernels.hip;
+// the expand plan: dpf_expand_plan.hip) and with_bits, the dispatch on an
+// integer leaf's width.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include <string>
+#include <type_traits>
 
 #include "../../../include/dpf_hip.h"
 
@@ -45,10 +48,29 @@ int max_subtree_depth();                       // files that include no device h
 int block_for(int64_t work_items);             // threads per workgroup: kBlock, or fewer
                                                // (multiple of 64) to spread a small launch over more CUs
 int grid_for(int64_t work_items, int block);   // workgroups of `block` threads, <= one per CU
-// Chunks of 64 items per workgroup for take_chunk (dpf_device.h), or 0 (a
-// fixed share per thread): dynamic when the launch gives every wave at least
-// 4 chunks and `env` is not "0" (A/B and test hooks, read per launch).
-int64_t dynamic_chunks_per_wg(int64_t items, int grid, int block, const char* env);
+// Shape of a launch whose kernel takes its items through ItemLoop
+// (dpf_device.h): block_for / grid_for of `items`, and dyn_per_wg, the chunks
+// of 64 items per workgroup, or 0 (a fixed share per thread).  Dynamic when
+// the launch gives every wave at least 4 chunks and the hook `hook` is not
+// "0" (A/B and test hooks, read per launch); dpf_hip_last_dynamic_chunks
+// reports dyn_per_wg.
+struct LaunchShape {
+  int block, grid;
+  int64_t dyn_per_wg;
+};
+LaunchShape chunked_shape(int64_t items, const char* hook);
+// f(std::integral_constant<int, B>) for the leaf width B = `bits` of 8, 16, 32
+// or 64, else 128.
+template <class F>
+auto with_bits(int bits, F&& f) {
+  switch (bits) {
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    default: return f(std::integral_constant<int, 128>{});
+  }
+}
 // Chunk schedule of a full-domain expand launch of `num_items` subtrees of
 // depth S, each k0 levels below its start seed, on `cus` workgroups of 16
 // waves (dpf_expand_plan.hip, "Who takes which chunk"; reads the DPF_OCTET_*

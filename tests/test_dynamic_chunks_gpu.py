@@ -3,7 +3,7 @@ batch kernels on an MI355X.
 
 Every AES-bound launcher hands its waves 64-item chunks from a per-workgroup
 counter once the launch holds 4 chunks per wave of the chip
-(dynamic_chunks_per_wg): T = 4 * CUs * 1024 items, 2^20 on 256 CUs.  Below T
+(chunked_shape, dpf_runtime.h): T = 4 * CUs * 1024 items, 2^20 on 256 CUs.  Below T
 the same kernels run a grid-stride loop, and that is all the rest of the suite
 reaches for these launchers.  Each case here is the smallest shape just above
 T, with a chunk count that is no multiple of the grid, so that the last
