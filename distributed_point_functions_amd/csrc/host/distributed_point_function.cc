@@ -874,6 +874,164 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateShardToDevice(
 }
 
 namespace {
+// The streamed database fold expands the domain slab by slab into scratch:
+// at most this many bytes of share vector at a time (a power of two of
+// elements; 2^25 uint64_t).  DPF_DOT_SLAB_LOG (read per call; test hook) sets
+// the slab's log2 element count instead.
+constexpr int64_t kDotSlabBytes = int64_t{256} << 20;
+constexpr int kDotMaxSlabLevels = 20;   // at most 2^20 slabs per call
+}  // namespace
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateDotToDevice(
+    const DpfKey& key, int hierarchy_level, int64_t shard, int64_t num_shards,
+    const void* device_db, int64_t db_bytes, int64_t record_words, void* device_out,
+    int64_t out_bytes, void* stream) const {
+  const int H = static_cast<int>(parameters().size());
+  if (hierarchy_level < 0 || hierarchy_level >= H)
+    return InvalidArgumentError(
+        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+  if (num_shards < 1 || (num_shards & (num_shards - 1)) || shard < 0 || shard >= num_shards)
+    return InvalidArgumentError("num_shards must be a power of two and 0 <= shard < num_shards");
+  int k = 0;
+  while ((int64_t{1} << k) < num_shards) ++k;
+  const int stop_level = hierarchy_to_tree()[hierarchy_level];
+  if (k > stop_level) return InvalidArgumentError("more shards than subtrees at this level");
+  const int log_domain_size = parameters()[hierarchy_level].log_domain_size();
+  if (log_domain_size - k > 62)
+    return InvalidArgumentError(
+        "Output size would be larger than 2**62. Please evaluate fewer hierarchy levels at once.");
+  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
+    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
+  const int cepb = corrected_elements_per_block(hierarchy_level);
+  const int W = static_cast<int>(record_words);
+  const int L = stop_level - k;                       // tree levels below the shard's root
+  const int64_t rows = (int64_t{1} << L) * cepb;      // records of this shard
+  const int64_t esz = f.packed_size;
+  if (rows > (std::numeric_limits<int64_t>::max() / (esz * W)) || db_bytes < rows * esz * W)
+    return InvalidArgumentError("database buffer too small");
+  if (out_bytes < esz * W) return InvalidArgumentError("device output buffer too small");
+  if (!device_db || !device_out)
+    return InvalidArgumentError("`device_db` and `device_out` must not be null");
+  DPF_RETURN_IF_ERROR(validator_->ValidateDpfKey(key));
+  const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
+  const int workspace_bytes = dpf_hip_expand_dot_workspace_bytes(&desc, W);
+  if (workspace_bytes < 0) return UnimplementedError(dpf_hip_last_error());
+  DPF_ASSIGN_OR_RETURN(std::vector<uint128> vcw, ValueCorrectionLeaves(key, hierarchy_level));
+
+  // Fused (no share vector), or streamed: the shard cut into 2^j slabs whose
+  // share vectors fit the scratch bound, each expanded by dpf_hip_expand and
+  // folded by dpf_hip_dot_rows.
+  const bool fused = dpf_hip_expand_dot_fused(&desc, W) != 0;
+  int j = 0;
+  if (!fused) {
+    int slab_log = 0;
+    while ((int64_t{2} << slab_log) * esz <= kDotSlabBytes) ++slab_log;
+    if (const char* v = std::getenv("DPF_DOT_SLAB_LOG"); v && *v) slab_log = std::atoi(v);
+    int64_t slab_rows = int64_t{1} << std::min(std::max(slab_log, 0), 62);
+    if (slab_rows < cepb) slab_rows = cepb;
+    while ((rows >> j) > slab_rows) ++j;
+    if (j > kDotMaxSlabLevels)
+      return InvalidArgumentError("the database fold would take more than 2**20 slabs");
+  }
+  const int64_t slabs = int64_t{1} << j;
+  const int64_t slab_rows = rows >> j;
+
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  // One packed image, as EvaluateShardToDevice: a root, party and path per
+  // slab, the value correction and both correction-word ranges.
+  const dpf_block root = ToBlock(FromProtoBlock(key.seed()));
+  const uint8_t party = static_cast<uint8_t>(key.party() & 1);
+  std::vector<dpf_block> roots(slabs, root), paths(slabs);
+  std::vector<uint8_t> parties(slabs, party);
+  for (int64_t i = 0; i < slabs; ++i)
+    paths[i] = ToBlock((static_cast<uint128>(shard) << j) | static_cast<uint128>(i));
+  std::vector<dpf_block> vcw_blocks(vcw.size());
+  for (size_t i = 0; i < vcw.size(); ++i) vcw_blocks[i] = ToBlock(vcw[i]);
+  PackedUploads& up = s->shard_alt ? s->packed_alt : s->packed;
+  s->shard_alt = !s->shard_alt;
+  DPF_RETURN_IF_ERROR(up.Reset());
+  const size_t o_seed = up.Add(roots.data(), roots.size());
+  const size_t o_ctrl = up.Add(parties.data(), parties.size());
+  const size_t o_path = up.Add(paths.data(), paths.size());
+  const size_t o_vcw = up.Add(vcw_blocks.data(), vcw_blocks.size());
+  const PackedCws o_top = AddCorrectionWords(key, 0, k + j, up);
+  const PackedCws o_cw = AddCorrectionWords(key, k + j, stop_level, up);
+  DPF_RETURN_IF_ERROR(up.Commit(stream));
+  dpf_block* seed = up.Ptr<dpf_block>(o_seed);
+  uint8_t* ctrl = up.Ptr<uint8_t>(o_ctrl);
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  if (k + j > 0) {
+    // The slab roots: the top k + j tree bits walked in place, one call.
+    HIP_RETURN_IF_ERROR(dpf_hip_eval_paths(slabs, k + j, seed, ctrl, up.Ptr<dpf_block>(o_path),
+                                           up.Ptr<dpf_block>(o_top.seed), up.Ptr<uint8_t>(o_top.left),
+                                           up.Ptr<uint8_t>(o_top.right), &kl, &kr, seed, ctrl,
+                                           stream));
+  }
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace, workspace_bytes, stream));
+  if (fused) {
+    HIP_RETURN_IF_ERROR(dpf_hip_expand_dot(
+        1, seed, ctrl, L, up.Ptr<dpf_block>(o_cw.seed), up.Ptr<uint8_t>(o_cw.left),
+        up.Ptr<uint8_t>(o_cw.right), &kl, &kr, &kv, &desc, cepb, up.Ptr<dpf_block>(o_vcw), party,
+        device_db, W, s->workspace.get(), device_out, stream));
+  } else {
+    DPF_RETURN_IF_ERROR(s->out.Reserve(static_cast<size_t>(slab_rows * esz)));
+    for (int64_t i = 0; i < slabs; ++i) {
+      HIP_RETURN_IF_ERROR(dpf_hip_expand(
+          1, seed + i, ctrl + i, L - j, up.Ptr<dpf_block>(o_cw.seed), up.Ptr<uint8_t>(o_cw.left),
+          up.Ptr<uint8_t>(o_cw.right), &kl, &kr, &kv, &desc, cepb, up.Ptr<dpf_block>(o_vcw), party,
+          s->out.get(), stream));
+      HIP_RETURN_IF_ERROR(dpf_hip_dot_rows(
+          slab_rows, W, &desc, s->out.get(),
+          static_cast<const char*>(device_db) + i * slab_rows * esz * W, i > 0,
+          s->workspace.get(), device_out, stream));
+    }
+  }
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  DPF_RETURN_IF_ERROR(up.MarkUsed(stream));
+  return record_words;
+}
+
+StatusOr<std::vector<uint8_t>> DistributedPointFunction::EvaluateDotPacked(
+    const DpfKey& key, int hierarchy_level, const void* device_db, int64_t db_bytes,
+    int64_t record_words, const ValueType* requested_type) const {
+  const int H = static_cast<int>(parameters().size());
+  if (hierarchy_level < 0 || hierarchy_level >= H)
+    return InvalidArgumentError(
+        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+  if (requested_type) {
+    DPF_ASSIGN_OR_RETURN(bool eq, dpf_internal::ValueTypesAreEqual(
+                                      *requested_type, parameters()[hierarchy_level].value_type()));
+    if (!eq) return InvalidArgumentError("Value type T doesn't match parameters at `hierarchy_level`");
+  }
+  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
+    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  const size_t bytes = static_cast<size_t>(record_words) * flat_[hierarchy_level].packed_size;
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);
+  // Checked before the result buffer is allocated: host errors touch no device.
+  if (!device_db) return InvalidArgumentError("`device_db` and `device_out` must not be null");
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  if (dpf_hip_expand_dot_workspace_bytes(&desc, static_cast<int>(record_words)) < 0)
+    return UnimplementedError(dpf_hip_last_error());
+  const int cepb = corrected_elements_per_block(hierarchy_level);
+  const int64_t rows = (int64_t{1} << hierarchy_to_tree()[hierarchy_level]) * cepb;
+  if (parameters()[hierarchy_level].log_domain_size() > 62 ||
+      db_bytes / static_cast<int64_t>(bytes) < rows)
+    return InvalidArgumentError("database buffer too small");
+  DPF_RETURN_IF_ERROR(validator_->ValidateDpfKey(key));
+  DPF_RETURN_IF_ERROR(s->gathered.Reserve(bytes));
+  DPF_RETURN_IF_ERROR(EvaluateDotToDevice(key, hierarchy_level, 0, 1, device_db, db_bytes,
+                                          record_words, s->gathered.get(),
+                                          static_cast<int64_t>(bytes), nullptr)
+                          .status());
+  std::vector<uint8_t> out(bytes);
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), s->gathered.get(), bytes, nullptr));
+  return out;
+}
+
+namespace {
 // Host-phase timing of EvaluateAt, printed at exit when DPF_HOST_TIMING is
 // set (the first 10 calls, allocations and page-locked buffers, not counted):
 // checks = the fused domain check + path / block-index pass over the points,

@@ -238,6 +238,40 @@ class PyDpf {
     }
     return py::make_tuple(n, Ser(ctx));
   }
+  int64_t EvaluateDotToDevice(const py::bytes& key_bytes, int level, int64_t shard,
+                              int64_t num_shards, uintptr_t db_ptr, int64_t db_bytes,
+                              int64_t record_words, uintptr_t out_ptr, int64_t out_bytes,
+                              uintptr_t stream) {
+    DpfKey key = Parse<DpfKey>(key_bytes);
+    py::gil_scoped_release nogil;
+    auto r = dpf_->EvaluateDotToDevice(key, level, shard, num_shards,
+                                       reinterpret_cast<const void*>(db_ptr), db_bytes,
+                                       record_words, reinterpret_cast<void*>(out_ptr), out_bytes,
+                                       reinterpret_cast<void*>(stream));
+    if (!r.ok()) {
+      py::gil_scoped_acquire g;
+      throw StatusError(r.status());
+    }
+    return *r;
+  }
+  py::array_t<uint8_t> EvaluateDot(const py::bytes& key_bytes, int level, uintptr_t db_ptr,
+                                   int64_t db_bytes, int64_t record_words) {
+    DpfKey key = Parse<DpfKey>(key_bytes);
+    std::vector<uint8_t> out;
+    {
+      py::gil_scoped_release nogil;
+      auto r = dpf_->EvaluateDotPacked(key, level, reinterpret_cast<const void*>(db_ptr), db_bytes,
+                                       record_words);
+      if (!r.ok()) {
+        py::gil_scoped_acquire g;
+        throw StatusError(r.status());
+      }
+      out = std::move(*r);
+    }
+    py::array_t<uint8_t> a(static_cast<py::ssize_t>(out.size()));
+    if (!out.empty()) std::memcpy(a.mutable_data(), out.data(), out.size());
+    return a;
+  }
   py::array_t<uint8_t> EvaluateAt(const py::bytes& key_bytes, int level,
                                   const py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& points,
                                   const py::object& vt) {
@@ -592,6 +626,8 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_until", &PyDpf::EvaluateUntil)
       .def("evaluate_until_to_device", &PyDpf::EvaluateUntilToDevice)
       .def("evaluate_shard_to_device", &PyDpf::EvaluateShardToDevice)
+      .def("evaluate_dot_to_device", &PyDpf::EvaluateDotToDevice)
+      .def("evaluate_dot", &PyDpf::EvaluateDot)
       .def("evaluate_at", &PyDpf::EvaluateAt)
       .def("evaluate_at_ctx", &PyDpf::EvaluateAtCtx)
       .def("evaluate_at_batch", &PyDpf::EvaluateAtBatch)

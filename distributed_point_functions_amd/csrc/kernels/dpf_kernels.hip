@@ -30,6 +30,7 @@
 
 #include "../../../include/dpf_hip.h"
 #include "dpf_device.h"
+#include "dpf_dot.h"
 #include "dpf_runtime.h"
 
 namespace dpf_rt {
@@ -195,6 +196,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_kernel(ExpandPar
     }
   }
   if constexpr (SCHED) ClockStamp::exits(p.clock);
+  if constexpr (HasFinish<Leaf>::value) leaf.finish();
 }
 
 // Octet form of expand_kernel for integer leaves that fill whole 16-byte
@@ -404,6 +406,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(Exp
     }
   }
   stamp.end(p.clock);
+  if constexpr (HasFinish<Leaf>::value) leaf.finish();
 }
 
 // Latency mode of full-domain expansion for small trees (r15; config 1 and
@@ -426,6 +429,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_octet_kernel(Exp
 // registers before a barrier and rewritten after it.
 template <class Leaf> struct IsFastInt : std::false_type {};
 template <int BITS, bool XOR> struct IsFastInt<FastIntLeaf<BITS, XOR>> : std::true_type {};
+template <int BITS, bool XOR> struct IsFastInt<DotLeaf<BITS, XOR>> : std::true_type {};
 template <class Leaf>
 __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_small_kernel(ExpandParams p, Leaf leaf) {
   __shared__ LdsImage lds;
@@ -518,6 +522,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_small_kernel(Exp
                   lds.cw_ctrl[lvl], c0, t0, c1, t1);
     leaf.emit2(lk, lk.ks.v, c0, t0, c1, t1, leaf0 + 2 * tid, p.out);
   }
+  if constexpr (HasFinish<Leaf>::value) leaf.finish();
 }
 
 // Leaf policy of the tree-top pass (expand_top, below): expand_small_kernel's
@@ -859,6 +864,7 @@ bool has_schedule(const ExpandParams& p) {
 // IntModN<uint32_t> (the half's four leaves hashed as two ILP4 groups).
 template <class Leaf> struct HasOctet : std::false_type {};
 template <int BITS, bool XOR> struct HasOctet<FastIntLeaf<BITS, XOR>> : std::true_type {};
+template <int BITS, bool XOR> struct HasOctet<DotLeaf<BITS, XOR>> : std::true_type {};
 template <> struct HasOctet<SwarLeaf> : std::true_type {};
 template <> struct HasOctet<Mod32Leaf<2>> : std::true_type {};
 
@@ -1108,12 +1114,14 @@ int dpf_hip_eval_paths(int64_t num_seeds, int num_levels, const dpf_block* seeds
   return kOk;
 }
 
-int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t* control_in,
-                   int num_levels, const dpf_block* cw_seed, const uint8_t* cw_left,
-                   const uint8_t* cw_right, const dpf_aes_key* key_left,
-                   const dpf_aes_key* key_right, const dpf_aes_key* key_value,
-                   const dpf_value_desc* desc, int elements_per_leaf,
-                   const dpf_block* value_correction, int party, void* out, void* stream) {
+// Argument checks and launch parameters dpf_hip_expand and dpf_hip_expand_dot
+// share (`out` apart).
+static int expand_params(int64_t num_starts, const dpf_block* seeds_in, const uint8_t* control_in,
+                         int num_levels, const dpf_block* cw_seed, const uint8_t* cw_left,
+                         const uint8_t* cw_right, const dpf_aes_key* key_left,
+                         const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                         const dpf_value_desc* desc, int elements_per_leaf,
+                         const dpf_block* value_correction, ExpandParams* out) {
   int st = validate_desc(desc);
   if (st) return st;
   if (num_starts < 0 || num_levels < 0 || num_levels > 62)
@@ -1122,7 +1130,7 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
     return fail(kInvalidArgument, "elements_per_leaf must be in [1, elements_per_block]");
   if (num_starts == 0) return kOk;
   if (!seeds_in || !control_in || !key_left || !key_right || !key_value || !value_correction ||
-      !out || (num_levels > 0 && (!cw_seed || !cw_left || !cw_right)))
+      (num_levels > 0 && (!cw_seed || !cw_left || !cw_right)))
     return fail(kInvalidArgument, "NULL pointer");
   if (num_starts > (INT64_MAX >> num_levels))
     return fail(kInvalidArgument, "expansion too large");
@@ -1136,12 +1144,29 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
   p.cw_seed = cw_seed;
   p.cw_left = cw_left;
   p.cw_right = cw_right;
-  p.out = (char*)out;
   p.rkl = expand_key(key_left);
   p.rkr = expand_key(key_right);
   p.rkv = expand_key(key_value);
   p.rkd = xor_keys(p.rkl, p.rkr);
   p.clock = dpf_rt::g_clock_acc.load(std::memory_order_relaxed);
+  *out = p;
+  return kOk;
+}
+
+int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t* control_in,
+                   int num_levels, const dpf_block* cw_seed, const uint8_t* cw_left,
+                   const uint8_t* cw_right, const dpf_aes_key* key_left,
+                   const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                   const dpf_value_desc* desc, int elements_per_leaf,
+                   const dpf_block* value_correction, int party, void* out, void* stream) {
+  ExpandParams p{};
+  if (int st = expand_params(num_starts, seeds_in, control_in, num_levels, cw_seed, cw_left,
+                             cw_right, key_left, key_right, key_value, desc, elements_per_leaf,
+                             value_correction, &p))
+    return st;
+  if (num_starts == 0) return kOk;
+  if (!out) return fail(kInvalidArgument, "NULL pointer");
+  p.out = (char*)out;
   hipStream_t s = (hipStream_t)stream;
   if (fast_int(desc))
     return expand_fast(p, desc, value_correction, desc->elements_per_block, party,
@@ -1172,6 +1197,57 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
   }
   return dispatch_expand(p, make_generic_leaf(desc, value_correction, party, elements_per_leaf),
                          true, s);
+}
+
+// Full-domain expansion folded into the database at the leaves: the launch
+// plan, kernels and chunk schedule are dpf_hip_expand's, with DotLeaf in
+// FastIntLeaf's place; then the workgroups' partials are folded into `out`.
+int dpf_hip_expand_dot(int64_t num_starts, const dpf_block* seeds_in, const uint8_t* control_in,
+                       int num_levels, const dpf_block* cw_seed, const uint8_t* cw_left,
+                       const uint8_t* cw_right, const dpf_aes_key* key_left,
+                       const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                       const dpf_value_desc* desc, int elements_per_leaf,
+                       const dpf_block* value_correction, int party, const void* db,
+                       int record_words, void* workspace, void* out, void* stream) {
+  ExpandParams p{};
+  if (int st = expand_params(num_starts, seeds_in, control_in, num_levels, cw_seed, cw_left,
+                             cw_right, key_left, key_right, key_value, desc, elements_per_leaf,
+                             value_correction, &p))
+    return st;
+  int words = 0, xor_type = 0;
+  if (int st = dot_type(desc, &words, &xor_type)) return st;
+  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
+    return fail(kInvalidArgument, "record_words must be in [1, 1024]");
+  if (!db || !workspace || !out) return fail(kInvalidArgument, "NULL pointer");
+  if (!dpf_hip_expand_dot_fused(desc, record_words))
+    return fail(kUnimplemented,
+                "no fused kernel for this record width: dpf_hip_expand into scratch, then "
+                "dpf_hip_dot_rows");
+  if (num_cus() > kDotMaxGroups) return fail(kInternal, "more workgroups than partial rows");
+  hipStream_t s = (hipStream_t)stream;
+  if (num_starts == 0) {   // an empty sum
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)words * 8, s));
+    return kOk;
+  }
+  const int store_bytes = elements_per_leaf * desc->bits[0] / 8;
+  char* ws = static_cast<char*>(workspace);
+  const char* d = static_cast<const char*>(db);
+  const int E = desc->elements_per_block;
+  int st;
+  if (desc->bits[0] == 128)
+    st = dispatch_expand(p, DotLeaf<128, true>{{value_correction, E, party, store_bytes, {}}, d, ws, 0, 0},
+                         true, s);
+  else if (xor_type)
+    st = dispatch_expand(p, DotLeaf<64, true>{{value_correction, E, party, store_bytes, {}}, d, ws, 0, 0},
+                         store_bytes == 16, s);
+  else
+    st = dispatch_expand(p, DotLeaf<64, false>{{value_correction, E, party, store_bytes, {}}, d, ws, 0, 0},
+                         store_bytes == 16, s);
+  if (st) return st;
+  const char* k = dpf_rt::g_last_expand;
+  g_last_dot = k[0] == 's' ? "small" : (k[0] == 'o' ? "octet" : "pair");
+  // The kernel's first workgroup wrote the number of partial rows.
+  return launch_dot_fold(words, xor_type, 0, workspace, out, s);
 }
 
 int dpf_hip_count_out_of_range(int64_t n, const dpf_block* points, int log_domain_size,

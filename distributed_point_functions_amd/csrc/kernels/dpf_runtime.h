@@ -105,6 +105,16 @@ int validate_desc(const dpf_value_desc* d);    // kOk or the failure code
 int packed_size(const dpf_value_desc* d);      // bytes of one packed element
 bool fast_int(const dpf_value_desc* d);        // one plain/XOR integer leaf, direct, b == 1
 
+// The dot calls (dpf_dot.hip).  dot_type: kOk and the uint64 words of one
+// element and whether the group is XOR for uint64_t, XorWrapper<uint64_t> and
+// XorWrapper<uint128>, else UNIMPLEMENTED.  launch_dot_fold: out[j] (row_words
+// uint64 words) = the group sum of word j of the partial rows the last kernel
+// left in `workspace`, combined with out's old value when `accumulate`.
+extern thread_local const char* g_last_dot;   // dpf_hip_last_dot_kernel
+int dot_type(const dpf_value_desc* d, int* words, int* xor_type);
+int launch_dot_fold(int row_words, int xor_type, int accumulate, const void* workspace, void* out,
+                    hipStream_t s);
+
 // One steady-state heavy-hitters level (dpf_batch_hh.hip): start seeds from
 // the expansion cache or gathered partial evaluations, no path walk, two
 // expanded levels, Tuple/IntModN<uint32_t> values summed over the keys.

@@ -325,6 +325,31 @@ class DistributedPointFunction:
         ctx.ParseFromString(new_ctx)
         return n
 
+    def evaluate_dot_to_device(self, key: pb.DpfKey, hierarchy_level: int, db, record_words: int,
+                               out, shard: int = 0, num_shards: int = 1, stream=None) -> int:
+        """Two-server PIR answer: full-domain evaluation of `key` folded into the
+        database `db` (torch device tensor: this shard's records, row-major,
+        `record_words` words of the value type's width each) without storing
+        the share vector.  Writes `record_words` packed elements into the torch
+        device tensor `out`: sum_i y[i] * db[i][w] mod 2^64 for uint64,
+        XOR_i (y[i] & db[i][w]) for XorWrapper<uint64 / uint128>.  The two
+        parties' (and all shards') results combine with the type's +."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(out.device)
+        return _call(self._impl.evaluate_dot_to_device, key.SerializeToString(),
+                     int(hierarchy_level), int(shard), int(num_shards), db.data_ptr(),
+                     db.numel() * db.element_size(), int(record_words), out.data_ptr(),
+                     out.numel() * out.element_size(), s.cuda_stream)
+
+    def evaluate_dot(self, key: pb.DpfKey, hierarchy_level: int, db, record_words: int):
+        """evaluate_dot_to_device over the whole domain, returned as numpy
+        (uint64 per word; (record_words, 16) bytes for 128-bit words)."""
+        out = _call(self._impl.evaluate_dot, key.SerializeToString(), int(hierarchy_level),
+                    db.data_ptr(), db.numel() * db.element_size(), int(record_words))
+        return _natural(self._parameters[hierarchy_level].value_type, out, int(record_words))
+
     def evaluate_at_batch(self, keys: Sequence[pb.DpfKey], hierarchy_level: int,
                           points: Sequence[int], points_per_key: int, packed: bool = False):
         pts = points if isinstance(points, np.ndarray) else u128_array(points)

@@ -105,9 +105,17 @@ def load(require_gpu: bool = False):
                             ("dpf_hip_last_expand_schedule", [ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_last_dynamic_chunks", [ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_mic_eval_batch",
-                             [I64, I, P, P, P, P, P, I, P, P, I, P, I] + [P] * 11)):
+                             [I64, I, P, P, P, P, P, I, P, P, I, P, I] + [P] * 11),
+                            ("dpf_hip_expand_dot",
+                             [I64, P, P, I, P, P, P, P, P, P, P, I, P, I, P, I, P, P, P]),
+                            ("dpf_hip_dot_rows", [I64, I, P, P, P, I, P, P, P]),
+                            ("dpf_hip_expand_dot_workspace_bytes", [P, I]),
+                            ("dpf_hip_expand_dot_fused", [P, I]),
+                            ("dpf_hip_last_dot_kernel", [])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = types
+        if hasattr(L, "dpf_hip_last_dot_kernel"):
+            L.dpf_hip_last_dot_kernel.restype = ctypes.c_char_p
         _lib = L
     if require_gpu:
         import torch
@@ -134,6 +142,22 @@ def last_points_kernel() -> str:
     """Kernel of this thread's last point evaluation, e.g. "points/ilp4" --
     dispatch diagnostics for the tests."""
     return load().dpf_hip_last_points_kernel().decode()
+
+
+def last_dot_kernel() -> str:
+    """Path of this thread's last dot call: "small", "pair" or "octet" (the
+    fused expand kernel) or "rows" (dot_rows) -- dispatch diagnostics for the
+    tests."""
+    return load().dpf_hip_last_dot_kernel().decode()
+
+
+def dot_workspace_bytes(desc: ValueDesc, record_words: int) -> int:
+    """Bytes of workspace expand_dot / dot_rows need (no GPU needed)."""
+    n = load().dpf_hip_expand_dot_workspace_bytes(ctypes.byref(desc), record_words)
+    if n < 0:
+        raise DpfHipError(12 if 1 <= record_words <= 1024 else 3,
+                          load().dpf_hip_last_error().decode())
+    return n
 
 
 def last_dynamic_chunks() -> int:
@@ -297,6 +321,44 @@ def expand(seeds, ctrl, cw_seed, cw_left, cw_right, keys, desc: ValueDesc, eleme
                            _p(cw_right), ctypes.byref(kl), ctypes.byref(kr), ctypes.byref(kv),
                            ctypes.byref(desc), elements_per_leaf, _p(value_correction), party,
                            _p(out), _stream(stream)))
+    return out
+
+
+def _dot_buffers(desc, record_words, workspace, out, device):
+    import torch
+    esz = load().dpf_hip_packed_element_size(ctypes.byref(desc))
+    if workspace is None:
+        workspace = torch.empty(dot_workspace_bytes(desc, record_words), dtype=torch.uint8,
+                                device=device)
+    if out is None:
+        out = torch.empty(record_words * esz, dtype=torch.uint8, device=device)
+    return workspace, out
+
+
+def expand_dot(seeds, ctrl, cw_seed, cw_left, cw_right, keys, desc: ValueDesc,
+               elements_per_leaf: int, value_correction, party: int, db, record_words: int = 1,
+               workspace=None, out=None, stream=None):
+    """expand() folded into the database `db` at the leaves (no share vector
+    is stored); returns `record_words` packed elements as a uint8 tensor."""
+    L = load(require_gpu=True)
+    workspace, out = _dot_buffers(desc, record_words, workspace, out, seeds.device)
+    kl, kr, kv = (aes_key(k) for k in keys)
+    check(L.dpf_hip_expand_dot(seeds.shape[0], _p(seeds), _p(ctrl), cw_left.shape[0], _p(cw_seed),
+                               _p(cw_left), _p(cw_right), ctypes.byref(kl), ctypes.byref(kr),
+                               ctypes.byref(kv), ctypes.byref(desc), elements_per_leaf,
+                               _p(value_correction), party, _p(db), record_words, _p(workspace),
+                               _p(out), _stream(stream)))
+    return out
+
+
+def dot_rows(num_rows: int, record_words: int, desc: ValueDesc, y, db, accumulate: bool = False,
+             workspace=None, out=None, stream=None):
+    """out[w] (+)= fold of the packed share vector `y` into `db`'s first
+    num_rows records; returns `record_words` packed elements (uint8 tensor)."""
+    L = load(require_gpu=True)
+    workspace, out = _dot_buffers(desc, record_words, workspace, out, db.device)
+    check(L.dpf_hip_dot_rows(num_rows, record_words, ctypes.byref(desc), _p(y), _p(db),
+                             1 if accumulate else 0, _p(workspace), _p(out), _stream(stream)))
     return out
 
 

@@ -218,6 +218,37 @@ class DistributedPointFunction {
   StatusOr<int64_t> EvaluateShardToDevice(int hierarchy_level, int64_t shard, int64_t num_shards,
                                           EvaluationContext& ctx, void* device_out,
                                           int64_t capacity_bytes, void* stream) const;
+  // Two-server PIR: full-domain evaluation folded into a database, without
+  // the share vector ever being stored.  With y = EvaluateUntil<T>(
+  // hierarchy_level, {}, fresh ctx) and `device_db` a row-major device array
+  // of y.size() records of `record_words` words of T's width,
+  //   uint64_t:                       out[w] = sum_i y[i] * db[i][w]  (mod 2^64)
+  //   XorWrapper<uint64_t / uint128>: out[w] = XOR_i (y[i] & db[i][w]);
+  // the two parties' results combine with T's + to beta * db[alpha]
+  // (beta & db[alpha]).  Other value types: UNIMPLEMENTED.  Stateless and
+  // key-based like EvaluateAt(key, ...).  With num_shards > 1 (a power of
+  // two), `device_db` holds only shard `shard`'s y.size() / num_shards
+  // records and the result is that shard's partial; the shards' partials
+  // combine with T's +.  Writes record_words packed elements to `device_out`
+  // on `stream` (asynchronous) and returns record_words.
+  StatusOr<int64_t> EvaluateDotToDevice(const DpfKey& key, int hierarchy_level, int64_t shard,
+                                        int64_t num_shards, const void* device_db,
+                                        int64_t db_bytes, int64_t record_words, void* device_out,
+                                        int64_t out_bytes, void* stream) const;
+  // The unsharded fold returned to the host (packed elements).
+  StatusOr<std::vector<uint8_t>> EvaluateDotPacked(const DpfKey& key, int hierarchy_level,
+                                                   const void* device_db, int64_t db_bytes,
+                                                   int64_t record_words,
+                                                   const ValueType* requested_type = nullptr) const;
+  template <typename T>
+  StatusOr<std::vector<T>> EvaluateDot(const DpfKey& key, int hierarchy_level,
+                                       const void* device_db, int64_t db_bytes,
+                                       int64_t record_words) const {
+    ValueType t = ToValueType<T>();
+    auto packed = EvaluateDotPacked(key, hierarchy_level, device_db, db_bytes, record_words, &t);
+    if (!packed.ok()) return packed.status();
+    return Unpack<T>(hierarchy_level, *packed);
+  }
   StatusOr<std::vector<uint8_t>> EvaluateAtPacked(const DpfKey& key, int hierarchy_level,
                                                   Span<const uint128> evaluation_points,
                                                   EvaluationContext* ctx,

@@ -185,6 +185,55 @@ int dpf_hip_expand(int64_t num_starts, const dpf_block* seeds_in, const uint8_t*
                    const dpf_value_desc* desc, int elements_per_leaf,
                    const dpf_block* value_correction, int party, void* out, void* stream);
 
+/* ---- full-domain expansion folded into a database (two-server PIR) ---------
+ * No reference counterpart: the reference returns the share vector and leaves
+ * the fold to its caller.  With y[0 .. n) what dpf_hip_expand writes for the
+ * same arguments (n = (num_starts << num_levels) * elements_per_leaf) and `db`
+ * a row-major device array of n records of record_words words of the value
+ * type's width,
+ *   uint64_t:                        out[w] = sum_i y[i] * db[i*W + w] (mod 2^64)
+ *   XorWrapper<uint64_t / uint128>:  out[w] = XOR_i (y[i] & db[i*W + w]).
+ * Both maps are linear in the type's group, so the two parties' results
+ * combine with its + to beta * db[alpha] (beta & db[alpha]); sums mod 2^64
+ * and XOR commute, so the result is bit-exact whatever the order.  Every
+ * other value type: 12 UNIMPLEMENTED.  `out` gets record_words packed
+ * elements.  `workspace` (device, dpf_hip_expand_dot_workspace_bytes) holds
+ * one partial row per workgroup, written with plain stores (no atomics) and
+ * folded by a second small kernel; the calls do not depend on what it held
+ * before.
+ *
+ * dpf_hip_expand_dot: dpf_hip_expand's kernels with the leaf's stores
+ * replaced by the product, accumulated in registers (no share vector is
+ * written).  Only for the widths dpf_hip_expand_dot_fused reports (today
+ * record_words == 1); others: 12 UNIMPLEMENTED -- expand into scratch and
+ * call dpf_hip_dot_rows per slab, as EvaluateDotToDevice does. */
+#define DPF_HIP_DOT_MAX_RECORD_WORDS 1024
+int dpf_hip_expand_dot(int64_t num_starts, const dpf_block* seeds_in, const uint8_t* control_in,
+                       int num_levels, const dpf_block* cw_seed, const uint8_t* cw_left,
+                       const uint8_t* cw_right, const dpf_aes_key* key_left,
+                       const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                       const dpf_value_desc* desc, int elements_per_leaf,
+                       const dpf_block* value_correction, int party, const void* db,
+                       int record_words, void* workspace, void* out, void* stream);
+/* out[w] (+)= the fold of y[0 .. num_rows) (packed elements, device) into
+ * db[0 .. num_rows)[record_words]; accumulate != 0 combines with out's old
+ * value (the next slab of a streamed fold), else out is overwritten.
+ * Bandwidth-bound: a record's words lie along the lanes, several rows per
+ * wave for narrow records.  record_words need not be a power of two. */
+int dpf_hip_dot_rows(int64_t num_rows, int record_words, const dpf_value_desc* desc,
+                     const void* y, const void* db, int accumulate, void* workspace, void* out,
+                     void* stream);
+/* Bytes of workspace either call needs for this type and width (-1 and a
+ * last error for an unsupported type or width).  No device is touched. */
+int dpf_hip_expand_dot_workspace_bytes(const dpf_value_desc* desc, int record_words);
+/* 1 when dpf_hip_expand_dot has a fused kernel for this type and width, else
+ * 0.  DPF_DOT_STREAM=1 (read per call; A/B and test hook) turns it off. */
+int dpf_hip_expand_dot_fused(const dpf_value_desc* desc, int record_words);
+/* Diagnostic: the path the calling thread's last dot call took: "small",
+ * "pair" or "octet" (dpf_hip_expand_dot, the expand kernel it ran) or "rows"
+ * (dpf_hip_dot_rows); "" before the first call. */
+const char* dpf_hip_last_dot_kernel(void);
+
 /* Diagnostic: which kernel the calling thread's last successful dpf_hip_expand
  * launched ("octet/<leaf>" or "pair/<leaf>", leaf = fast, swar, mod32,
  * generic; "" before the first call), and the depth-first subtree depth it

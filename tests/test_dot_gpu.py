@@ -1,0 +1,375 @@
+"""Full-domain evaluation folded into a database (two-server PIR) on the GPU.
+
+Reference: the oracle's EvaluateUntil output of the same key, reduced with
+numpy against a seeded random database -- wrapping uint64 arithmetic for
+uint64_t, & and XOR for the XorWrapper types.  Sums mod 2^64 and XOR commute,
+so every comparison is an equality.  Both parties are checked against the
+reference, and their two answers must combine to beta * db[alpha]
+(beta & db[alpha]).  After each call the path it took is asserted
+(last_dot_kernel, last_expand_schedule): a fallback must not pass.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+U64, X64, X128 = ("int", 64), ("xor", 64), ("xor", 128)
+HOOKS = ("DPF_OCTET_DYNAMIC", "DPF_OCTET_TAPER", "DPF_OCTET_GLOBAL", "DPF_OCTET_TAPER_AT",
+         "DPF_OCTET_WALK", "DPF_EXPAND_TOP", "DPF_EXPAND_NO_OCTET", "DPF_EXPAND_SMALL",
+         "DPF_DOT_STREAM", "DPF_DOT_SLAB_LOG")
+
+
+@pytest.fixture(scope="module")
+def hip():
+    import torch
+    from distributed_point_functions_amd import hip_abi
+    hip_abi.load(require_gpu=True)
+    assert torch.cuda.is_available()
+    return hip_abi
+
+
+@pytest.fixture(autouse=True)
+def _no_hooks(monkeypatch):
+    for h in HOOKS:
+        monkeypatch.delenv(h, raising=False)
+
+
+def _words(vt):
+    return vt[1] // 64
+
+
+def _log_domain(vt, levels):
+    """Tree levels -> log_domain_size: a uint64 block holds two elements."""
+    return levels + 1 if vt[1] == 64 else levels
+
+
+# ---------------------------------------------------------------- reference
+@functools.lru_cache(maxsize=None)
+def _keys(vt, log_domain):
+    P = O.OracleParams([(log_domain, vt, 0)])
+    rng = np.random.default_rng(1000 * log_domain + vt[1] + (vt[0] == "xor"))
+    alpha = int(rng.integers(0, 1 << log_domain)) if log_domain else 0
+    beta = int.from_bytes(rng.bytes(vt[1] // 8), "little") | 1
+    k0, k1 = O.generate_keys(P, alpha, [[beta]], 0x5EED0 + log_domain, 0x5EED1 + log_domain)
+    return P, alpha, beta, (k0, k1)
+
+
+@functools.lru_cache(maxsize=2)
+def _db(vt, log_domain, record_words):
+    """Seeded random database: (records, record_words * words) uint64."""
+    rng = np.random.default_rng(77 + 31 * log_domain + record_words + vt[1])
+    return rng.integers(0, 2**64, size=(1 << log_domain, record_words * _words(vt)),
+                        dtype=np.uint64)
+
+
+def _fold(vt, y, db, record_words):
+    """numpy fold of the packed share vector y (n, esz) uint8 into db."""
+    w = _words(vt)
+    yv = np.ascontiguousarray(y).view(np.uint64).reshape(-1, 1, w)
+    d = db.reshape(db.shape[0], record_words, w)
+    if vt[0] == "xor":
+        return np.bitwise_xor.reduce(yv & d, axis=0).reshape(-1)
+    with np.errstate(over="ignore"):
+        return (yv * d).sum(axis=0, dtype=np.uint64).reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(vt, log_domain, record_words, party):
+    """The oracle's share vector folded into the database, computed once."""
+    P, _, _, keys = _keys(vt, log_domain)
+    y = O.evaluate_until(P, 0, [], O.create_context(P, keys[party]))
+    assert y.shape[0] == 1 << log_domain
+    return _fold(vt, y, _db(vt, log_domain, record_words), record_words)
+
+
+def _combine(vt, a, b):
+    return a ^ b if vt[0] == "xor" else a + b
+
+
+def _selected(vt, log_domain, record_words):
+    """beta * db[alpha] (beta & db[alpha]): what the two answers combine to."""
+    _, alpha, beta, _ = _keys(vt, log_domain)
+    w = _words(vt)
+    row = _db(vt, log_domain, record_words)[alpha].reshape(record_words, w)
+    b = np.array([(beta >> (64 * i)) & O.MASK64 for i in range(w)], dtype=np.uint64)
+    if vt[0] == "xor":
+        return (row & b).reshape(-1)
+    with np.errstate(over="ignore"):
+        return (row * b).reshape(-1)
+
+
+def _u64(t):
+    return t.cpu().numpy().view(np.uint64)
+
+
+# --------------------------------------------------------------- C ABI args
+def _abi_args(hip, vt, log_domain, party):
+    P, _, _, keys = _keys(vt, log_domain)
+    key = keys[party]
+    cs, cl, cr = O._cw_arrays(key, 0, P.hierarchy_to_tree[0])
+    desc = hip.value_desc(O.leaves(vt), O.is_direct(vt), O.elements_per_block(vt),
+                          P.blocks_needed[0])
+    return (hip.to_device_blocks(O.blocks_from_ints([key["seed"]])),
+            hip.to_device_u8(np.array([key["party"]], np.uint8)),
+            hip.to_device_blocks(cs), hip.to_device_u8(cl), hip.to_device_u8(cr),
+            (O.PRG_KEY_LEFT, O.PRG_KEY_RIGHT, O.PRG_KEY_VALUE), desc, P.cepb(0),
+            hip.to_device_blocks(O._leaf_array(O._value_correction(P, key, 0))), party)
+
+
+def _device_db(vt, log_domain, record_words=1):
+    import torch
+    return torch.from_numpy(_db(vt, log_domain, record_words).view(np.int64)).cuda()
+
+
+def _fused_case(hip, monkeypatch, vt, levels, env, kernel, schedule=None, device_check=False,
+                oracle_check=True):
+    import torch
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    ld = _log_domain(vt, levels)
+    db = _device_db(vt, ld)
+    got = []
+    for party in (0, 1):
+        args = _abi_args(hip, vt, ld, party)
+        assert args[3].shape[0] == levels
+        out = hip.expand_dot(*args, db)
+        torch.cuda.synchronize()
+        assert hip.last_dot_kernel() in kernel, (hip.last_dot_kernel(), kernel)
+        # The launch plan is dpf_hip_expand's own.
+        assert hip.last_expand_kernel()[0].split("/")[0] == hip.last_dot_kernel()
+        if schedule is not None:
+            schedule(hip.last_expand_schedule())
+        got.append(_u64(out))
+        if oracle_check:
+            assert np.array_equal(got[-1], _reference(vt, ld, 1, party)), (vt, levels, party)
+        assert device_check or oracle_check
+        if device_check:
+            # The unchanged expand kernel's share vector, reduced on the device.
+            y = hip.expand(*args).view(torch.int64).reshape(-1, _words(vt))
+            d = db.reshape(-1, _words(vt))
+            if vt[0] == "xor":
+                x = y & d
+                while x.shape[0] > 1:
+                    x = x[: x.shape[0] // 2] ^ x[x.shape[0] // 2:]
+                want = x.reshape(-1)
+            else:
+                want = (y * d).sum(dim=0)
+            assert np.array_equal(got[-1], _u64(want)), (vt, levels, party)
+            del y, d
+    assert np.array_equal(_combine(vt, got[0], got[1]), _selected(vt, ld, 1))
+
+
+def _static(s):
+    assert s["shift"] == 0, s
+
+
+def _per_workgroup_uniform(s):
+    assert s["shift"] > 0 and not s["global"] and len(s["phases"]) == 1, s
+
+
+def _global_counter(s):
+    assert s["shift"] > 0 and s["global"] and s["counters"] == 1, s
+
+
+def _global_tapered(s):
+    _global_counter(s)
+    assert [ph["depth"] for ph in s["phases"]] == [6, 4], s
+
+
+SMALL0 = {"DPF_EXPAND_SMALL": "0"}
+TAPER = {"DPF_OCTET_GLOBAL": "1", "DPF_OCTET_TAPER": "2"}
+
+
+@pytest.mark.parametrize("log_domain", [0, 1])
+def test_uint64_one_block(hip, monkeypatch, log_domain):
+    # One block: one kept element of two, then both.
+    import torch
+    got = []
+    db = _device_db(U64, log_domain)
+    for party in (0, 1):
+        out = hip.expand_dot(*_abi_args(hip, U64, log_domain, party), db)
+        torch.cuda.synchronize()
+        assert hip.last_dot_kernel() == "pair"
+        got.append(_u64(out))
+        assert np.array_equal(got[-1], _reference(U64, log_domain, 1, party))
+    assert np.array_equal(got[0] + got[1], _selected(U64, log_domain, 1))
+
+
+@pytest.mark.parametrize("levels,env,kernel,schedule", [
+    (1, SMALL0, ("pair",), None),                 # pair kernel, single-leaf ending
+    (2, SMALL0, ("pair",), None),                 # pair kernel, leaf-pair ending
+    (5, {}, ("small",), None),                    # quad levels
+    (12, {}, ("small",), None),                   # lane levels
+    (19, {}, ("small",), None),                   # largest small tree on 256 CUs
+    (12, SMALL0, ("octet", "pair"), _static),     # static, below one workgroup per CU
+    # 2^20 leaf blocks: one subtree of depth 2 per thread of the 256 workgroups
+    # (choose_subtree_depth), below the octet kernel's 3 levels -- the pair
+    # kernel, as for dpf_hip_expand; from 21 levels on the octet kernel, static.
+    (20, {}, ("pair",), _static),
+    (21, {}, ("octet",), _static),
+    (20, {"DPF_EXPAND_NO_OCTET": "1"}, ("pair",), None),
+    (21, {"DPF_EXPAND_NO_OCTET": "1"}, ("pair",), None),
+], ids=lambda v: None if callable(v) else str(v))
+def test_uint64_fused_shapes(hip, monkeypatch, levels, env, kernel, schedule):
+    _fused_case(hip, monkeypatch, U64, levels, env, kernel, schedule)
+
+
+@pytest.mark.parametrize("vt", [U64, X64, X128], ids=str)
+@pytest.mark.parametrize("env,schedule", [({}, _per_workgroup_uniform), (TAPER, _global_counter)],
+                         ids=["per_workgroup", "global_counter"])
+def test_fused_24_levels_dynamic(hip, monkeypatch, vt, env, schedule):
+    # One key's 24 levels run as subtrees of depth 6 -> 4: with the taper hooks
+    # the launch takes its chunks from one counter, but a finer phase would be
+    # below the octet's three levels (test_fused_26_levels_tapered has one).
+    _fused_case(hip, monkeypatch, vt, 24, env, ("octet",), schedule, device_check=True)
+
+
+def test_fused_26_levels_tapered(hip, monkeypatch):
+    """One counter and tapered chunks (depth 8 -> 6, then 4), the smallest
+    single-key shape that has them.  2^27 outputs are past the oracle's few
+    seconds, so the reference is dpf_hip_expand's share vector -- unchanged
+    code, tied to the oracle by the existing tests -- reduced on the device,
+    and the two answers must still select the record."""
+    _fused_case(hip, monkeypatch, U64, 26, TAPER, ("octet",), _global_tapered, device_check=True,
+                oracle_check=False)
+
+
+@pytest.mark.parametrize("vt", [X64, X128], ids=str)
+@pytest.mark.parametrize("levels,kernel", [(5, "small"), (20, "pair"), (21, "octet")])
+def test_xor_fused_shapes(hip, monkeypatch, vt, levels, kernel):
+    _fused_case(hip, monkeypatch, vt, levels, {}, (kernel,), _static if levels >= 20 else None)
+
+
+def test_workspace_contents_and_reuse_do_not_matter(hip):
+    """A workspace full of 0xA5, then a second key through the same workspace
+    and output, and a guard region behind the output that must stay as it was."""
+    import torch
+    ld = _log_domain(U64, 21)
+    db = _device_db(U64, ld)
+    args0 = _abi_args(hip, U64, ld, 0)
+    ws = torch.full((hip.dot_workspace_bytes(args0[6], 1),), 0xA5, dtype=torch.uint8, device="cuda")
+    buf = torch.full((8 + 256,), 0x5A, dtype=torch.uint8, device="cuda")
+    for party in (0, 1, 0):
+        out = hip.expand_dot(*_abi_args(hip, U64, ld, party), db, workspace=ws, out=buf[:8])
+        torch.cuda.synchronize()
+        assert out.data_ptr() == buf.data_ptr()
+        assert np.array_equal(_u64(buf[:8]), _reference(U64, ld, 1, party))
+        assert bool((buf[8:] == 0x5A).all())
+    # A small tree next, whose fewer workgroups leave most partial rows stale.
+    ld = _log_domain(U64, 5)
+    out = hip.expand_dot(*_abi_args(hip, U64, ld, 1), _device_db(U64, ld), workspace=ws,
+                         out=buf[:8])
+    torch.cuda.synchronize()
+    assert np.array_equal(_u64(out), _reference(U64, ld, 1, 1))
+    assert bool((buf[8:] == 0x5A).all())
+
+
+# ------------------------------------------------------------- host API
+def _host(vt, log_domain):
+    from distributed_point_functions_amd import dpf as D
+    from distributed_point_functions_amd import proto as pb
+    pvt = D.integer_type(vt[1]) if vt[0] == "int" else D.xor_wrapper_type(vt[1])
+    p = pb.DpfParameters(log_domain_size=log_domain)
+    p.value_type.CopyFrom(pvt)
+    dpf = D.DistributedPointFunction.create(p)
+    dpf.register_value_type(pvt)
+    _, alpha, beta, _ = _keys(vt, log_domain)
+    keys = dpf.generate_keys_incremental(
+        alpha, [D.to_value(pvt, beta)], seeds=(0x5EED0 + log_domain, 0x5EED1 + log_domain))
+    return dpf, keys
+
+
+def _host_dot(dpf, key, vt, db, record_words, shard=0, num_shards=1):
+    import torch
+    out = torch.full((record_words * vt[1] // 8 + 64,), 0x5A, dtype=torch.uint8, device="cuda")
+    n = dpf.evaluate_dot_to_device(key, 0, db, record_words, out[:-64], shard=shard,
+                                   num_shards=num_shards)
+    torch.cuda.synchronize()
+    assert n == record_words
+    assert bool((out[-64:] == 0x5A).all())
+    return _u64(out[:-64])
+
+
+@pytest.mark.parametrize("vt,record_words", [(U64, 1), (U64, 2), (U64, 3), (U64, 32), (X64, 33),
+                                             (X128, 3), (U64, 1024), (X128, 1024)], ids=str)
+def test_streamed_path_three_or_more_slabs(hip, monkeypatch, vt, record_words):
+    # 2^14 records in slabs of 2^12 (W = 1024: 2^10 records in slabs of 2^8).
+    ld = 14 if record_words < 1024 else 10
+    monkeypatch.setenv("DPF_DOT_SLAB_LOG", str(ld - 2))
+    if record_words == 1:
+        monkeypatch.setenv("DPF_DOT_STREAM", "1")
+    dpf, keys = _host(vt, ld)
+    db = _device_db(vt, ld, record_words)
+    got = []
+    for party in (0, 1):
+        got.append(_host_dot(dpf, keys[party], vt, db, record_words))
+        assert hip.last_dot_kernel() == "rows"
+        assert np.array_equal(got[-1], _reference(vt, ld, record_words, party))
+    assert np.array_equal(_combine(vt, got[0], got[1]), _selected(vt, ld, record_words))
+
+
+@pytest.mark.parametrize("vt,record_words,ld", [(U64, 3, 7), (X128, 2, 9), (U64, 33, 0)], ids=str)
+def test_streamed_path_one_short_slab(hip, vt, record_words, ld):
+    dpf, keys = _host(vt, ld)
+    db = _device_db(vt, ld, record_words)
+    got = [_host_dot(dpf, keys[party], vt, db, record_words) for party in (0, 1)]
+    assert hip.last_dot_kernel() == "rows"
+    for party in (0, 1):
+        assert np.array_equal(got[party], _reference(vt, ld, record_words, party))
+    assert np.array_equal(_combine(vt, got[0], got[1]), _selected(vt, ld, record_words))
+
+
+def test_host_fused_takes_the_fused_kernel(hip):
+    ld = _log_domain(U64, 12)
+    dpf, keys = _host(U64, ld)
+    got = _host_dot(dpf, keys[1], U64, _device_db(U64, ld), 1)
+    assert hip.last_dot_kernel() == "small"
+    assert np.array_equal(got, _reference(U64, ld, 1, 1))
+
+
+@pytest.mark.parametrize("vt,record_words", [(U64, 1), (U64, 3), (X128, 1)], ids=str)
+def test_four_shards_combine_to_the_unsharded_answer(hip, vt, record_words):
+    ld = 16
+    dpf, keys = _host(vt, ld)
+    db = _device_db(vt, ld, record_words)
+    rows = db.shape[0] // 4
+    for party in (0, 1):
+        whole = _host_dot(dpf, keys[party], vt, db, record_words)
+        total = None
+        for shard in range(4):
+            part = _host_dot(dpf, keys[party], vt, db[shard * rows:(shard + 1) * rows].contiguous(),
+                             record_words, shard=shard, num_shards=4)
+            total = part if total is None else _combine(vt, total, part)
+        assert np.array_equal(total, whole)
+        assert np.array_equal(whole, _reference(vt, ld, record_words, party))
+
+
+@pytest.mark.parametrize("vt", [U64, X64, X128], ids=str)
+def test_python_evaluate_dot(hip, vt):
+    ld = 10
+    dpf, keys = _host(vt, ld)
+    db = _device_db(vt, ld, 2)
+    got = [np.ascontiguousarray(dpf.evaluate_dot(keys[p], 0, db, 2)).view(np.uint64).reshape(-1)
+           for p in (0, 1)]
+    for party in (0, 1):
+        assert np.array_equal(got[party], _reference(vt, ld, 2, party))
+    assert np.array_equal(_combine(vt, got[0], got[1]), _selected(vt, ld, 2))
+
+
+def test_python_evaluate_dot_uint32_is_unimplemented(hip):
+    import torch
+    from distributed_point_functions_amd import dpf as D
+    from distributed_point_functions_amd import proto as pb
+    p = pb.DpfParameters(log_domain_size=10)
+    p.value_type.CopyFrom(D.integer_type(32))
+    dpf = D.DistributedPointFunction.create(p)
+    k0, _ = dpf.generate_keys_incremental(5, [D.to_value(D.integer_type(32), 7)], seeds=(3, 4))
+    db = torch.zeros(1 << 10, dtype=torch.int32, device="cuda")
+    with pytest.raises(D.DpfStatusError) as e:
+        dpf.evaluate_dot(k0, 0, db, 1)
+    assert e.value.code == 12
+    assert "uint64_t, XorWrapper<uint64_t> and XorWrapper<absl::uint128>" in e.value.message
