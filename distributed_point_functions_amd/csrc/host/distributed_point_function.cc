@@ -1031,6 +1031,181 @@ StatusOr<std::vector<uint8_t>> DistributedPointFunction::EvaluateDotPacked(
   return out;
 }
 
+// Dense PIR: the streamed path of EvaluateDotToDevice with one bit per record
+// and up to 64 keys per pass over the database.  The shard is cut into slabs
+// of whole leaf blocks whose Q bit rows fit the dot call's scratch bound
+// together; every key's slab is expanded by the unchanged dpf_hip_expand into
+// its row of the scratch, and dpf_hip_select_rows folds the slab of the
+// database into all Q answers at once.  DPF_SELECT_SLAB_LOG (read per call;
+// test hook) sets the log2 of a slab's records instead, at least 7.
+Status DistributedPointFunction::CheckSelectArgs(
+    Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard, int64_t num_shards,
+    const void* device_db, int64_t db_bytes, int64_t record_words, const void* device_out,
+    int64_t out_bytes) const {
+  const int H = static_cast<int>(parameters().size());
+  if (hierarchy_level < 0 || hierarchy_level >= H)
+    return InvalidArgumentError(
+        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+  const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
+  const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
+  const int bits = desc.bits[0];
+  if (desc.num_leaves != 1 || !desc.direct || desc.kind[0] != DPF_LEAF_XOR ||
+      desc.blocks_needed != 1 || !(bits == 64 || bits == 128) ||
+      desc.elements_per_block != 128 / bits)
+    return UnimplementedError(
+        "the bit-selected database fold is implemented for XorWrapper<uint64_t> and "
+        "XorWrapper<absl::uint128> only");
+  if (num_shards < 1 || (num_shards & (num_shards - 1)) || shard < 0 || shard >= num_shards)
+    return InvalidArgumentError("num_shards must be a power of two and 0 <= shard < num_shards");
+  int k = 0;
+  while ((int64_t{1} << k) < num_shards) ++k;
+  const int stop_level = hierarchy_to_tree()[hierarchy_level];
+  if (k > stop_level) return InvalidArgumentError("more shards than subtrees at this level");
+  // The cap of EvaluateDotToDevice, on the records: one per output bit.
+  const int log_domain_size = parameters()[hierarchy_level].log_domain_size();
+  if (log_domain_size - k + (bits == 64 ? 6 : 7) > 62)
+    return InvalidArgumentError(
+        "Output size would be larger than 2**62. Please evaluate fewer hierarchy levels at once.");
+  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
+    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  const int64_t Q = static_cast<int64_t>(keys.size());
+  if (Q < 1 || Q > DPF_HIP_SELECT_MAX_QUERIES)
+    return InvalidArgumentError("`keys` must hold between 1 and 64 keys");
+  const int64_t rows = (int64_t{1} << (stop_level - k)) *
+                       corrected_elements_per_block(hierarchy_level) * f.packed_size * 8;
+  if (rows > (std::numeric_limits<int64_t>::max() / (8 * record_words)) ||
+      db_bytes < rows * 8 * record_words)
+    return InvalidArgumentError("database buffer too small");
+  if (out_bytes < Q * record_words * 8)
+    return InvalidArgumentError("device output buffer too small");
+  if (!device_db || !device_out)
+    return InvalidArgumentError("`device_db` and `device_out` must not be null");
+  for (int64_t q = 0; q < Q; ++q) {
+    if (!keys[q])
+      return InvalidArgumentError("`keys[" + std::to_string(q) + "]` must not be null");
+    if (Status st = validator_->ValidateDpfKey(*keys[q]); !st.ok())
+      return Status(st.code(), "DpfKey " + std::to_string(q) + ": " + st.message());
+  }
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateSelectToDevice(
+    Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard, int64_t num_shards,
+    const void* device_db, int64_t db_bytes, int64_t record_words, void* device_out,
+    int64_t out_bytes, void* stream) const {
+  DPF_RETURN_IF_ERROR(CheckSelectArgs(keys, hierarchy_level, shard, num_shards, device_db,
+                                      db_bytes, record_words, device_out, out_bytes));
+  const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
+  const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
+  int k = 0;
+  while ((int64_t{1} << k) < num_shards) ++k;
+  const int stop_level = hierarchy_to_tree()[hierarchy_level];
+  const int cepb = corrected_elements_per_block(hierarchy_level);
+  const int W = static_cast<int>(record_words);
+  const int64_t Q = static_cast<int64_t>(keys.size());
+  const int L = stop_level - k;                                      // tree levels below the shard's root
+  const int64_t rows = (int64_t{1} << L) * cepb * f.packed_size * 8;  // records of this shard
+  const int workspace_bytes = dpf_hip_select_workspace_bytes(W, static_cast<int>(Q));
+  if (workspace_bytes < 0) return InvalidArgumentError(dpf_hip_last_error());
+
+  // 2^j slabs of whole leaf blocks: Q * slab_rows / 8 <= kDotSlabBytes.
+  int slab_log = 7;
+  while ((int64_t{2} << slab_log) * Q / 8 <= kDotSlabBytes) ++slab_log;
+  if (const char* v = std::getenv("DPF_SELECT_SLAB_LOG"); v && *v)
+    slab_log = std::min(std::max(std::atoi(v), 7), 62);
+  int j = 0;
+  while (j < L && (rows >> j) > (int64_t{1} << slab_log)) ++j;
+  if (j > kDotMaxSlabLevels)
+    return InvalidArgumentError("the database fold would take more than 2**20 slabs");
+  const int64_t slabs = int64_t{1} << j;
+  const int64_t slab_rows = rows >> j;
+  const int64_t stride = (slab_rows / 8 + 15) & ~int64_t{15};   // bytes of a key's bit row
+
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  // One packed image: the slabs' paths, and per key a root and party per
+  // slab, the value correction and both correction-word ranges.
+  std::vector<dpf_block> paths(slabs);
+  for (int64_t i = 0; i < slabs; ++i)
+    paths[i] = ToBlock((static_cast<uint128>(shard) << j) | static_cast<uint128>(i));
+  PackedUploads& up = s->shard_alt ? s->packed_alt : s->packed;
+  s->shard_alt = !s->shard_alt;
+  DPF_RETURN_IF_ERROR(up.Reset());
+  const size_t o_path = up.Add(paths.data(), paths.size());
+  struct KeyOffsets {
+    size_t seed, ctrl, vcw;
+    PackedCws top, cw;
+    int party;
+  };
+  std::vector<KeyOffsets> ko(Q);
+  for (int64_t q = 0; q < Q; ++q) {
+    const DpfKey& key = *keys[q];
+    DPF_ASSIGN_OR_RETURN(std::vector<uint128> vcw, ValueCorrectionLeaves(key, hierarchy_level));
+    std::vector<dpf_block> vcw_blocks(vcw.size());
+    for (size_t i = 0; i < vcw.size(); ++i) vcw_blocks[i] = ToBlock(vcw[i]);
+    const uint8_t party = static_cast<uint8_t>(key.party() & 1);
+    const std::vector<dpf_block> roots(slabs, ToBlock(FromProtoBlock(key.seed())));
+    const std::vector<uint8_t> parties(slabs, party);
+    ko[q].party = party;
+    ko[q].seed = up.Add(roots.data(), roots.size());
+    ko[q].ctrl = up.Add(parties.data(), parties.size());
+    ko[q].vcw = up.Add(vcw_blocks.data(), vcw_blocks.size());
+    ko[q].top = AddCorrectionWords(key, 0, k + j, up);
+    ko[q].cw = AddCorrectionWords(key, k + j, stop_level, up);
+  }
+  DPF_RETURN_IF_ERROR(up.Commit(stream));
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  if (k + j > 0) {
+    // Every key's slab roots: the top k + j tree bits walked in place.
+    for (int64_t q = 0; q < Q; ++q) {
+      dpf_block* seed = up.Ptr<dpf_block>(ko[q].seed);
+      uint8_t* ctrl = up.Ptr<uint8_t>(ko[q].ctrl);
+      HIP_RETURN_IF_ERROR(dpf_hip_eval_paths(
+          slabs, k + j, seed, ctrl, up.Ptr<dpf_block>(o_path), up.Ptr<dpf_block>(ko[q].top.seed),
+          up.Ptr<uint8_t>(ko[q].top.left), up.Ptr<uint8_t>(ko[q].top.right), &kl, &kr, seed, ctrl,
+          stream));
+    }
+  }
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace, workspace_bytes, stream));
+  DPF_RETURN_IF_ERROR(s->out.Reserve(static_cast<size_t>(Q * stride)));
+  char* sel = static_cast<char*>(s->out.get());
+  for (int64_t i = 0; i < slabs; ++i) {
+    for (int64_t q = 0; q < Q; ++q)
+      HIP_RETURN_IF_ERROR(dpf_hip_expand(
+          1, up.Ptr<dpf_block>(ko[q].seed) + i, up.Ptr<uint8_t>(ko[q].ctrl) + i, L - j,
+          up.Ptr<dpf_block>(ko[q].cw.seed), up.Ptr<uint8_t>(ko[q].cw.left),
+          up.Ptr<uint8_t>(ko[q].cw.right), &kl, &kr, &kv, &desc, cepb,
+          up.Ptr<dpf_block>(ko[q].vcw), ko[q].party, sel + q * stride, stream));
+    HIP_RETURN_IF_ERROR(dpf_hip_select_rows(
+        slab_rows, W, static_cast<int>(Q), sel, stride,
+        static_cast<const char*>(device_db) + i * slab_rows * 8 * W, i > 0, s->workspace.get(),
+        device_out, stream));
+  }
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  DPF_RETURN_IF_ERROR(up.MarkUsed(stream));
+  return Q * record_words;
+}
+
+StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateSelect(
+    Span<const DpfKey* const> keys, int hierarchy_level, const void* device_db, int64_t db_bytes,
+    int64_t record_words) const {
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);
+  // Checked before the result buffer is allocated: host errors touch no device.
+  DPF_RETURN_IF_ERROR(CheckSelectArgs(keys, hierarchy_level, 0, 1, device_db, db_bytes,
+                                      record_words, /*device_out=*/this,
+                                      std::numeric_limits<int64_t>::max()));
+  const size_t words = keys.size() * static_cast<size_t>(record_words);
+  DPF_RETURN_IF_ERROR(s->gathered.Reserve(words * 8));
+  DPF_RETURN_IF_ERROR(EvaluateSelectToDevice(keys, hierarchy_level, 0, 1, device_db, db_bytes,
+                                             record_words, s->gathered.get(),
+                                             static_cast<int64_t>(words * 8), nullptr)
+                          .status());
+  std::vector<uint64_t> out(words);
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), s->gathered.get(), words * 8, nullptr));
+  return out;
+}
+
 namespace {
 // Host-phase timing of EvaluateAt, printed at exit when DPF_HOST_TIMING is
 // set (the first 10 calls, allocations and page-locked buffers, not counted):

@@ -350,6 +350,43 @@ class DistributedPointFunction:
                     db.data_ptr(), db.numel() * db.element_size(), int(record_words))
         return _natural(self._parameters[hierarchy_level].value_type, out, int(record_words))
 
+    def evaluate_select_to_device(self, keys: Sequence[pb.DpfKey], hierarchy_level: int, db,
+                                  record_words: int, out, shard: int = 0, num_shards: int = 1,
+                                  stream=None) -> int:
+        """Dense two-server PIR answers of up to 64 keys against one pass over
+        the database: for XorWrapper<uint64 / uint128> every output *bit* of a
+        key's full-domain evaluation selects one record (128 per leaf block),
+        and out[q][w] = XOR of db[j][w] over the set bits j of key q.  `db`
+        (torch device tensor) holds this shard's records, row-major,
+        `record_words` uint64 words each; writes len(keys) * record_words
+        uint64 into the torch device tensor `out` and returns that count.  The
+        two parties' (and all shards') answers combine with XOR."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(out.device)
+        return _call(self._impl.evaluate_select_to_device,
+                     [k.SerializeToString() for k in keys], int(hierarchy_level), int(shard),
+                     int(num_shards), db.data_ptr(), db.numel() * db.element_size(),
+                     int(record_words), out.data_ptr(), out.numel() * out.element_size(),
+                     s.cuda_stream)
+
+    def evaluate_select(self, keys: Sequence[pb.DpfKey], hierarchy_level: int, db,
+                        record_words: int, shard: int = 0, num_shards: int = 1):
+        """evaluate_select_to_device returned as a numpy uint64 array of shape
+        (len(keys), record_words)."""
+        if int(num_shards) == 1 and int(shard) == 0:
+            return _call(self._impl.evaluate_select, [k.SerializeToString() for k in keys],
+                         int(hierarchy_level), db.data_ptr(), db.numel() * db.element_size(),
+                         int(record_words))
+        import torch
+        n = max(len(keys) * int(record_words), 0)
+        out = torch.empty(max(n, 1), dtype=torch.int64, device=db.device)
+        self.evaluate_select_to_device(keys, hierarchy_level, db, record_words, out, shard=shard,
+                                       num_shards=num_shards)
+        torch.cuda.synchronize(out.device)
+        return out[:n].cpu().numpy().view(np.uint64).reshape(len(keys), int(record_words))
+
     def evaluate_at_batch(self, keys: Sequence[pb.DpfKey], hierarchy_level: int,
                           points: Sequence[int], points_per_key: int, packed: bool = False):
         pts = points if isinstance(points, np.ndarray) else u128_array(points)

@@ -111,7 +111,10 @@ def load(require_gpu: bool = False):
                             ("dpf_hip_dot_rows", [I64, I, P, P, P, I, P, P, P]),
                             ("dpf_hip_expand_dot_workspace_bytes", [P, I]),
                             ("dpf_hip_expand_dot_fused", [P, I]),
-                            ("dpf_hip_last_dot_kernel", [])):
+                            ("dpf_hip_last_dot_kernel", []),
+                            ("dpf_hip_select_rows", [I64, I, I, P, I64, P, I, P, P, P]),
+                            ("dpf_hip_select_workspace_bytes", [I, I]),
+                            ("dpf_hip_last_select_shape", [ctypes.POINTER(ctypes.c_int64)])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = types
         if hasattr(L, "dpf_hip_last_dot_kernel"):
@@ -146,8 +149,8 @@ def last_points_kernel() -> str:
 
 def last_dot_kernel() -> str:
     """Path of this thread's last dot call: "small", "pair" or "octet" (the
-    fused expand kernel) or "rows" (dot_rows) -- dispatch diagnostics for the
-    tests."""
+    fused expand kernel), "rows" (dot_rows) or "select" (select_rows) --
+    dispatch diagnostics for the tests."""
     return load().dpf_hip_last_dot_kernel().decode()
 
 
@@ -158,6 +161,22 @@ def dot_workspace_bytes(desc: ValueDesc, record_words: int) -> int:
         raise DpfHipError(12 if 1 <= record_words <= 1024 else 3,
                           load().dpf_hip_last_error().decode())
     return n
+
+
+def select_workspace_bytes(record_words: int, num_queries: int) -> int:
+    """Bytes of workspace select_rows needs (no GPU needed)."""
+    n = load().dpf_hip_select_workspace_bytes(record_words, num_queries)
+    if n < 0:
+        raise DpfHipError(3, load().dpf_hip_last_error().decode())
+    return n
+
+
+def last_select_shape():
+    """(queries per tile, passes over the database, workgroups per pass) of
+    this thread's last select_rows -- dispatch diagnostics for the tests."""
+    a = (ctypes.c_int64 * 3)()
+    check(load().dpf_hip_last_select_shape(a))
+    return tuple(a)
 
 
 def last_dynamic_chunks() -> int:
@@ -359,6 +378,24 @@ def dot_rows(num_rows: int, record_words: int, desc: ValueDesc, y, db, accumulat
     workspace, out = _dot_buffers(desc, record_words, workspace, out, db.device)
     check(L.dpf_hip_dot_rows(num_rows, record_words, ctypes.byref(desc), _p(y), _p(db),
                              1 if accumulate else 0, _p(workspace), _p(out), _stream(stream)))
+    return out
+
+
+def select_rows(num_rows: int, record_words: int, num_queries: int, sel, sel_stride_bytes: int,
+                db, accumulate: bool = False, workspace=None, out=None, stream=None):
+    """out[q][w] (^)= XOR of db[j][w] over the rows j < num_rows whose bit j of
+    row q of `sel` (device bytes, rows sel_stride_bytes apart) is set; returns
+    (num_queries, record_words) as an int64 tensor (the bits of uint64)."""
+    import torch
+    L = load(require_gpu=True)
+    if workspace is None:
+        workspace = torch.empty(select_workspace_bytes(record_words, num_queries),
+                                dtype=torch.uint8, device=db.device)
+    if out is None:
+        out = torch.empty((num_queries, record_words), dtype=torch.int64, device=db.device)
+    check(L.dpf_hip_select_rows(num_rows, record_words, num_queries, _p(sel), sel_stride_bytes,
+                                _p(db), 1 if accumulate else 0, _p(workspace), _p(out),
+                                _stream(stream)))
     return out
 
 

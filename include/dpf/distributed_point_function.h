@@ -249,6 +249,32 @@ class DistributedPointFunction {
     if (!packed.ok()) return packed.status();
     return Unpack<T>(hierarchy_level, *packed);
   }
+  // Dense two-server PIR, batched over queries: one output *bit* selects one
+  // record.  For T = XorWrapper<uint64_t> or XorWrapper<absl::uint128> (other
+  // value types: UNIMPLEMENTED) let y_q be the packed output of
+  // EvaluateUntil<T>(hierarchy_level, {}, fresh ctx of keys[q]) read as a
+  // byte string, bit j = (byte[j >> 3] >> (j & 7)) & 1 for j in [0, n), n =
+  // 2^log_domain_size * bits of T (128 records per leaf block), and
+  // `device_db` a row-major device array of n records of `record_words`
+  // uint64 words, whatever T is.  Then
+  //   out[q][w] = XOR over { j : bit_j(y_q) = 1 } of db[j][w];
+  // the two parties' answers for query q XOR to the XOR of db[alpha*bits + b]
+  // over the set bits b of beta.  The database is read once per tile of
+  // queries, not once per key; keys.size() is in [1, 64].  With num_shards > 1
+  // (a power of two, at most one shard per tree leaf), `device_db` holds only
+  // the records [shard * n / num_shards, (shard + 1) * n / num_shards) and
+  // the shards' answers XOR to the unsharded one.  Stateless and key-based
+  // like EvaluateDotToDevice.  Writes keys.size() * record_words uint64 to
+  // `device_out` on `stream` (asynchronous) and returns that count.
+  StatusOr<int64_t> EvaluateSelectToDevice(Span<const DpfKey* const> keys, int hierarchy_level,
+                                           int64_t shard, int64_t num_shards,
+                                           const void* device_db, int64_t db_bytes,
+                                           int64_t record_words, void* device_out,
+                                           int64_t out_bytes, void* stream) const;
+  // The unsharded answers returned to the host, [keys.size()][record_words].
+  StatusOr<std::vector<uint64_t>> EvaluateSelect(Span<const DpfKey* const> keys,
+                                                 int hierarchy_level, const void* device_db,
+                                                 int64_t db_bytes, int64_t record_words) const;
   StatusOr<std::vector<uint8_t>> EvaluateAtPacked(const DpfKey& key, int hierarchy_level,
                                                   Span<const uint128> evaluation_points,
                                                   EvaluationContext* ctx,
@@ -414,6 +440,10 @@ class DistributedPointFunction {
                                    DeviceStart* out, void* stream,
                                    const std::function<Status()>& before_device) const;
   StatusOr<std::vector<uint128>> ValueCorrectionLeaves(const DpfKey& key, int h) const;
+  // Every argument check of EvaluateSelectToDevice; touches no device.
+  Status CheckSelectArgs(Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard,
+                         int64_t num_shards, const void* device_db, int64_t db_bytes,
+                         int64_t record_words, const void* device_out, int64_t out_bytes) const;
   // Sizes `b` for n keys, and fills row k from `key` (validated).
   void ResizeKeyBatch(int64_t n, KeyBatch* b) const;
   Status FillKeyBatchRow(const DpfKey& key, int64_t k, KeyBatch* b) const;

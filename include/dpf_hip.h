@@ -230,9 +230,40 @@ int dpf_hip_expand_dot_workspace_bytes(const dpf_value_desc* desc, int record_wo
  * 0.  DPF_DOT_STREAM=1 (read per call; A/B and test hook) turns it off. */
 int dpf_hip_expand_dot_fused(const dpf_value_desc* desc, int record_words);
 /* Diagnostic: the path the calling thread's last dot call took: "small",
- * "pair" or "octet" (dpf_hip_expand_dot, the expand kernel it ran) or "rows"
- * (dpf_hip_dot_rows); "" before the first call. */
+ * "pair" or "octet" (dpf_hip_expand_dot, the expand kernel it ran), "rows"
+ * (dpf_hip_dot_rows) or "select" (dpf_hip_select_rows); "" before the first
+ * call. */
 const char* dpf_hip_last_dot_kernel(void);
+
+/* ---- dense PIR: a bit-selected database fold batched over queries ----------
+ * No reference counterpart.  `db` is a row-major device array of num_rows
+ * records of record_words uint64 words; row q of `sel` (device, at sel +
+ * q * sel_stride_bytes) is query q's bit vector, bit j = (byte[j >> 3] >>
+ * (j & 7)) & 1 -- the packed output of dpf_hip_expand for XorWrapper<uint64_t
+ * / uint128>, 128 records per leaf block.  For q < num_queries, w < W:
+ *   out[q*W + w] (^)= XOR over { j < num_rows : bit j of row q } of db[j*W + w]
+ * (accumulate != 0 XORs into out's old value -- the next slab of a streamed
+ * fold --, else out is overwritten; num_rows == 0 is an empty XOR).  The
+ * database is read once per tile of queries (dpf_hip_last_select_shape), not
+ * once per query.  num_rows is arbitrary; bits at positions >= num_rows are
+ * ignored whatever they hold.  sel_stride_bytes: a multiple of 16 and at
+ * least ceil(num_rows / 8).  record_words in [1, DPF_HIP_DOT_MAX_RECORD_WORDS],
+ * num_queries in [1, DPF_HIP_SELECT_MAX_QUERIES]; else 3 INVALID_ARGUMENT.
+ * `workspace` (device, dpf_hip_select_workspace_bytes) holds one partial
+ * [tile][record_words] per workgroup, written with plain stores (no atomics)
+ * and folded by a second small kernel; the call does not depend on what it
+ * held before.  dpf_hip_last_dot_kernel reports "select" after this call. */
+#define DPF_HIP_SELECT_MAX_QUERIES 64
+int dpf_hip_select_rows(int64_t num_rows, int record_words, int num_queries, const void* sel,
+                        int64_t sel_stride_bytes, const void* db, int accumulate, void* workspace,
+                        void* out, void* stream);
+/* Bytes of workspace the call needs (-1 and a last error for arguments out of
+ * range).  No device is touched. */
+int dpf_hip_select_workspace_bytes(int record_words, int num_queries);
+/* Diagnostic: the shape of the calling thread's last dpf_hip_select_rows:
+ * {queries per tile, passes over the database = ceil(num_queries / tile),
+ * workgroups of one pass}. */
+int dpf_hip_last_select_shape(int64_t* out3);
 
 /* Diagnostic: which kernel the calling thread's last successful dpf_hip_expand
  * launched ("octet/<leaf>" or "pair/<leaf>", leaf = fast, swar, mod32,
