@@ -18,10 +18,12 @@
 #include <cstring>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <unordered_map>
 
 #include "dpf_hip.h"
 #include "host_util.h"
+#include "shard_plan.h"
 #include "until_plan.h"
 
 namespace distributed_point_functions {
@@ -46,6 +48,13 @@ struct DistributedPointFunction::DeviceStart {
   int64_t n = 0;
   dpf_block* seeds = nullptr;
   uint8_t* ctrl = nullptr;
+};
+
+// What CheckSelectArgs derives: the shard's tree levels, the tree depth of the
+// hierarchy level and the records of the shard.
+struct DistributedPointFunction::SelectShape {
+  int k = 0, stop_level = 0;
+  int64_t rows = 0;
 };
 
 DistributedPointFunction::DistributedPointFunction(
@@ -312,6 +321,104 @@ PackedCws AddCorrectionWords(const DpfKey& key, int start, int stop, PackedUploa
   return o;
 }
 
+// Value-correction leaves added to a packed upload as blocks.
+size_t AddLeafBlocks(const std::vector<uint128>& leaves, PackedUploads& up) {
+  size_t off;
+  dpf_block* b = up.Reserve<dpf_block>(leaves.size(), &off);
+  for (size_t i = 0; i < leaves.size(); ++i) b[i] = ToBlock(leaves[i]);
+  return off;
+}
+
+// One key's tree expanded as `parts` independent subtree launches: the split
+// first call of EvaluateUntil (the 2^kSplitLevels subtrees under the root), a
+// shard (the one subtree under its prefix) and the slabs of the database
+// folds (the 2^j subtrees under the shard's prefix).  Everything the launches
+// read goes up in ONE packed image and one async H2D (seven synchronous
+// uploads had cost ~30 us per call, as much as config 1's whole expansion
+// kernel): per part a copy of the key's root and party, which one
+// dpf_hip_eval_paths walks in place down the part's path to its subtree root
+// at depth `top`, then the value correction and the correction words cut at
+// `top`.  Offsets are into the image.
+struct SubtreeParts {
+  int64_t parts;
+  int top, stop_level, party;
+  size_t seed, ctrl, vcw;
+  PackedCws top_cw, cw;   // correction words [0, top) and [top, stop_level)
+};
+
+// The parts' paths, (prefix << j) | i: once per call, whatever the number of keys.
+size_t AddSubtreePaths(int64_t prefix, int j, PackedUploads& up) {
+  const int64_t parts = int64_t{1} << j;
+  size_t off;
+  dpf_block* paths = up.Reserve<dpf_block>(parts, &off);
+  for (int64_t i = 0; i < parts; ++i) paths[i] = ToBlock(dpf_internal::SubtreePath(prefix, j, i));
+  return off;
+}
+
+SubtreeParts AddSubtreeParts(const DpfKey& key, int64_t parts, int top, int stop_level,
+                             const std::vector<uint128>& vcw, PackedUploads& up) {
+  SubtreeParts p{parts, top, stop_level, static_cast<int>(key.party() & 1), 0, 0, 0, {}, {}};
+  std::fill_n(up.Reserve<dpf_block>(parts, &p.seed), parts, ToBlock(FromProtoBlock(key.seed())));
+  std::fill_n(up.Reserve<uint8_t>(parts, &p.ctrl), parts, static_cast<uint8_t>(p.party));
+  p.vcw = AddLeafBlocks(vcw, up);
+  p.top_cw = AddCorrectionWords(key, 0, top, up);
+  p.cw = AddCorrectionWords(key, top, stop_level, up);
+  return p;
+}
+
+// The parts' roots walked in place to depth `top` (EvaluateSeeds); the image
+// is committed.
+Status WalkSubtreeRoots(const SubtreeParts& p, size_t o_path, const PackedUploads& up,
+                        void* stream) {
+  if (p.top == 0) return OkStatus();
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight);
+  dpf_block* seed = up.Ptr<dpf_block>(p.seed);
+  uint8_t* ctrl = up.Ptr<uint8_t>(p.ctrl);
+  return FromHip(dpf_hip_eval_paths(p.parts, p.top, seed, ctrl, up.Ptr<dpf_block>(o_path),
+                                    up.Ptr<dpf_block>(p.top_cw.seed), up.Ptr<uint8_t>(p.top_cw.left),
+                                    up.Ptr<uint8_t>(p.top_cw.right), &kl, &kr, seed, ctrl, stream));
+}
+
+// Part i's subtree expanded into `out`.
+Status ExpandSubtree(const SubtreeParts& p, int64_t i, const dpf_value_desc& desc, int cepb,
+                     const PackedUploads& up, void* out, void* stream) {
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  return FromHip(dpf_hip_expand(1, up.Ptr<dpf_block>(p.seed) + i, up.Ptr<uint8_t>(p.ctrl) + i,
+                                p.stop_level - p.top, up.Ptr<dpf_block>(p.cw.seed),
+                                up.Ptr<uint8_t>(p.cw.left), up.Ptr<uint8_t>(p.cw.right), &kl, &kr,
+                                &kv, &desc, cepb, up.Ptr<dpf_block>(p.vcw), p.party, out, stream));
+}
+
+// The shard, dot and select calls alternate between `packed` and `packed_alt`,
+// so a call waits (PackedUploads::Reset) for the launch two calls back, not
+// for the one still running: back-to-back shard calls keep the GPU busy while
+// the host builds the next call's image.
+PackedUploads& NextShardImage(dpf_internal::DeviceScratch& s) {
+  PackedUploads& up = s.shard_alt ? s.packed_alt : s.packed;
+  s.shard_alt = !s.shard_alt;
+  return up;
+}
+
+// Argument checks the full-domain entry points share.
+Status CheckLevel(int hierarchy_level, size_t num_levels) {
+  if (hierarchy_level < 0 || hierarchy_level >= static_cast<int>(num_levels))
+    return InvalidArgumentError(
+        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+  return OkStatus();
+}
+Status CheckRecordWords(int64_t record_words) {
+  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
+    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  return OkStatus();
+}
+
+// A slab hook (DPF_DOT_SLAB_LOG, DPF_SELECT_SLAB_LOG; read per call; test
+// hooks): the log2 of a slab's rows, in place of the scratch bound.
+std::optional<int> SlabLogHook(const char* name) {
+  const char* v = std::getenv(name);
+  return v && *v ? std::optional<int>(std::atoi(v)) : std::nullopt;
+}
+
 // Phase split of the prefix walk (ComputePartialEvaluations), printed at exit
 // with DPF_HOST_TIMING: the lookup of the stored evaluations, the image and
 // its upload, the walk on the device (with the walked seeds' D2H), and the
@@ -540,9 +647,7 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
   dpf_internal::PhaseTimer::Clock clk(g_until_timing);
   DPF_RETURN_IF_ERROR(validator_->ValidateEvaluationContext(ctx));
   const int H = static_cast<int>(parameters().size());
-  if (hierarchy_level < 0 || hierarchy_level >= H)
-    return InvalidArgumentError(
-        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
   if (requested_type) {
     DPF_ASSIGN_OR_RETURN(bool eq, dpf_internal::ValueTypesAreEqual(
                                       *requested_type, parameters()[hierarchy_level].value_type()));
@@ -643,10 +748,6 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
   *num_elements = total;
 
   clk.mark(5);
-  std::vector<dpf_block> vcw_blocks(vcw.size());
-  for (size_t i = 0; i < vcw.size(); ++i) vcw_blocks[i] = ToBlock(vcw[i]);
-  const size_t o_vcw = up.Add(vcw_blocks.data(), vcw_blocks.size());
-  const PackedCws o_cw = AddCorrectionWords(ctx.key(), start_level, stop_level, up);
   // A first call's output of >= DPF_HIP_REGISTER_MIN_BYTES bound for a fresh
   // host vector: the expansion runs as kSplitParts subtree launches, each
   // followed by an event, and the copy of part j (dpf_hip_memcpy_d2h_staged_after)
@@ -655,19 +756,15 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
   const bool split = host_out && host_out->grow && tree_indices.empty() && SplitOn() &&
                      L >= kSplitLevels + 12 &&
                      static_cast<size_t>(total) * esz >= DPF_HIP_REGISTER_MIN_BYTES;
-  size_t o_sub_seed = 0, o_sub_ctrl = 0, o_sub_path = 0;
-  PackedCws o_top{}, o_sub{};
+  size_t o_vcw = 0, o_sub_path = 0;
+  PackedCws o_cw{};
+  SubtreeParts sub{};
   if (split) {
-    const dpf_block root = ToBlock(FromProtoBlock(ctx.key().seed()));
-    const uint8_t party = static_cast<uint8_t>(ctx.key().party() & 1);
-    std::vector<dpf_block> roots(kSplitParts, root), paths(kSplitParts);
-    std::vector<uint8_t> parties(kSplitParts, party);
-    for (int j = 0; j < kSplitParts; ++j) paths[j] = ToBlock(static_cast<uint128>(j));
-    o_sub_seed = up.Add(roots.data(), roots.size());
-    o_sub_ctrl = up.Add(parties.data(), parties.size());
-    o_sub_path = up.Add(paths.data(), paths.size());
-    o_top = AddCorrectionWords(ctx.key(), 0, kSplitLevels, up);
-    o_sub = AddCorrectionWords(ctx.key(), kSplitLevels, stop_level, up);
+    o_sub_path = AddSubtreePaths(0, kSplitLevels, up);
+    sub = AddSubtreeParts(ctx.key(), kSplitParts, kSplitLevels, stop_level, vcw, up);
+  } else {
+    o_vcw = AddLeafBlocks(vcw, up);
+    o_cw = AddCorrectionWords(ctx.key(), start_level, stop_level, up);
   }
   clk.mark(6);
   DPF_RETURN_IF_ERROR(up.Commit(stream));
@@ -700,28 +797,20 @@ Status DistributedPointFunction::EvaluateUntilCore(int hierarchy_level, Span<con
     expand_out = s->out.get();
   }
   const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
-  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
   clk.mark(1);
   dpf_internal::PartEvents parts;
   if (split) {
     // The subtree roots at depth kSplitLevels (EvaluateSeeds, in place), then
     // one expansion per subtree into its slice of the output.
-    dpf_block* sub_seed = up.Ptr<dpf_block>(o_sub_seed);
-    uint8_t* sub_ctrl = up.Ptr<uint8_t>(o_sub_ctrl);
-    HIP_RETURN_IF_ERROR(dpf_hip_eval_paths(kSplitParts, kSplitLevels, sub_seed, sub_ctrl,
-                                           up.Ptr<dpf_block>(o_sub_path), up.Ptr<dpf_block>(o_top.seed),
-                                           up.Ptr<uint8_t>(o_top.left), up.Ptr<uint8_t>(o_top.right),
-                                           &kl, &kr, sub_seed, sub_ctrl, stream));
+    DPF_RETURN_IF_ERROR(WalkSubtreeRoots(sub, o_sub_path, up, stream));
     const size_t part_bytes = static_cast<size_t>(corrected / kSplitParts) * esz;
     for (int j = 0; j < kSplitParts; ++j) {
-      HIP_RETURN_IF_ERROR(dpf_hip_expand(
-          1, sub_seed + j, sub_ctrl + j, L - kSplitLevels, up.Ptr<dpf_block>(o_sub.seed),
-          up.Ptr<uint8_t>(o_sub.left), up.Ptr<uint8_t>(o_sub.right), &kl, &kr, &kv, &desc, cepb,
-          up.Ptr<dpf_block>(o_vcw), ctx.key().party() & 1,
-          static_cast<char*>(expand_out) + j * part_bytes, stream));
+      DPF_RETURN_IF_ERROR(ExpandSubtree(sub, j, desc, cepb, up,
+                                        static_cast<char*>(expand_out) + j * part_bytes, stream));
       DPF_RETURN_IF_ERROR(parts.Record(part_bytes * (j + 1), stream));
     }
   } else {
+    const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
     HIP_RETURN_IF_ERROR(dpf_hip_expand(start.n, start.seeds, start.ctrl, L,
                                        up.Ptr<dpf_block>(o_cw.seed), up.Ptr<uint8_t>(o_cw.left),
                                        up.Ptr<uint8_t>(o_cw.right), &kl, &kr, &kv, &desc, cepb,
@@ -812,22 +901,13 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateShardToDevice(
     int hierarchy_level, int64_t shard, int64_t num_shards, EvaluationContext& ctx,
     void* device_out, int64_t capacity_bytes, void* stream) const {
   DPF_RETURN_IF_ERROR(validator_->ValidateEvaluationContext(ctx));
-  const int H = static_cast<int>(parameters().size());
-  if (hierarchy_level < 0 || hierarchy_level >= H)
-    return InvalidArgumentError(
-        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
   if (ctx.previous_hierarchy_level() >= 0)
     return InvalidArgumentError("sharded evaluation is only defined for the first call with `ctx`");
-  if (num_shards < 1 || (num_shards & (num_shards - 1)) || shard < 0 || shard >= num_shards)
-    return InvalidArgumentError("num_shards must be a power of two and 0 <= shard < num_shards");
-  int k = 0;
-  while ((int64_t{1} << k) < num_shards) ++k;
   const int stop_level = hierarchy_to_tree()[hierarchy_level];
-  if (k > stop_level) return InvalidArgumentError("more shards than subtrees at this level");
-  const int log_domain_size = parameters()[hierarchy_level].log_domain_size();
-  if (log_domain_size - k > 62)
-    return InvalidArgumentError(
-        "Output size would be larger than 2**62. Please evaluate fewer hierarchy levels at once.");
+  DPF_ASSIGN_OR_RETURN(const int k, dpf_internal::ShardLevels(
+                                        shard, num_shards, stop_level,
+                                        parameters()[hierarchy_level].log_domain_size(), 0));
   DPF_ASSIGN_OR_RETURN(std::vector<uint128> vcw, ValueCorrectionLeaves(ctx.key(), hierarchy_level));
   const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
   const int cepb = corrected_elements_per_block(hierarchy_level);
@@ -836,72 +916,30 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateShardToDevice(
     return InvalidArgumentError("device output buffer too small");
   auto* s = scratch_.get();
   std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
-  // Everything the launches read -- root, party, shard path, value correction
-  // and both correction-word ranges -- goes up as ONE page-locked image and
-  // one async H2D (seven synchronous uploads had cost ~30 us per call, as
-  // much as config 1's whole expansion kernel).
-  const dpf_block root = ToBlock(FromProtoBlock(ctx.key().seed()));
-  const uint8_t party = static_cast<uint8_t>(ctx.key().party() & 1);
-  const dpf_block path = ToBlock(static_cast<uint128>(shard));
-  std::vector<dpf_block> vcw_blocks(vcw.size());
-  for (size_t i = 0; i < vcw.size(); ++i) vcw_blocks[i] = ToBlock(vcw[i]);
-  PackedUploads& up = s->shard_alt ? s->packed_alt : s->packed;
-  s->shard_alt = !s->shard_alt;
+  // One part: the subtree under the shard's k-bit prefix.
+  PackedUploads& up = NextShardImage(*s);
   DPF_RETURN_IF_ERROR(up.Reset());
-  const size_t o_seed = up.Add(&root, 1), o_ctrl = up.Add(&party, 1), o_path = up.Add(&path, 1);
-  const size_t o_vcw = up.Add(vcw_blocks.data(), vcw_blocks.size());
-  const PackedCws o_top = AddCorrectionWords(ctx.key(), 0, k, up);
-  const PackedCws o_cw = AddCorrectionWords(ctx.key(), k, stop_level, up);
+  const size_t o_path = AddSubtreePaths(shard, 0, up);
+  const SubtreeParts sub = AddSubtreeParts(ctx.key(), 1, k, stop_level, vcw, up);
   DPF_RETURN_IF_ERROR(up.Commit(stream));
-  dpf_block* seed = up.Ptr<dpf_block>(o_seed);
-  uint8_t* ctrl = up.Ptr<uint8_t>(o_ctrl);
-  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
-  if (k > 0) {
-    // Walk the root to the shard's subtree root along the top k tree bits (in place).
-    HIP_RETURN_IF_ERROR(dpf_hip_eval_paths(1, k, seed, ctrl, up.Ptr<dpf_block>(o_path),
-                                           up.Ptr<dpf_block>(o_top.seed), up.Ptr<uint8_t>(o_top.left),
-                                           up.Ptr<uint8_t>(o_top.right), &kl, &kr, seed, ctrl,
-                                           stream));
-  }
+  DPF_RETURN_IF_ERROR(WalkSubtreeRoots(sub, o_path, up, stream));
   const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
-  HIP_RETURN_IF_ERROR(dpf_hip_expand(1, seed, ctrl, stop_level - k, up.Ptr<dpf_block>(o_cw.seed),
-                                     up.Ptr<uint8_t>(o_cw.left), up.Ptr<uint8_t>(o_cw.right), &kl,
-                                     &kr, &kv, &desc, cepb, up.Ptr<dpf_block>(o_vcw), party,
-                                     device_out, stream));
+  DPF_RETURN_IF_ERROR(ExpandSubtree(sub, 0, desc, cepb, up, device_out, stream));
   DPF_RETURN_IF_ERROR(up.MarkUsed(stream));
   ctx.set_previous_hierarchy_level(hierarchy_level);
   return total;
 }
 
-namespace {
-// The streamed database fold expands the domain slab by slab into scratch:
-// at most this many bytes of share vector at a time (a power of two of
-// elements; 2^25 uint64_t).  DPF_DOT_SLAB_LOG (read per call; test hook) sets
-// the slab's log2 element count instead.
-constexpr int64_t kDotSlabBytes = int64_t{256} << 20;
-constexpr int kDotMaxSlabLevels = 20;   // at most 2^20 slabs per call
-}  // namespace
-
 StatusOr<int64_t> DistributedPointFunction::EvaluateDotToDevice(
     const DpfKey& key, int hierarchy_level, int64_t shard, int64_t num_shards,
     const void* device_db, int64_t db_bytes, int64_t record_words, void* device_out,
     int64_t out_bytes, void* stream) const {
-  const int H = static_cast<int>(parameters().size());
-  if (hierarchy_level < 0 || hierarchy_level >= H)
-    return InvalidArgumentError(
-        "`hierarchy_level` must be non-negative and less than parameters_.size()");
-  if (num_shards < 1 || (num_shards & (num_shards - 1)) || shard < 0 || shard >= num_shards)
-    return InvalidArgumentError("num_shards must be a power of two and 0 <= shard < num_shards");
-  int k = 0;
-  while ((int64_t{1} << k) < num_shards) ++k;
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
   const int stop_level = hierarchy_to_tree()[hierarchy_level];
-  if (k > stop_level) return InvalidArgumentError("more shards than subtrees at this level");
-  const int log_domain_size = parameters()[hierarchy_level].log_domain_size();
-  if (log_domain_size - k > 62)
-    return InvalidArgumentError(
-        "Output size would be larger than 2**62. Please evaluate fewer hierarchy levels at once.");
-  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
-    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  DPF_ASSIGN_OR_RETURN(const int k, dpf_internal::ShardLevels(
+                                        shard, num_shards, stop_level,
+                                        parameters()[hierarchy_level].log_domain_size(), 0));
+  DPF_RETURN_IF_ERROR(CheckRecordWords(record_words));
   const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
   const int cepb = corrected_elements_per_block(hierarchy_level);
   const int W = static_cast<int>(record_words);
@@ -923,68 +961,35 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateDotToDevice(
   // share vectors fit the scratch bound, each expanded by dpf_hip_expand and
   // folded by dpf_hip_dot_rows.
   const bool fused = dpf_hip_expand_dot_fused(&desc, W) != 0;
-  int j = 0;
+  dpf_internal::SlabPlan slab{0, 1, rows};
   if (!fused) {
-    int slab_log = 0;
-    while ((int64_t{2} << slab_log) * esz <= kDotSlabBytes) ++slab_log;
-    if (const char* v = std::getenv("DPF_DOT_SLAB_LOG"); v && *v) slab_log = std::atoi(v);
-    int64_t slab_rows = int64_t{1} << std::min(std::max(slab_log, 0), 62);
-    if (slab_rows < cepb) slab_rows = cepb;
-    while ((rows >> j) > slab_rows) ++j;
-    if (j > kDotMaxSlabLevels)
-      return InvalidArgumentError("the database fold would take more than 2**20 slabs");
+    DPF_ASSIGN_OR_RETURN(slab, dpf_internal::PlanSlabs(rows, cepb, 8 * esz,
+                                                       SlabLogHook("DPF_DOT_SLAB_LOG")));
   }
-  const int64_t slabs = int64_t{1} << j;
-  const int64_t slab_rows = rows >> j;
 
   auto* s = scratch_.get();
   std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
-  // One packed image, as EvaluateShardToDevice: a root, party and path per
-  // slab, the value correction and both correction-word ranges.
-  const dpf_block root = ToBlock(FromProtoBlock(key.seed()));
-  const uint8_t party = static_cast<uint8_t>(key.party() & 1);
-  std::vector<dpf_block> roots(slabs, root), paths(slabs);
-  std::vector<uint8_t> parties(slabs, party);
-  for (int64_t i = 0; i < slabs; ++i)
-    paths[i] = ToBlock((static_cast<uint128>(shard) << j) | static_cast<uint128>(i));
-  std::vector<dpf_block> vcw_blocks(vcw.size());
-  for (size_t i = 0; i < vcw.size(); ++i) vcw_blocks[i] = ToBlock(vcw[i]);
-  PackedUploads& up = s->shard_alt ? s->packed_alt : s->packed;
-  s->shard_alt = !s->shard_alt;
+  PackedUploads& up = NextShardImage(*s);
   DPF_RETURN_IF_ERROR(up.Reset());
-  const size_t o_seed = up.Add(roots.data(), roots.size());
-  const size_t o_ctrl = up.Add(parties.data(), parties.size());
-  const size_t o_path = up.Add(paths.data(), paths.size());
-  const size_t o_vcw = up.Add(vcw_blocks.data(), vcw_blocks.size());
-  const PackedCws o_top = AddCorrectionWords(key, 0, k + j, up);
-  const PackedCws o_cw = AddCorrectionWords(key, k + j, stop_level, up);
+  const size_t o_path = AddSubtreePaths(shard, slab.j, up);
+  const SubtreeParts sub = AddSubtreeParts(key, slab.slabs, k + slab.j, stop_level, vcw, up);
   DPF_RETURN_IF_ERROR(up.Commit(stream));
-  dpf_block* seed = up.Ptr<dpf_block>(o_seed);
-  uint8_t* ctrl = up.Ptr<uint8_t>(o_ctrl);
-  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
-  if (k + j > 0) {
-    // The slab roots: the top k + j tree bits walked in place, one call.
-    HIP_RETURN_IF_ERROR(dpf_hip_eval_paths(slabs, k + j, seed, ctrl, up.Ptr<dpf_block>(o_path),
-                                           up.Ptr<dpf_block>(o_top.seed), up.Ptr<uint8_t>(o_top.left),
-                                           up.Ptr<uint8_t>(o_top.right), &kl, &kr, seed, ctrl,
-                                           stream));
-  }
+  DPF_RETURN_IF_ERROR(WalkSubtreeRoots(sub, o_path, up, stream));
   DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace, workspace_bytes, stream));
   if (fused) {
+    const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
     HIP_RETURN_IF_ERROR(dpf_hip_expand_dot(
-        1, seed, ctrl, L, up.Ptr<dpf_block>(o_cw.seed), up.Ptr<uint8_t>(o_cw.left),
-        up.Ptr<uint8_t>(o_cw.right), &kl, &kr, &kv, &desc, cepb, up.Ptr<dpf_block>(o_vcw), party,
-        device_db, W, s->workspace.get(), device_out, stream));
+        1, up.Ptr<dpf_block>(sub.seed), up.Ptr<uint8_t>(sub.ctrl), L, up.Ptr<dpf_block>(sub.cw.seed),
+        up.Ptr<uint8_t>(sub.cw.left), up.Ptr<uint8_t>(sub.cw.right), &kl, &kr, &kv, &desc, cepb,
+        up.Ptr<dpf_block>(sub.vcw), sub.party, device_db, W, s->workspace.get(), device_out,
+        stream));
   } else {
-    DPF_RETURN_IF_ERROR(s->out.Reserve(static_cast<size_t>(slab_rows * esz)));
-    for (int64_t i = 0; i < slabs; ++i) {
-      HIP_RETURN_IF_ERROR(dpf_hip_expand(
-          1, seed + i, ctrl + i, L - j, up.Ptr<dpf_block>(o_cw.seed), up.Ptr<uint8_t>(o_cw.left),
-          up.Ptr<uint8_t>(o_cw.right), &kl, &kr, &kv, &desc, cepb, up.Ptr<dpf_block>(o_vcw), party,
-          s->out.get(), stream));
+    DPF_RETURN_IF_ERROR(s->out.Reserve(static_cast<size_t>(slab.slab_rows * esz)));
+    for (int64_t i = 0; i < slab.slabs; ++i) {
+      DPF_RETURN_IF_ERROR(ExpandSubtree(sub, i, desc, cepb, up, s->out.get(), stream));
       HIP_RETURN_IF_ERROR(dpf_hip_dot_rows(
-          slab_rows, W, &desc, s->out.get(),
-          static_cast<const char*>(device_db) + i * slab_rows * esz * W, i > 0,
+          slab.slab_rows, W, &desc, s->out.get(),
+          static_cast<const char*>(device_db) + i * slab.slab_rows * esz * W, i > 0,
           s->workspace.get(), device_out, stream));
     }
   }
@@ -996,17 +1001,13 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateDotToDevice(
 StatusOr<std::vector<uint8_t>> DistributedPointFunction::EvaluateDotPacked(
     const DpfKey& key, int hierarchy_level, const void* device_db, int64_t db_bytes,
     int64_t record_words, const ValueType* requested_type) const {
-  const int H = static_cast<int>(parameters().size());
-  if (hierarchy_level < 0 || hierarchy_level >= H)
-    return InvalidArgumentError(
-        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
   if (requested_type) {
     DPF_ASSIGN_OR_RETURN(bool eq, dpf_internal::ValueTypesAreEqual(
                                       *requested_type, parameters()[hierarchy_level].value_type()));
     if (!eq) return InvalidArgumentError("Value type T doesn't match parameters at `hierarchy_level`");
   }
-  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
-    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  DPF_RETURN_IF_ERROR(CheckRecordWords(record_words));
   const size_t bytes = static_cast<size_t>(record_words) * flat_[hierarchy_level].packed_size;
   auto* s = scratch_.get();
   std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);
@@ -1041,11 +1042,8 @@ StatusOr<std::vector<uint8_t>> DistributedPointFunction::EvaluateDotPacked(
 Status DistributedPointFunction::CheckSelectArgs(
     Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard, int64_t num_shards,
     const void* device_db, int64_t db_bytes, int64_t record_words, const void* device_out,
-    int64_t out_bytes) const {
-  const int H = static_cast<int>(parameters().size());
-  if (hierarchy_level < 0 || hierarchy_level >= H)
-    return InvalidArgumentError(
-        "`hierarchy_level` must be non-negative and less than parameters_.size()");
+    int64_t out_bytes, SelectShape* shape) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
   const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
   const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
   const int bits = desc.bits[0];
@@ -1055,24 +1053,19 @@ Status DistributedPointFunction::CheckSelectArgs(
     return UnimplementedError(
         "the bit-selected database fold is implemented for XorWrapper<uint64_t> and "
         "XorWrapper<absl::uint128> only");
-  if (num_shards < 1 || (num_shards & (num_shards - 1)) || shard < 0 || shard >= num_shards)
-    return InvalidArgumentError("num_shards must be a power of two and 0 <= shard < num_shards");
-  int k = 0;
-  while ((int64_t{1} << k) < num_shards) ++k;
-  const int stop_level = hierarchy_to_tree()[hierarchy_level];
-  if (k > stop_level) return InvalidArgumentError("more shards than subtrees at this level");
   // The cap of EvaluateDotToDevice, on the records: one per output bit.
-  const int log_domain_size = parameters()[hierarchy_level].log_domain_size();
-  if (log_domain_size - k + (bits == 64 ? 6 : 7) > 62)
-    return InvalidArgumentError(
-        "Output size would be larger than 2**62. Please evaluate fewer hierarchy levels at once.");
-  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
-    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  const int stop_level = hierarchy_to_tree()[hierarchy_level];
+  DPF_ASSIGN_OR_RETURN(const int k, dpf_internal::ShardLevels(
+                                        shard, num_shards, stop_level,
+                                        parameters()[hierarchy_level].log_domain_size(),
+                                        bits == 64 ? 6 : 7));
+  DPF_RETURN_IF_ERROR(CheckRecordWords(record_words));
   const int64_t Q = static_cast<int64_t>(keys.size());
   if (Q < 1 || Q > DPF_HIP_SELECT_MAX_QUERIES)
     return InvalidArgumentError("`keys` must hold between 1 and 64 keys");
   const int64_t rows = (int64_t{1} << (stop_level - k)) *
                        corrected_elements_per_block(hierarchy_level) * f.packed_size * 8;
+  if (shape) *shape = SelectShape{k, stop_level, rows};
   if (rows > (std::numeric_limits<int64_t>::max() / (8 * record_words)) ||
       db_bytes < rows * 8 * record_words)
     return InvalidArgumentError("database buffer too small");
@@ -1093,92 +1086,44 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateSelectToDevice(
     Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard, int64_t num_shards,
     const void* device_db, int64_t db_bytes, int64_t record_words, void* device_out,
     int64_t out_bytes, void* stream) const {
+  SelectShape shape;
   DPF_RETURN_IF_ERROR(CheckSelectArgs(keys, hierarchy_level, shard, num_shards, device_db,
-                                      db_bytes, record_words, device_out, out_bytes));
-  const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
-  const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
-  int k = 0;
-  while ((int64_t{1} << k) < num_shards) ++k;
-  const int stop_level = hierarchy_to_tree()[hierarchy_level];
+                                      db_bytes, record_words, device_out, out_bytes, &shape));
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
   const int cepb = corrected_elements_per_block(hierarchy_level);
   const int W = static_cast<int>(record_words);
   const int64_t Q = static_cast<int64_t>(keys.size());
-  const int L = stop_level - k;                                      // tree levels below the shard's root
-  const int64_t rows = (int64_t{1} << L) * cepb * f.packed_size * 8;  // records of this shard
   const int workspace_bytes = dpf_hip_select_workspace_bytes(W, static_cast<int>(Q));
   if (workspace_bytes < 0) return InvalidArgumentError(dpf_hip_last_error());
 
-  // 2^j slabs of whole leaf blocks: Q * slab_rows / 8 <= kDotSlabBytes.
-  int slab_log = 7;
-  while ((int64_t{2} << slab_log) * Q / 8 <= kDotSlabBytes) ++slab_log;
-  if (const char* v = std::getenv("DPF_SELECT_SLAB_LOG"); v && *v)
-    slab_log = std::min(std::max(std::atoi(v), 7), 62);
-  int j = 0;
-  while (j < L && (rows >> j) > (int64_t{1} << slab_log)) ++j;
-  if (j > kDotMaxSlabLevels)
-    return InvalidArgumentError("the database fold would take more than 2**20 slabs");
-  const int64_t slabs = int64_t{1} << j;
-  const int64_t slab_rows = rows >> j;
-  const int64_t stride = (slab_rows / 8 + 15) & ~int64_t{15};   // bytes of a key's bit row
+  // Slabs of whole leaf blocks (128 records) whose Q bit rows fit the scratch bound.
+  DPF_ASSIGN_OR_RETURN(const dpf_internal::SlabPlan slab,
+                       dpf_internal::PlanSlabs(shape.rows, 128, Q,
+                                               SlabLogHook("DPF_SELECT_SLAB_LOG")));
+  const int64_t stride = (slab.slab_rows / 8 + 15) & ~int64_t{15};   // bytes of a key's bit row
 
   auto* s = scratch_.get();
   std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
-  // One packed image: the slabs' paths, and per key a root and party per
-  // slab, the value correction and both correction-word ranges.
-  std::vector<dpf_block> paths(slabs);
-  for (int64_t i = 0; i < slabs; ++i)
-    paths[i] = ToBlock((static_cast<uint128>(shard) << j) | static_cast<uint128>(i));
-  PackedUploads& up = s->shard_alt ? s->packed_alt : s->packed;
-  s->shard_alt = !s->shard_alt;
+  // One image for all keys: the slabs' paths once, then each key's parts.
+  PackedUploads& up = NextShardImage(*s);
   DPF_RETURN_IF_ERROR(up.Reset());
-  const size_t o_path = up.Add(paths.data(), paths.size());
-  struct KeyOffsets {
-    size_t seed, ctrl, vcw;
-    PackedCws top, cw;
-    int party;
-  };
-  std::vector<KeyOffsets> ko(Q);
+  const size_t o_path = AddSubtreePaths(shard, slab.j, up);
+  std::vector<SubtreeParts> sub(Q);
   for (int64_t q = 0; q < Q; ++q) {
-    const DpfKey& key = *keys[q];
-    DPF_ASSIGN_OR_RETURN(std::vector<uint128> vcw, ValueCorrectionLeaves(key, hierarchy_level));
-    std::vector<dpf_block> vcw_blocks(vcw.size());
-    for (size_t i = 0; i < vcw.size(); ++i) vcw_blocks[i] = ToBlock(vcw[i]);
-    const uint8_t party = static_cast<uint8_t>(key.party() & 1);
-    const std::vector<dpf_block> roots(slabs, ToBlock(FromProtoBlock(key.seed())));
-    const std::vector<uint8_t> parties(slabs, party);
-    ko[q].party = party;
-    ko[q].seed = up.Add(roots.data(), roots.size());
-    ko[q].ctrl = up.Add(parties.data(), parties.size());
-    ko[q].vcw = up.Add(vcw_blocks.data(), vcw_blocks.size());
-    ko[q].top = AddCorrectionWords(key, 0, k + j, up);
-    ko[q].cw = AddCorrectionWords(key, k + j, stop_level, up);
+    DPF_ASSIGN_OR_RETURN(std::vector<uint128> vcw, ValueCorrectionLeaves(*keys[q], hierarchy_level));
+    sub[q] = AddSubtreeParts(*keys[q], slab.slabs, shape.k + slab.j, shape.stop_level, vcw, up);
   }
   DPF_RETURN_IF_ERROR(up.Commit(stream));
-  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
-  if (k + j > 0) {
-    // Every key's slab roots: the top k + j tree bits walked in place.
-    for (int64_t q = 0; q < Q; ++q) {
-      dpf_block* seed = up.Ptr<dpf_block>(ko[q].seed);
-      uint8_t* ctrl = up.Ptr<uint8_t>(ko[q].ctrl);
-      HIP_RETURN_IF_ERROR(dpf_hip_eval_paths(
-          slabs, k + j, seed, ctrl, up.Ptr<dpf_block>(o_path), up.Ptr<dpf_block>(ko[q].top.seed),
-          up.Ptr<uint8_t>(ko[q].top.left), up.Ptr<uint8_t>(ko[q].top.right), &kl, &kr, seed, ctrl,
-          stream));
-    }
-  }
+  for (int64_t q = 0; q < Q; ++q) DPF_RETURN_IF_ERROR(WalkSubtreeRoots(sub[q], o_path, up, stream));
   DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace, workspace_bytes, stream));
   DPF_RETURN_IF_ERROR(s->out.Reserve(static_cast<size_t>(Q * stride)));
   char* sel = static_cast<char*>(s->out.get());
-  for (int64_t i = 0; i < slabs; ++i) {
+  for (int64_t i = 0; i < slab.slabs; ++i) {
     for (int64_t q = 0; q < Q; ++q)
-      HIP_RETURN_IF_ERROR(dpf_hip_expand(
-          1, up.Ptr<dpf_block>(ko[q].seed) + i, up.Ptr<uint8_t>(ko[q].ctrl) + i, L - j,
-          up.Ptr<dpf_block>(ko[q].cw.seed), up.Ptr<uint8_t>(ko[q].cw.left),
-          up.Ptr<uint8_t>(ko[q].cw.right), &kl, &kr, &kv, &desc, cepb,
-          up.Ptr<dpf_block>(ko[q].vcw), ko[q].party, sel + q * stride, stream));
+      DPF_RETURN_IF_ERROR(ExpandSubtree(sub[q], i, desc, cepb, up, sel + q * stride, stream));
     HIP_RETURN_IF_ERROR(dpf_hip_select_rows(
-        slab_rows, W, static_cast<int>(Q), sel, stride,
-        static_cast<const char*>(device_db) + i * slab_rows * 8 * W, i > 0, s->workspace.get(),
+        slab.slab_rows, W, static_cast<int>(Q), sel, stride,
+        static_cast<const char*>(device_db) + i * slab.slab_rows * 8 * W, i > 0, s->workspace.get(),
         device_out, stream));
   }
   DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
@@ -1194,7 +1139,7 @@ StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateSelect(
   // Checked before the result buffer is allocated: host errors touch no device.
   DPF_RETURN_IF_ERROR(CheckSelectArgs(keys, hierarchy_level, 0, 1, device_db, db_bytes,
                                       record_words, /*device_out=*/this,
-                                      std::numeric_limits<int64_t>::max()));
+                                      std::numeric_limits<int64_t>::max(), /*shape=*/nullptr));
   const size_t words = keys.size() * static_cast<size_t>(record_words);
   DPF_RETURN_IF_ERROR(s->gathered.Reserve(words * 8));
   DPF_RETURN_IF_ERROR(EvaluateSelectToDevice(keys, hierarchy_level, 0, 1, device_db, db_bytes,
@@ -1318,12 +1263,10 @@ Status DistributedPointFunction::EvaluateAtToHost(const DpfKey& key, int hierarc
                                                   /*update_ctx=*/true, *ctx, &start, nullptr,
                                                   nullptr));
   }
-  std::vector<dpf_block> vcw_blocks(vcw.size());
-  for (size_t i = 0; i < vcw.size(); ++i) vcw_blocks[i] = ToBlock(vcw[i]);
   const dpf_block root = ToBlock(FromProtoBlock(key.seed()));
   const uint8_t party = static_cast<uint8_t>(key.party() & 1);
   const PackedCws o_cw = AddCorrectionWords(key, start_level, stop_level, up);
-  const size_t o_vcw = up.Add(vcw_blocks.data(), vcw_blocks.size());
+  const size_t o_vcw = AddLeafBlocks(vcw, up);
   const size_t o_root = up.Add(&root, 1);
   const size_t o_party = up.Add(&party, 1);
   clk.mark(1);

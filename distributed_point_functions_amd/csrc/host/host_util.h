@@ -735,12 +735,8 @@ class DeviceScratch {
   std::recursive_mutex mu;
   PackedUploads packed;
   PackedUploads packed_pe;   // ComputePartialEvaluations' walk (its seeds feed the expansion)
-  // EvaluateShardToDevice alternates between `packed` and this image, so a
-  // call waits (PackedUploads::Reset) for the launch two calls back, not for
-  // the one still running: back-to-back shard calls keep the GPU busy while
-  // the host builds the next call's image.
-  PackedUploads packed_alt;
-  bool shard_alt = false;
+  PackedUploads packed_alt;  // the shard, dot and select calls' second image
+  bool shard_alt = false;    // (NextShardImage, distributed_point_function.cc)
   // EvaluateUntil's prefix dedup, kept across calls so a call of the same
   // size value-initialises nothing.
   std::vector<uint128> tree_indices;

@@ -440,10 +440,13 @@ class DistributedPointFunction {
                                    DeviceStart* out, void* stream,
                                    const std::function<Status()>& before_device) const;
   StatusOr<std::vector<uint128>> ValueCorrectionLeaves(const DpfKey& key, int h) const;
-  // Every argument check of EvaluateSelectToDevice; touches no device.
+  // Every argument check of EvaluateSelectToDevice, and the shard's shape
+  // they derive (`shape` may be null); touches no device.
+  struct SelectShape;
   Status CheckSelectArgs(Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard,
                          int64_t num_shards, const void* device_db, int64_t db_bytes,
-                         int64_t record_words, const void* device_out, int64_t out_bytes) const;
+                         int64_t record_words, const void* device_out, int64_t out_bytes,
+                         SelectShape* shape) const;
   // Sizes `b` for n keys, and fills row k from `key` (validated).
   void ResizeKeyBatch(int64_t n, KeyBatch* b) const;
   Status FillKeyBatchRow(const DpfKey& key, int64_t k, KeyBatch* b) const;

@@ -1,6 +1,9 @@
 """The database fold (EvaluateDotToDevice, dpf_hip_expand_dot / dpf_hip_dot_rows)
 as far as it can be checked without a GPU: the C ABI's declarations, the
 workspace size, and every error the host API detects before any device work."""
+import os
+import subprocess
+
 import pytest
 import torch
 
@@ -166,3 +169,103 @@ def test_unsupported_value_types_are_unimplemented(vt):
     with pytest.raises(D.DpfStatusError) as e:
         dpf.evaluate_dot(key, 0, db, 1)
     assert e.value.code == UNIMPLEMENTED
+
+
+LEVEL_MSG = "`hierarchy_level` must be non-negative and less than parameters_.size()"
+SHARD_MSG = "num_shards must be a power of two and 0 <= shard < num_shards"
+MORE_SHARDS_MSG = "more shards than subtrees at this level"
+WORDS_MSG = "`record_words` must be in [1, 1024]"
+DB_MSG = "database buffer too small"
+OUT_MSG = "device output buffer too small"
+NULL_MSG = "`device_db` and `device_out` must not be null"
+
+
+def _without_last_correction_word(key):
+    bad = pb.DpfKey()
+    bad.CopyFrom(key)
+    del bad.correction_words[-1]
+    return bad
+
+
+def _raised(call):
+    with pytest.raises(D.DpfStatusError) as e:
+        call()
+    return e.value.code, e.value.message
+
+
+def test_evaluate_dot_to_device_reports_the_first_failing_check():
+    """Two faults at once: the check that comes first in EvaluateDotToDevice is
+    the one reported (level, shard split, record_words, database size, output
+    size, null pointers, key validation, unsupported type)."""
+    vt = D.integer_type(64)
+    dpf = _dpf(10, vt)
+    key = _key(dpf, vt)
+    bad = _without_last_correction_word(key)
+    key_msg = _raised(lambda: dpf.evaluate_at(bad, 0, [0]))[1]
+    db = torch.zeros(1 << 13, dtype=torch.uint8)
+    out = torch.zeros(8, dtype=torch.uint8)
+    null_db = _Buffer(0, 1 << 13)
+
+    assert _raised(lambda: _dot(dpf, key, db, 1, out, level=1, shard=0, num_shards=3)) == \
+        (INVALID_ARGUMENT, LEVEL_MSG)
+    assert _raised(lambda: _dot(dpf, key, db, 0, out, shard=0, num_shards=3)) == \
+        (INVALID_ARGUMENT, SHARD_MSG)
+    assert _raised(lambda: _dot(dpf, key, db, 0, out, num_shards=1 << 10)) == \
+        (INVALID_ARGUMENT, MORE_SHARDS_MSG)
+    assert _raised(lambda: _dot(dpf, key, db[:-1], 1025, out)) == (INVALID_ARGUMENT, WORDS_MSG)
+    assert _raised(lambda: _dot(dpf, key, db[:-1], 1, out[:7])) == (INVALID_ARGUMENT, DB_MSG)
+    assert _raised(lambda: _dot(dpf, key, null_db, 1, out[:7])) == (INVALID_ARGUMENT, OUT_MSG)
+    assert _raised(lambda: _dot(dpf, bad, null_db, 1, out)) == (INVALID_ARGUMENT, NULL_MSG)
+    assert _raised(lambda: _dot(dpf, bad, db[:-1], 1, out)) == (INVALID_ARGUMENT, DB_MSG)
+
+    # An invalid key of a value type the fold does not support: the key's error.
+    v32 = D.integer_type(32)
+    dpf32 = _dpf(6, v32)
+    bad32 = _without_last_correction_word(_key(dpf32, v32))
+    key32_msg = _raised(lambda: dpf32.evaluate_at(bad32, 0, [0]))[1]
+    assert _raised(lambda: _dot(dpf32, bad32, db, 1, out)) == (INVALID_ARGUMENT, key32_msg)
+    assert _raised(lambda: _dot(dpf, bad, db, 1, out)) == (INVALID_ARGUMENT, key_msg)
+    # ... and a short database with it: the database's.
+    assert _raised(lambda: _dot(dpf32, bad32, db[:255], 1, out)) == (INVALID_ARGUMENT, DB_MSG)
+
+
+def test_evaluate_dot_reports_the_first_failing_check():
+    """EvaluateDotPacked's order: level, record_words, null database,
+    unsupported type, database size, key validation.  evaluate_dot passes no
+    requested type; test_evaluate_dot_template_type_check_comes_second has
+    that check, through the C++ template."""
+    vt = D.integer_type(64)
+    dpf = _dpf(10, vt)
+    key = _key(dpf, vt)
+    bad = _without_last_correction_word(key)
+    key_msg = _raised(lambda: dpf.evaluate_at(bad, 0, [0]))[1]
+    db = torch.zeros(1 << 13, dtype=torch.uint8)
+    null_db = _Buffer(0, 1 << 13)
+    v32 = D.integer_type(32)
+    dpf32 = _dpf(6, v32)
+    key32 = _key(dpf32, v32)
+
+    assert _raised(lambda: dpf.evaluate_dot(key, 1, db, 0)) == (INVALID_ARGUMENT, LEVEL_MSG)
+    assert _raised(lambda: dpf.evaluate_dot(key, 0, null_db, 1025)) == (INVALID_ARGUMENT, WORDS_MSG)
+    assert _raised(lambda: dpf32.evaluate_dot(key32, 0, null_db, 1)) == (INVALID_ARGUMENT, NULL_MSG)
+    code, msg = _raised(lambda: dpf32.evaluate_dot(key32, 0, db[:255], 1))
+    assert code == UNIMPLEMENTED
+    assert "uint64_t, XorWrapper<uint64_t> and XorWrapper<absl::uint128>" in msg
+    assert _raised(lambda: dpf.evaluate_dot(bad, 0, db[:-1], 1)) == (INVALID_ARGUMENT, DB_MSG)
+    assert _raised(lambda: dpf.evaluate_dot(bad, 0, db, 1)) == (INVALID_ARGUMENT, key_msg)
+
+
+def test_evaluate_dot_template_type_check_comes_second(tmp_path):
+    """EvaluateDot<T> with a T that is not the level's type: reported after a
+    bad level and before bad record_words, a null or a short database
+    (tests/cpp/dot_type_precedence_test.cc; host errors only, no GPU calls)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib = os.path.join(root, "distributed_point_functions_amd", "lib")
+    exe = tmp_path / "dot_type_precedence_test"
+    subprocess.run(["g++", "-O1", "-std=c++20", "-Wall", f"-I{os.path.join(root, 'include')}",
+                    os.path.join(root, "tests", "cpp", "dot_type_precedence_test.cc"),
+                    "-o", str(exe), f"-L{lib}", "-ldpf", "-ldpf_hip", f"-Wl,-rpath,{lib}"],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "0 failures" in r.stdout

@@ -348,6 +348,30 @@ def test_four_shards_combine_to_the_unsharded_answer(hip, vt, record_words):
         assert np.array_equal(whole, _reference(vt, ld, record_words, party))
 
 
+@pytest.mark.parametrize("vt,record_words", [(U64, 3), (X128, 2), (U64, 1)], ids=str)
+def test_four_shards_of_four_slabs_each(hip, monkeypatch, vt, record_words):
+    # 2^10 records: each shard's 256 in four slabs of 64, so the slab roots lie
+    # at tree path (shard << 2) | slab and the correction words are cut there.
+    ld = 10
+    monkeypatch.setenv("DPF_DOT_SLAB_LOG", "6")
+    if record_words == 1:
+        monkeypatch.setenv("DPF_DOT_STREAM", "1")
+    dpf, keys = _host(vt, ld)
+    db = _device_db(vt, ld, record_words)
+    rows = db.shape[0] // 4
+    for party in (0, 1):
+        total = None
+        for shard in range(4):
+            part = _host_dot(dpf, keys[party], vt, db[shard * rows:(shard + 1) * rows].contiguous(),
+                             record_words, shard=shard, num_shards=4)
+            assert hip.last_dot_kernel() == "rows"
+            total = part if total is None else _combine(vt, total, part)
+        whole = _host_dot(dpf, keys[party], vt, db, record_words)
+        assert hip.last_dot_kernel() == "rows"
+        assert np.array_equal(total, whole)
+        assert np.array_equal(total, _reference(vt, ld, record_words, party))
+
+
 @pytest.mark.parametrize("vt", [U64, X64, X128], ids=str)
 def test_python_evaluate_dot(hip, vt):
     ld = 10

@@ -410,5 +410,62 @@ def test_evaluate_shard_argument_validation_before_device():
                                      stream=_NullStream())
 
 
+def test_evaluate_shard_reports_the_first_failing_check():
+    """Two faults at once: the check that comes first in EvaluateShardToDevice
+    is the one reported (context validation, level, first call only, shard
+    split, value correction, output buffer).  The fixture context's key has
+    three levels of uint32 (level 0: 2^4 outputs, four leaf blocks) and a value
+    correction of the wrong size at level 0."""
+    import torch
+    level_msg = "`hierarchy_level` must be non-negative and less than parameters_.size()"
+    first_call_msg = "sharded evaluation is only defined for the first call with `ctx`"
+    shard_msg = "num_shards must be a power of two and 0 <= shard < num_shards"
+    more_shards_msg = "more shards than subtrees at this level"
+    correction_msg = "values.size() (= 1) does not match ElementsPerBlock<T>() (= 4)"
+    buffer_msg = "device output buffer too small"
+    dpf = D.DistributedPointFunction.create_incremental(list(_fixture_context().parameters))
+    buf = torch.zeros(64, dtype=torch.uint8)      # level 0 whole: 16 uint32
+    short = buf[:3]
+
+    def raised(level, shard, num, out, previous=-1):
+        ctx = _fixture_context()
+        ctx.previous_hierarchy_level = previous
+        with pytest.raises(D.DpfStatusError) as e:
+            dpf.evaluate_shard_to_device(level, shard, num, ctx, out, stream=_NullStream())
+        return e.value.code, e.value.message
+
+    assert raised(3, 0, 1, buf, previous=2) == (3, "This context has already been fully evaluated")
+    assert raised(3, 0, 3, buf, previous=0) == (3, level_msg)
+    assert raised(-1, 0, 1, short, previous=0) == (3, level_msg)
+    assert raised(1, 0, 3, short, previous=0) == (3, first_call_msg)
+    assert raised(1, 0, 8, buf, previous=0) == (3, first_call_msg)
+    assert raised(0, 0, 3, short) == (3, shard_msg)
+    assert raised(0, 4, 4, short) == (3, shard_msg)
+    assert raised(0, 0, 8, short) == (3, more_shards_msg)
+    assert raised(0, 1, 2, short) == (3, correction_msg)
+    assert raised(0, 0, 1, buf) == (3, correction_msg)         # that fault alone
+    assert raised(2, 0, 128, short) == (3, more_shards_msg)    # the last level: 64 leaf blocks
+
+    # A well-formed key: the buffer's error is the last one.
+    ok = D.DistributedPointFunction.create(params([(10, ("int", 64), 0)])[0])
+    k0, _ = ok.generate_keys_incremental(3, [D.to_value(D.integer_type(64), 1)], seeds=(1, 2))
+    for shard, num, want in ((0, 1, buffer_msg), (511, 512, buffer_msg),
+                             (0, 1024, more_shards_msg), (512, 512, shard_msg)):
+        with pytest.raises(D.DpfStatusError) as e:
+            ok.evaluate_shard_to_device(0, shard, num, ok.create_evaluation_context(k0), short,
+                                        stream=_NullStream())
+        assert (e.value.code, e.value.message) == (3, want)
+
+    # The 2^62 cap is the split's last check, ahead of the buffer's.
+    big = D.DistributedPointFunction.create(params([(64, ("int", 64), 0)])[0])
+    k0, _ = big.generate_keys_incremental(3, [D.to_value(D.integer_type(64), 1)], seeds=(1, 2))
+    for num, want in ((3, shard_msg), (2, "Output size would be larger than 2**62. Please evaluate "
+                                          "fewer hierarchy levels at once.")):
+        with pytest.raises(D.DpfStatusError) as e:
+            big.evaluate_shard_to_device(0, 0, num, big.create_evaluation_context(k0), short,
+                                         stream=_NullStream())
+        assert (e.value.code, e.value.message) == (3, want)
+
+
 class _NullStream:
     cuda_stream = 0

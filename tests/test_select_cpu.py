@@ -224,3 +224,66 @@ def test_other_value_types_are_unimplemented(vt):
             call()
         assert e.value.code == UNIMPLEMENTED
         assert "XorWrapper<uint64_t> and XorWrapper<absl::uint128>" in e.value.message
+
+
+LEVEL_MSG = "`hierarchy_level` must be non-negative and less than parameters_.size()"
+SHARD_MSG = "num_shards must be a power of two and 0 <= shard < num_shards"
+MORE_SHARDS_MSG = "more shards than subtrees at this level"
+WORDS_MSG = "`record_words` must be in [1, 1024]"
+KEYS_MSG = "`keys` must hold between 1 and 64 keys"
+DB_MSG = "database buffer too small"
+OUT_MSG = "device output buffer too small"
+NULL_MSG = "`device_db` and `device_out` must not be null"
+TYPE_MSG = ("the bit-selected database fold is implemented for XorWrapper<uint64_t> and "
+            "XorWrapper<absl::uint128> only")
+
+
+def _raised(call):
+    with pytest.raises(D.DpfStatusError) as e:
+        call()
+    return e.value.code, e.value.message
+
+
+def test_select_reports_the_first_failing_check():
+    """Two faults at once: the check that comes first in CheckSelectArgs is the
+    one reported (level, unsupported type, shard split, record_words, key
+    count, database size, output size, null pointers, key validation)."""
+    dpf = _dpf(LOG_DOMAIN, X128)
+    key = _key(dpf, X128)
+    bad = pb.DpfKey()
+    bad.CopyFrom(key)
+    del bad.correction_words[-1]
+    key_msg = _raised(lambda: dpf.evaluate_at(bad, 0, [0]))[1]
+    db, out = _db(), _out()
+    short_db = _Buffer(0x1000, RECORDS * 8 - 1)
+    u64 = D.integer_type(64)
+    other = _dpf(LOG_DOMAIN, u64)
+    other_key = _key(other, u64)
+
+    assert _raised(lambda: _select(other, [other_key], db, 1, out, level=1)) == \
+        (INVALID_ARGUMENT, LEVEL_MSG)
+    assert _raised(lambda: _select(other, [other_key], db, 1, out, shard=0, num_shards=3)) == \
+        (UNIMPLEMENTED, TYPE_MSG)
+    assert _raised(lambda: _select(dpf, [key], db, 0, out, shard=4, num_shards=4)) == \
+        (INVALID_ARGUMENT, SHARD_MSG)
+    assert _raised(lambda: _select(dpf, [key], db, 0, out, num_shards=1 << (LOG_DOMAIN + 1))) == \
+        (INVALID_ARGUMENT, MORE_SHARDS_MSG)
+    assert _raised(lambda: _select(dpf, [], db, 1025, out)) == (INVALID_ARGUMENT, WORDS_MSG)
+    assert _raised(lambda: _select(dpf, [key] * 65, short_db, 1, _out(65))) == \
+        (INVALID_ARGUMENT, KEYS_MSG)
+    assert _raised(lambda: _select(dpf, [key, key], short_db, 1, _Buffer(0x2000, 15))) == \
+        (INVALID_ARGUMENT, DB_MSG)
+    assert _raised(lambda: _select(dpf, [key, key], _Buffer(0, RECORDS * 8), 1,
+                                   _Buffer(0x2000, 15))) == (INVALID_ARGUMENT, OUT_MSG)
+    assert _raised(lambda: _select(dpf, [bad], _Buffer(0, RECORDS * 8), 1, out)) == \
+        (INVALID_ARGUMENT, NULL_MSG)
+    assert _raised(lambda: _select(dpf, [key, bad], short_db, 1, _out(2))) == \
+        (INVALID_ARGUMENT, DB_MSG)
+    assert _raised(lambda: _select(dpf, [key, bad], db, 1, _out(2))) == \
+        (INVALID_ARGUMENT, "DpfKey 1: " + key_msg)
+    # evaluate_select: the same checks on the whole domain.
+    assert _raised(lambda: other.evaluate_select([other_key], 0, short_db, 0)) == \
+        (UNIMPLEMENTED, TYPE_MSG)
+    assert _raised(lambda: dpf.evaluate_select([key] * 65, 0, short_db, 1)) == \
+        (INVALID_ARGUMENT, KEYS_MSG)
+    assert _raised(lambda: dpf.evaluate_select([bad], 0, short_db, 1)) == (INVALID_ARGUMENT, DB_MSG)

@@ -282,6 +282,24 @@ def test_shards_xor_to_the_unsharded_answer(hip, vt, num_shards):
 
 
 @pytest.mark.parametrize("vt", [X64, X128], ids=str)
+def test_two_shards_of_four_slabs_each(hip, monkeypatch, vt):
+    # 4096 records: each shard's 2048 in four slabs of 512, so the slab roots
+    # lie at tree path (shard << 2) | slab and the correction words are cut there.
+    depth, Q, W = 5, 3, 4
+    monkeypatch.setenv("DPF_SELECT_SLAB_LOG", "9")
+    dpf, keys = _host(vt, depth, Q)
+    db = _device_db(vt, depth, W)
+    rows = db.shape[0] // 2
+    for party in (0, 1):
+        total = np.zeros((Q, W), dtype=np.uint64)
+        for shard in range(2):
+            total ^= _host_select(dpf, keys[party], db[shard * rows:(shard + 1) * rows].contiguous(),
+                                  W, shard=shard, num_shards=2)
+            assert hip.last_select_shape()[2] == 2     # workgroups of one slab's 512 rows
+        assert np.array_equal(total, _reference(vt, depth, Q, W, party))
+
+
+@pytest.mark.parametrize("vt", [X64, X128], ids=str)
 def test_python_evaluate_select(hip, vt):
     depth, Q, W = 5, 3, 4
     dpf, keys = _host(vt, depth, Q)
