@@ -198,8 +198,9 @@ def build_tools(force=False):
     suite restated (tools/dpf_benchmark.cc), the C++ template tests
     (tests/cpp/dpf_api_test.cc), the interval-containment gate's
     (tests/cpp/mic_gate_test.cc), the database fold's
-    (tests/cpp/dot_api_test.cc) and the bit-selected fold's
-    (tests/cpp/select_api_test.cc)."""
+    (tests/cpp/dot_api_test.cc), the bit-selected fold's
+    (tests/cpp/select_api_test.cc) and the batched sketch's
+    (tests/cpp/sketch_api_test.cc)."""
     hdrs = _files(os.path.join(INCLUDE), (".h",))
     cxx = os.environ.get("CXX", "g++")
     for src, name in ((os.path.join(ROOT, "tools", "dpf_benchmark.cc"), "dpf_benchmark"),
@@ -207,7 +208,9 @@ def build_tools(force=False):
                       (os.path.join(ROOT, "tests", "cpp", "mic_gate_test.cc"), "mic_gate_test"),
                       (os.path.join(ROOT, "tests", "cpp", "dot_api_test.cc"), "dot_api_test"),
                       (os.path.join(ROOT, "tests", "cpp", "select_api_test.cc"),
-                       "select_api_test")):
+                       "select_api_test"),
+                      (os.path.join(ROOT, "tests", "cpp", "sketch_api_test.cc"),
+                       "sketch_api_test")):
         out = os.path.join(LIBDIR, name)
         if force or _stale(out, [src, os.path.join(LIBDIR, "libdpf.so")] + hdrs):
             _run([cxx, "-O2", "-std=c++20", "-Wall", f"-I{INCLUDE}", src, "-o", out,

@@ -173,7 +173,7 @@ DeviceBatchContext::~DeviceBatchContext() {
   if (tables_event_) dpf_hip_event_destroy(tables_event_);
   if (pinned_tables_) dpf_hip_host_free(pinned_tables_);
   for (void* p : {seeds_, ctrl_, next_seeds_, next_ctrl_, parent_, workspace_, stage_, stage2_,
-                  leaf_seeds_, leaf_spare_, slots_, leaf_slot_})
+                  leaf_seeds_, leaf_spare_, slots_, leaf_slot_, sketch_w_, sketch_acc_})
     if (p) dpf_hip_free(p);
 }
 
@@ -385,6 +385,27 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchSumToDevice(
                                 stream);
 }
 
+// The sketch output mode of a batched call: J rows of n weights in, K * J * nl
+// uint32 out (include/dpf_hip.h, dpf_hip_sketch_rows).
+struct DistributedPointFunction::BatchSketch {
+  const uint32_t* weights;
+  int rows;
+  int64_t per_row;
+  uint32_t* out;
+  int64_t capacity_bytes;
+};
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchSketchToDevice(
+    int hierarchy_level, Span<const uint128> prefixes, DeviceBatchContext& ctx,
+    const uint32_t* device_weights, int num_weight_rows, int64_t weights_per_row,
+    void* device_sums, int64_t sums_capacity_bytes, uint32_t* device_sketch,
+    int64_t sketch_capacity_bytes, void* stream) const {
+  const BatchSketch sketch{device_weights, num_weight_rows, weights_per_row, device_sketch,
+                           sketch_capacity_bytes};
+  return EvaluateUntilBatchCore(hierarchy_level, prefixes, ctx, device_sums != nullptr,
+                                device_sums, sums_capacity_bytes, stream, &sketch);
+}
+
 // EvaluateUntil's argument checks (h:655-700), in the reference's order.
 Status DistributedPointFunction::CheckUntilBatchArgs(int hierarchy_level,
                                                      Span<const uint128> prefixes,
@@ -430,6 +451,7 @@ struct DistributedPointFunction::BatchCall {
   StartSource source = StartSource::kRoot;
   dpf_value_desc desc;
   bool native_sum = false;  // the kernel sums over the keys itself
+  bool fused_sketch = false;  // the key-sum kernel also computes the sketches
   UntilBatchShape shape;
   DeviceBatchContext::CacheTarget target;  // where the call's leaves go
   dpf_internal::TableLayout tables;        // the start-node table image
@@ -515,9 +537,16 @@ Status DistributedPointFunction::PlanBatchCall(int hierarchy_level, int64_t P,
 //   store: K rows.
 // A non-identity gather (dpf_hip_gather for one row, dpf_hip_gather_batched
 // for K) then writes the caller's buffer.
+//   sketch, fused (BatchCall::fused_sketch): the native key sum's launch
+//     through dpf_hip_eval_prefix_batch_sketch, which also writes the sketch
+//     buffer; the sums go to stage_ when the caller wants none;
+//   sketch, streamed: K rows into stage_, gathered per key into stage2_ unless
+//     the gather is the identity, then dpf_hip_sketch_rows over those rows into
+//     the sketch buffer and, with `sum`, dpf_hip_sum_rows into the caller's.
 Status DistributedPointFunction::LaunchBatchCall(int hierarchy_level, BatchCall& c,
                                                  DeviceBatchContext& ctx, bool sum,
-                                                 void* device_out, void* stream) const {
+                                                 void* device_out, void* stream,
+                                                 const BatchSketch* sketch) const {
   DeviceBatchContext::CacheTarget* target = &c.target;
   const dpf_internal::TableLayout& tab = c.tables;
   const DeviceKeyBatch& keys = ctx.keys();
@@ -534,10 +563,24 @@ Status DistributedPointFunction::LaunchBatchCall(int hierarchy_level, BatchCall&
     return ctx.EnsureEvicting(p, cap, bytes, target, stream);
   };
 
+  const bool streamed = sketch && !c.fused_sketch;
   void* kernel_out = device_out;
-  if (row_sum || gather_out) {
+  if (row_sum || gather_out || streamed || !device_out) {
     DPF_RETURN_IF_ERROR(ensure(&ctx.stage_, &ctx.stage_cap_, rows * sh.n_blk * esz));
     kernel_out = ctx.stage_;
+  }
+  if (streamed && gather_out)
+    DPF_RETURN_IF_ERROR(ensure(&ctx.stage2_, &ctx.stage2_cap_, K * sh.n * esz));
+  if (c.fused_sketch) {
+    DPF_RETURN_IF_ERROR(ensure(&ctx.sketch_w_, &ctx.sketch_w_cap_,
+                               sh.n_blk * sketch->rows * 2 * sizeof(uint32_t)));
+    DPF_RETURN_IF_ERROR(ensure(&ctx.sketch_acc_, &ctx.sketch_acc_cap_,
+                               K * sketch->rows * 2 * sizeof(uint64_t)));
+    // The caller's weights in the kernel's slot order, through the output
+    // gather's offsets.
+    HIP_RETURN_IF_ERROR(dpf_hip_sketch_slot_weights(
+        gather_out ? sh.P : sh.n, gather_out ? sh.cnt : 1, d_offsets, &c.desc, sketch->rows,
+        sketch->weights, ctx.sketch_w_, stream));
   }
   if (c.native_sum)
     DPF_RETURN_IF_ERROR(
@@ -561,21 +604,43 @@ Status DistributedPointFunction::LaunchBatchCall(int hierarchy_level, BatchCall&
     start_ctrl = ctx.partial_control();
   }
   const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
-  HIP_RETURN_IF_ERROR(dpf_hip_eval_prefix_batch_layout(
-      K, sh.U, sh.Wk + sh.s, sh.update_ctx && !target->gather ? sh.Wk : -1, sh.E,
-      sh.cached ? hierarchy_to_tree()[ctx.previous_hierarchy_level_] : c.start_level,
-      keys.num_levels(), keys.seed(), keys.party(), start_seeds, start_ctrl, start_stride,
-      reinterpret_cast<const int32_t*>(dtab),
-      tab.need_path ? reinterpret_cast<const dpf_block*>(dtab + tab.off_path) : nullptr,
-      tab.need_save ? reinterpret_cast<const int32_t*>(dtab + tab.off_save) : nullptr,
-      static_cast<dpf_block*>(ctx.next_seeds_), static_cast<uint8_t*>(ctx.next_ctrl_), sh.T,
-      keys.cw_seed(), keys.cw_left(), keys.cw_right(), &kl, &kr, &kv, &c.desc,
-      corrected_elements_per_block(hierarchy_level), keys.value_correction(hierarchy_level),
-      c.native_sum ? 1 : 0, c.native_sum ? static_cast<uint64_t*>(ctx.workspace_) : nullptr,
-      kernel_out, static_cast<dpf_block*>(target->leaf_seeds), target->stride,
-      target->permute ? static_cast<const int32_t*>(ctx.leaf_slot_) : nullptr,
-      ctx.index_major_ ? 1 : 0, stream));
+  // The one launch: dpf_hip_eval_prefix_batch_layout, or with the fused
+  // sketch dpf_hip_eval_prefix_batch_sketch (the same arguments and four more).
+  auto launch = [&](auto fn, auto... sketch_args) {
+    return fn(K, sh.U, sh.Wk + sh.s, sh.update_ctx && !target->gather ? sh.Wk : -1, sh.E,
+              sh.cached ? hierarchy_to_tree()[ctx.previous_hierarchy_level_] : c.start_level,
+              keys.num_levels(), keys.seed(), keys.party(), start_seeds, start_ctrl, start_stride,
+              reinterpret_cast<const int32_t*>(dtab),
+              tab.need_path ? reinterpret_cast<const dpf_block*>(dtab + tab.off_path) : nullptr,
+              tab.need_save ? reinterpret_cast<const int32_t*>(dtab + tab.off_save) : nullptr,
+              static_cast<dpf_block*>(ctx.next_seeds_), static_cast<uint8_t*>(ctx.next_ctrl_), sh.T,
+              keys.cw_seed(), keys.cw_left(), keys.cw_right(), &kl, &kr, &kv, &c.desc,
+              corrected_elements_per_block(hierarchy_level), keys.value_correction(hierarchy_level),
+              c.native_sum ? 1 : 0, c.native_sum ? static_cast<uint64_t*>(ctx.workspace_) : nullptr,
+              kernel_out, static_cast<dpf_block*>(target->leaf_seeds), target->stride,
+              target->permute ? static_cast<const int32_t*>(ctx.leaf_slot_) : nullptr,
+              ctx.index_major_ ? 1 : 0, sketch_args..., stream);
+  };
+  if (c.fused_sketch)
+    HIP_RETURN_IF_ERROR(launch(dpf_hip_eval_prefix_batch_sketch, sketch->rows,
+                               static_cast<const uint32_t*>(ctx.sketch_w_),
+                               static_cast<uint64_t*>(ctx.sketch_acc_), sketch->out));
+  else
+    HIP_RETURN_IF_ERROR(launch(dpf_hip_eval_prefix_batch_layout));
 
+  if (streamed) {
+    const void* key_rows = kernel_out;
+    if (gather_out) {
+      HIP_RETURN_IF_ERROR(dpf_hip_gather_batched(K, sh.n_blk, sh.P, sh.cnt, esz, d_offsets,
+                                                 kernel_out, ctx.stage2_, stream));
+      key_rows = ctx.stage2_;
+    }
+    HIP_RETURN_IF_ERROR(dpf_hip_sketch_rows(K, sh.n, &c.desc, key_rows, sketch->rows, 32,
+                                            sketch->weights, sketch->out, stream));
+    if (sum)
+      HIP_RETURN_IF_ERROR(dpf_hip_sum_rows(K, sh.n, &c.desc, key_rows, device_out, stream));
+    return OkStatus();
+  }
   const void* gather_in = kernel_out;
   if (row_sum) {
     // Value types without an on-device key sum in the kernel: a group sum
@@ -588,9 +653,9 @@ Status DistributedPointFunction::LaunchBatchCall(int hierarchy_level, BatchCall&
     HIP_RETURN_IF_ERROR(dpf_hip_sum_rows(K, sh.n_blk, &c.desc, ctx.stage_, summed, stream));
     gather_in = summed;
   }
-  if (gather_out && sum)
+  if (gather_out && sum && device_out)
     HIP_RETURN_IF_ERROR(dpf_hip_gather(sh.P, sh.cnt, esz, d_offsets, gather_in, device_out, stream));
-  if (gather_out && !sum)
+  if (gather_out && !sum && !sketch)
     HIP_RETURN_IF_ERROR(dpf_hip_gather_batched(K, sh.n_blk, sh.P, sh.cnt, esz, d_offsets, gather_in,
                                                device_out, stream));
   return OkStatus();
@@ -598,7 +663,7 @@ Status DistributedPointFunction::LaunchBatchCall(int hierarchy_level, BatchCall&
 
 StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchCore(
     int hierarchy_level, Span<const uint128> prefixes, DeviceBatchContext& ctx, bool sum,
-    void* device_out, int64_t capacity_bytes, void* stream) const {
+    void* device_out, int64_t capacity_bytes, void* stream, const BatchSketch* sketch) const {
   DPF_RETURN_IF_ERROR(CheckUntilBatchArgs(hierarchy_level, prefixes, ctx));
   PhaseTimer::Clock clk(g_timing);
   g_timing.count_call();
@@ -622,11 +687,38 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchCore(
     c.prefix_map.clear();
   }
   clk.mark(0);
-  DPF_RETURN_IF_ERROR(
-      PlanBatchCall(hierarchy_level, static_cast<int64_t>(prefixes.size()), ctx, sum, &c));
+  // A sketch call is planned as per-key rows (every type it accepts takes the
+  // same shape in both modes, so the context ends up as the sum call's).
+  DPF_RETURN_IF_ERROR(PlanBatchCall(hierarchy_level, static_cast<int64_t>(prefixes.size()), ctx,
+                                    sum && !sketch, &c));
   const UntilBatchShape& sh = c.shape;
-  if (!device_out || capacity_bytes < sh.out_bytes)
+  if (sketch) {
+    const int64_t K = ctx.keys().num_keys();
+    const int64_t nl = static_cast<int64_t>(flat_[hierarchy_level].leaves.size());
+    if (sum && capacity_bytes < sh.n * flat_[hierarchy_level].packed_size)
+      return InvalidArgumentError("device output buffer too small");
+    if (sketch->rows < 1 || sketch->rows > DPF_HIP_SKETCH_MAX_WEIGHTS)
+      return InvalidArgumentError("num_weight_rows must be in [1, 4]");
+    if (sketch->per_row != sh.n)
+      return InvalidArgumentError("weights_per_row does not match the number of outputs");
+    if (!sketch->weights || !sketch->out ||
+        sketch->capacity_bytes < K * sketch->rows * nl * static_cast<int64_t>(sizeof(uint32_t)))
+      return InvalidArgumentError("device sketch buffer too small");
+    if (!dpf_hip_sketch_supported(&c.desc))
+      return UnimplementedError("value type not supported by the batched sketch");
+    // Fused into the key-sum kernel when the launch has its shape, the outputs
+    // are a permutation of its slots (no duplicate prefixes), and the
+    // accumulators' 32-bit offsets and uint64 sums hold; else streamed.
+    c.fused_sketch =
+        sh.P > 0 && sh.P == sh.T && sh.cnt == sh.block && sh.n < (int64_t{1} << 32) &&
+        K * sketch->rows * 16 < (int64_t{1} << 32) &&
+        dpf_hip_prefix_batch_sketch_fused(&c.desc, sh.Wk + sh.s, sh.E,
+                                          corrected_elements_per_block(hierarchy_level), 1,
+                                          ctx.index_major_ ? 1 : 0, sketch->rows) != 0;
+    c.native_sum = c.fused_sketch;
+  } else if (!device_out || capacity_bytes < sh.out_bytes) {
     return InvalidArgumentError("device output buffer too small");
+  }
 
   // Where this call's leaves go: the next call's expansion cache (not after
   // the last level).
@@ -664,7 +756,7 @@ StatusOr<int64_t> DistributedPointFunction::EvaluateUntilBatchCore(
   clk.mark(3);
 
   DPF_RETURN_IF_ERROR(
-      LaunchBatchCall(hierarchy_level, c, ctx, sum, device_out, stream));
+      LaunchBatchCall(hierarchy_level, c, ctx, sum, device_out, stream, sketch));
 
   ctx.CommitCache(target, hierarchy_level, sh.dE, hierarchy_level == H - 1, c.leaf_slot);
   if (g_timing.on()) dpf_hip_stream_sync(stream);  // attribute device time to its phase

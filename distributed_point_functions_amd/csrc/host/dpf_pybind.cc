@@ -442,6 +442,23 @@ class PyDpf {
     }
     return *r;
   }
+  int64_t EvaluateUntilBatchSketchToDevice(
+      int level, const py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& prefixes,
+      PyBatchContext& ctx, uintptr_t weights, int weight_rows, int64_t weights_per_row,
+      uintptr_t sums, int64_t sums_capacity, uintptr_t sketch, int64_t sketch_capacity,
+      uintptr_t stream) {
+    auto p = ToU128(prefixes);
+    py::gil_scoped_release nogil;
+    auto r = dpf_->EvaluateUntilBatchSketchToDevice(
+        level, MakeConstSpan(p), *ctx.ctx, reinterpret_cast<const uint32_t*>(weights), weight_rows,
+        weights_per_row, reinterpret_cast<void*>(sums), sums_capacity,
+        reinterpret_cast<uint32_t*>(sketch), sketch_capacity, reinterpret_cast<void*>(stream));
+    if (!r.ok()) {
+      py::gil_scoped_acquire g;
+      throw StatusError(r.status());
+    }
+    return *r;
+  }
   py::bytes ExportEvaluationContext(const PyBatchContext& ctx, const PyKeyBatch& host, int64_t k,
                                     uintptr_t stream) {
     return Ser(Take(dpf_->ExportEvaluationContext(*ctx.ctx, *host.b, k,
@@ -683,6 +700,7 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_at_batch_sum_to_device", &PyDpf::EvaluateAtBatchSumToDevice)
       .def("create_batch_evaluation_context", &PyDpf::CreateBatchEvaluationContext)
       .def("evaluate_until_batch_to_device", &PyDpf::EvaluateUntilBatchToDevice)
+      .def("evaluate_until_batch_sketch_to_device", &PyDpf::EvaluateUntilBatchSketchToDevice)
       .def("export_evaluation_context", &PyDpf::ExportEvaluationContext)
       .def("sum_packed_shares", &PyDpf::SumPackedShares)
       .def("parameters", &PyDpf::Parameters)

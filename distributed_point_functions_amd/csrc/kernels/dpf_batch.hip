@@ -929,11 +929,30 @@ HHLevelArgs hh_args(const BatchLevelParams& p, const dpf_value_desc* desc, int b
   return a;
 }
 
+// The fused per-key sketch of a launch (dpf_hip_eval_prefix_batch_sketch).
+struct FusedSketch {
+  int rows;
+  const uint32_t* weights;
+  uint64_t* acc;
+  uint32_t* out;
+};
+
+// The launches hh_keys_kernel takes (dispatch_batch), which are the ones that
+// can carry the fused sketch.
+bool lean_keys_shape(const dpf_value_desc* desc, int sum, int walk_levels, int expand_levels,
+                     bool has_seeds_in, int elements_per_leaf, int index_major) {
+  int b = 0;
+  return sum && !hook_is("DPF_BATCH_NO_LEAN", '1') && walk_levels == 0 && expand_levels == 2 &&
+         has_seeds_in && elements_per_leaf == 1 && mod32_eligible(desc, &b) &&
+         desc->num_leaves <= 2 && (desc->num_leaves == 1 || b == 2) && index_major;
+}
+
 // Picks the kernel by value type and shape and launches it.  *sum_words: the
 // uint64 words per summed element the kernel left in the workspace.
 int dispatch_batch(const BatchLevelParams& p, const dpf_value_desc* desc, int sum,
                    const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-                   const dpf_aes_key* key_value, hipStream_t s, int* sum_words) {
+                   const dpf_aes_key* key_value, hipStream_t s, int* sum_words,
+                   const FusedSketch* sk) {
   int b = 0;
   // The steady state of heavy hitters (start seeds from the expansion cache
   // or a gather, no walk, two expanded levels, IntModN<uint32_t> sums): the
@@ -942,12 +961,19 @@ int dispatch_batch(const BatchLevelParams& p, const dpf_value_desc* desc, int su
   const bool no_lean = hook_is("DPF_BATCH_NO_LEAN", '1');
   if (sum && !no_lean && p.walk_levels == 0 && p.expand_levels == 2 && p.seeds_in && p.epl == 1 &&
       mod32_eligible(desc, &b) && p.nl <= 2 && (p.nl == 1 || b == 2)) {
-    const HHLevelArgs a = hh_args(p, desc, b, key_left, key_right, key_value);
+    HHLevelArgs a = hh_args(p, desc, b, key_left, key_right, key_value);
+    if (sk) {
+      a.sk_rows = sk->rows;
+      a.sk_weights = sk->weights;
+      a.sk_acc = reinterpret_cast<unsigned long long*>(sk->acc);
+      a.sk_out = sk->out;
+    }
     const int st = launch_hh_level(a, s);
     if (a.index_major) *sum_words = 1;   // hh_keys_kernel sums into one uint64 per element
-    g_last_batch_kernel = a.index_major ? "hh_keys" : "hh_level";
+    g_last_batch_kernel = sk ? "hh_keys_sketch" : (a.index_major ? "hh_keys" : "hh_level");
     return st;
   }
+  if (sk) return fail(kUnimplemented, "no fused sketch for this launch");
   if (fast_int(desc)) {
     g_last_batch_kernel = "batch_level/fast";
     const int xm = desc->kind[0] == DPF_LEAF_XOR;
@@ -973,7 +999,7 @@ int dispatch_batch(const BatchLevelParams& p, const dpf_value_desc* desc, int su
 }
 }  // namespace
 
-int dpf_hip_eval_prefix_batch_layout(
+static int eval_prefix_batch_layout(
     int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
     int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
     const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
@@ -983,7 +1009,7 @@ int dpf_hip_eval_prefix_batch_layout(
     const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
     const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
     dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
-    void* stream) {
+    void* stream, const FusedSketch* sk) {
   if (int st = check_batch_levels(desc, sum, num_keys, num_starts, walk_levels, save_after,
                                   expand_levels, cw_first, cw_stride, elements_per_leaf))
     return st;
@@ -1037,7 +1063,7 @@ int dpf_hip_eval_prefix_batch_layout(
     p.rkr = expand_key(key_right);
     p.rkv = expand_key(key_value);
     p.rkd = xor_keys(p.rkl, p.rkr);
-    if (int st = dispatch_batch(p, desc, sum, key_left, key_right, key_value, s, &sum_words))
+    if (int st = dispatch_batch(p, desc, sum, key_left, key_right, key_value, s, &sum_words, sk))
       return st;
   }
   if (sum && slots > 0) {
@@ -1049,6 +1075,84 @@ int dpf_hip_eval_prefix_batch_layout(
     HIP_TRY(hipGetLastError());
   }
   return kOk;
+}
+
+int dpf_hip_eval_prefix_batch_layout(
+    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
+    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
+    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
+    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
+    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
+    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
+    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
+    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
+    void* stream) {
+  return eval_prefix_batch_layout(
+      num_keys, num_starts, walk_levels, save_after, expand_levels, cw_first, cw_stride, key_seed,
+      party, seeds_in, control_in, in_stride, parent, path, save_index, seeds_out, control_out,
+      out_stride, cw_seed, cw_left, cw_right, key_left, key_right, key_value, desc,
+      elements_per_leaf, value_correction, sum, workspace, out, leaf_cache, leaf_stride, leaf_slot,
+      index_major, stream, nullptr);
+}
+
+int dpf_hip_prefix_batch_sketch_fused(const dpf_value_desc* desc, int walk_levels,
+                                      int expand_levels, int elements_per_leaf, int has_seeds_in,
+                                      int index_major, int num_weights) {
+  if (!desc || validate_desc(desc) != kOk || hook_is("DPF_BATCH_SKETCH_FUSED", '0')) return 0;
+  return num_weights >= 1 && num_weights <= kHHSketchMaxRows &&
+                 lean_keys_shape(desc, 1, walk_levels, expand_levels, has_seeds_in != 0,
+                                 elements_per_leaf, index_major)
+             ? 1
+             : 0;
+}
+
+int dpf_hip_sketch_slot_weights(int64_t num_rows, int64_t count, const int64_t* src_offset,
+                                const dpf_value_desc* desc, int num_weights, const void* weights,
+                                void* out, void* stream) {
+  if (!desc) return fail(kInvalidArgument, "NULL pointer");
+  if (int st = validate_desc(desc)) return st;
+  int b = 0;
+  if (!mod32_eligible(desc, &b) || desc->num_leaves > 2)
+    return fail(kUnimplemented, "slot weights: at most two IntModN<uint32_t> leaves");
+  if (num_rows < 0 || count < 1 || num_weights < 1 || num_weights > kHHSketchMaxRows)
+    return fail(kInvalidArgument, "bad sizes");
+  if (num_rows == 0) return kOk;
+  if (!weights || !out) return fail(kInvalidArgument, "NULL pointer");
+  const uint32_t mod[2] = {(uint32_t)desc->mod_low[0],
+                           (uint32_t)desc->mod_low[desc->num_leaves > 1 ? 1 : 0]};
+  return launch_sketch_slot_weights(num_rows * count, count, src_offset, num_weights,
+                                    static_cast<const uint32_t*>(weights), mod,
+                                    static_cast<uint32_t*>(out), (hipStream_t)stream);
+}
+
+int dpf_hip_eval_prefix_batch_sketch(
+    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
+    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
+    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
+    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
+    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
+    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
+    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
+    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
+    int num_weights, const uint32_t* slot_weights, uint64_t* accumulators, uint32_t* sketch,
+    void* stream) {
+  if (!dpf_hip_prefix_batch_sketch_fused(desc, walk_levels, expand_levels, elements_per_leaf,
+                                         seeds_in != nullptr, index_major, num_weights) ||
+      !sum)
+    return fail(kUnimplemented, "no fused sketch for this launch (dpf_hip_prefix_batch_sketch_fused)");
+  // Four outputs per start node, each added as a term below 2^32 to a uint64.
+  if (num_starts >= (int64_t{1} << 30)) return fail(kInvalidArgument, "too many start nodes");
+  if (num_keys > 0 && num_starts > 0 && (!slot_weights || !accumulators || !sketch))
+    return fail(kInvalidArgument, "NULL pointer");
+  const FusedSketch sk{num_weights, slot_weights, accumulators, sketch};
+  return eval_prefix_batch_layout(
+      num_keys, num_starts, walk_levels, save_after, expand_levels, cw_first, cw_stride, key_seed,
+      party, seeds_in, control_in, in_stride, parent, path, save_index, seeds_out, control_out,
+      out_stride, cw_seed, cw_left, cw_right, key_left, key_right, key_value, desc,
+      elements_per_leaf, value_correction, sum, workspace, out, leaf_cache, leaf_stride, leaf_slot,
+      index_major, stream, &sk);
 }
 
 const char* dpf_hip_last_batch_kernel(void) { return g_last_batch_kernel; }

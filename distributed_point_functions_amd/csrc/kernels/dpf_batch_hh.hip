@@ -558,6 +558,241 @@ void hh_keys_kernel(HHKeysParams p) {
   }
 }
 
+// The fused per-key sketch of hh_keys_sketch_kernel.
+struct HHSketchParams {
+  const uint32_t* weights;   // [slot][J][2], reduced mod N_e; slot = (u << 2) + leaf
+  unsigned long long* acc;   // [K][J][2] sums of reduced products, zeroed before the launch
+  Div32 ranges;              // division by u_ranges (num_waves < 2^31)
+};
+
+// hh_keys_kernel with the per-key sketch fused in: after the key sum of start
+// node u, the lane that holds key k's four corrected leaves multiplies them
+// by the node's J rows of weights (wave-uniform: scalar loads) and adds the
+// J * nl sums of four reduced products to the key's uint64 accumulators with
+// vector atomics; integers below 2^34 per node, so the result does not depend
+// on the order.  The accumulators of one key are contiguous and addressed by
+// a 32-bit byte offset (the host keeps K * J * 16 below 2^32), so no 64-bit
+// address per accumulator is held across the start-node loop: with a [J][2][K]
+// layout those were seven spilled VGPRs at J = 2.
+// hh_keys_kernel above keeps its own text: instantiating it from this
+// template changed its register allocation (125 instead of 128 VGPRs), i.e.
+// the code every heavy-hitters pass runs.
+template <int J>
+__global__ __launch_bounds__(kHHKeysBlock)
+__attribute__((amdgpu_waves_per_eu(kHHWaves, kHHWaves)))
+void hh_keys_sketch_kernel(HHKeysParams p, HHSketchParams q) {
+  __shared__ HHKeysLds lds;
+  fill_tables(lds.tab);
+  __syncthreads();
+  const uint32_t lt = (threadIdx.x & 31) * 4u;
+  uint32_t m1;
+  asm volatile("v_mov_b32 %0, 0xff00" : "=v"(m1));
+  const LdsLookup lk{reinterpret_cast<const char*>(lds.tab),
+                     {lt, lt + 128u, lt + 65536u, lt + 65664u}, m1,
+                     KeySet{key_ref(p.rkl), key_ref(p.rkr), key_ref(p.rkv), KeyRef{}}};
+  const int64_t K = p.num_keys, U = p.num_starts;
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t waves_per_block = kHHKeysBlock / 64;
+  const int64_t wave0 = (int64_t)blockIdx.x * waves_per_block +
+                        __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nl = p.nl;
+  const Div32 div0 = p.div[0], div1 = p.div[1];
+  // Tasks (64 keys x a range of start nodes) by grid stride, or -- with a
+  // task counter -- taken one at a time in order, so the waves the CU's
+  // arbiter favours take more of them and all finish together (the octet
+  // kernel's items, dpf_kernels.hip; the LDS here is full, so the counter is
+  // in global memory).  Neighbouring tasks share their 64 keys.
+  auto take = [&]() -> int64_t {
+    unsigned int c = 0;
+    if (lane == 0) c = atomicAdd(p.task_counter, 1u);
+    c = __builtin_amdgcn_readfirstlane(c);
+    return (int64_t)c < p.num_waves ? (int64_t)c : p.num_waves;
+  };
+  for (int64_t w = p.task_counter ? take() : wave0; w < p.num_waves;
+       w = p.task_counter ? take() : w + (int64_t)gridDim.x * waves_per_block) {
+    // The task's key group by the host's invariant-divisor constants, on the
+    // scalar unit: the compiler's own reciprocal of u_ranges is a VGPR held
+    // for the whole kernel, the one this kernel does not have.
+    uint32_t rem;
+    const int64_t grp = div_2by1(q.ranges.sh ? (uint32_t)w >> (32 - q.ranges.sh) : 0u,
+                                 (uint32_t)w << q.ranges.sh, q.ranges.dn, q.ranges.v, rem);
+    const int64_t rng = w - grp * p.u_ranges;
+    const int64_t k_raw = grp * 64 + lane;
+    const bool valid = k_raw < K;
+    const int64_t k = valid ? k_raw : K - 1;
+    const int64_t u_begin = rng * p.u_per_range;
+    const int64_t u_end = u_begin + p.u_per_range < U ? u_begin + p.u_per_range : U;
+    const int64_t len = u_end - u_begin;
+    const int64_t rot = len > 0 ? grp % len : 0;
+    for (int64_t i = 0; i < len; ++i) {
+      int64_t ui = i + rot;
+      if (ui >= len) ui -= len;
+      const int64_t u = u_begin + ui;   // wave-uniform
+      const int64_t par = p.parent[u];
+      Block4 s = stream_load(p.seeds_in + par * K + k);
+      uint32_t t;
+      if (p.ctrl_in) {
+        t = p.ctrl_in[par * K + k] & 1u;
+      } else {
+        t = s.w0 & 1u;
+        s.w0 &= ~1u;
+      }
+      if (p.save) {
+        const int64_t save = p.save_index ? p.save_index[u] : u;
+        if (save >= 0 && valid) {
+          stream_store(p.seeds_out + save * K + k, s);
+          p.ctrl_out[save * K + k] = (uint8_t)t;
+        }
+      }
+      // Two tree levels (cc:304-347): children (ILP2), grandchildren (ILP4);
+      // leaf order 0..3 = LL, LR, RL, RR.
+      Block4 c0, c1;
+      uint32_t t0, t1;
+      {
+        const uint4 cs0 = p.key_tab[k];
+        const uint32_t cc0 = p.key_tab[2 * K + k].x & 3u;
+        children_step(lk, lk.ks.l, lk.ks.r, s, t, cs0, cc0, c0, t0, c1, t1);
+      }
+      Block4 L[4];
+      uint32_t tl[4];
+      {
+        const uint4 cs1 = p.key_tab[K + k];
+        const uint32_t cc1 = (p.key_tab[2 * K + k].x >> 2) & 3u;
+        children_step_x2(lk, lk.ks.l, lk.ks.r, c0, t0, c1, t1, cs1, cc1, L, tl);
+      }
+      if (p.leaf_seeds && valid) {
+        int4 sl = make_int4((int)(u << 2), (int)(u << 2) + 1, (int)(u << 2) + 2, (int)(u << 2) + 3);
+        if (p.leaf_slot) sl = *reinterpret_cast<const int4*>(p.leaf_slot + (u << 2));
+        const int slot[4] = {sl.x, sl.y, sl.z, sl.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          Block4 c = L[j];
+          c.w0 |= tl[j];
+          stream_store(p.leaf_seeds + slot[j] * K + k, c);
+        }
+      }
+      lds.stash[0][threadIdx.x] = make_uint4(L[2].w0 | tl[2], L[2].w1, L[2].w2, L[2].w3);
+      lds.stash[1][threadIdx.x] = make_uint4(L[3].w0 | tl[3], L[3].w1, L[3].w2, L[3].w3);
+      // Value hashes (cc:500-524), sampling, correction, party negation.
+      uint32_t v[8];   // [leaf * 2 + element]
+      // Leaves 0 and 1 are sampled before leaves 2 and 3 are hashed; the
+      // correction and negation of all four wait until after (the value
+      // correction and party are read there): fewer live registers across
+      // the second pair's hashes.
+      uint32_t tb = tl[0] | (tl[1] << 1);
+      const UniformRK rk[4] = {UniformRK{lk.ks.v}, UniformRK{lk.ks.v}, UniformRK{lk.ks.v},
+                               UniformRK{lk.ks.v}};
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr) {
+        if (pr == 1) {
+          // Same thread wrote these: no barrier needed.
+          const uint4 a = lds.stash[0][threadIdx.x], c = lds.stash[1][threadIdx.x];
+          tb |= ((a.x & 1u) << 2) | ((c.x & 1u) << 3);
+          L[2] = Block4{a.x & ~1u, a.y, a.z, a.w};
+          L[3] = Block4{c.x & ~1u, c.y, c.z, c.w};
+        }
+        Block4 h[4];
+        if (p.b == 2) {
+          hash_leaf_pair(lk, lk.ks.v, L[2 * pr], L[2 * pr + 1], h);
+        } else {
+          Block4 two[2] = {L[2 * pr], L[2 * pr + 1]};
+          dpf_aes::mmo_hashN<2>(two, lk, rk);
+          h[0] = two[0];
+          h[2] = two[1];
+          h[1] = h[3] = Block4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int leaf = 2 * pr + j;
+          sample2(nl, div0, div1, h[2 * j], h[2 * j + 1].w0, &v[leaf * 2]);
+        }
+      }
+      {
+        const uint4 meta = p.key_tab[2 * K + k];
+        const uint32_t corr[2] = {meta.y, meta.z};
+        const bool neg = (meta.x & 16u) != 0;
+#pragma unroll
+        for (int leaf = 0; leaf < 4; ++leaf) {
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const uint32_t n = e ? div1.n : div0.n;
+            uint32_t r = v[leaf * 2 + e];
+            if ((tb >> leaf) & 1u) r = mod_add(r, corr[e], n);   // int_mod_n.h:116-120
+            if (neg) r = r == 0 ? 0u : n - r;                     // int_mod_n.h:208-218
+            v[leaf * 2 + e] = (e < nl && valid) ? r : 0u;
+          }
+        }
+      }
+      // The sketch reads the corrected leaves back from the stash (free since
+      // the second leaf pair left it) after the key sum, whose lane exchanges
+      // consume v: the products' temporaries are not live beside all of v[8].
+      lds.stash[0][threadIdx.x] = make_uint4(v[0], v[1], v[2], v[3]);
+      lds.stash[1][threadIdx.x] = make_uint4(v[4], v[5], v[6], v[7]);
+      const uint32_t total = wave_sum8_mod(v, div0.n, nl > 1 ? div1.n : div0.n);
+      const int idx = lane >> 3, e = idx & 1;
+      if ((lane & 7) == 0 && e < nl && total)
+        atomicAdd(p.sums + ((u << 2) + (idx >> 1)) * nl + e, (unsigned long long)total);
+      {
+        const uint32_t* wu = q.weights + (u << 2) * (J * 2);
+        // The key's byte offset is recomputed per node from k (live anyway):
+        // held across the loop it was one more VGPR than the kernel has.
+        uint32_t k32 = (uint32_t)k;
+        asm volatile("" : "+v"(k32));
+        char* const acc_k = reinterpret_cast<char*>(q.acc) + k32 * (uint32_t)(J * 16);
+#pragma unroll
+        for (int e2 = 0; e2 < 2; ++e2) {
+          if (e2 < nl) {
+            // Same thread wrote these: no barrier needed.
+            const uint32_t* lo = reinterpret_cast<const uint32_t*>(&lds.stash[0][threadIdx.x]);
+            const uint32_t* hi = reinterpret_cast<const uint32_t*>(&lds.stash[1][threadIdx.x]);
+            const uint32_t y[4] = {lo[e2], lo[2 + e2], hi[e2], hi[2 + e2]};
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+              unsigned long long t = 0;
+#pragma unroll
+              for (int leaf = 0; leaf < 4; ++leaf)
+                t += mul_mod(wu[(leaf * J + j) * 2 + e2], y[leaf], e2 ? div1 : div0);
+              // Padding lanes (k clamped to K - 1) add 0: their v is 0.
+              atomicAdd(reinterpret_cast<unsigned long long*>(acc_k) + (j * 2 + e2), t);
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+// out[k][j][e] = acc[k][j][e] mod N_e: the fused sketch's accumulators into
+// the output layout of dpf_hip_sketch_rows.
+__global__ void sketch_finish_kernel(int64_t K, int J, int nl, Div32 d0, Div32 d1,
+                                     const unsigned long long* __restrict__ acc,
+                                     uint32_t* __restrict__ out) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < K;
+       k += (int64_t)gridDim.x * blockDim.x)
+    for (int j = 0; j < J; ++j)
+      for (int e = 0; e < nl; ++e)
+        out[(k * J + j) * nl + e] = mod64(acc[(k * J + j) * 2 + e], e ? d1 : d0);
+}
+
+// The caller's weights w[j][i] (output order) in the kernel's slot order,
+// reduced per modulus: output i = r * count + c lies at slot src_offset[r] + c
+// (the output gather's offsets; NULL: slot i).
+__global__ void sketch_slot_weights_kernel(int64_t n, int64_t count,
+                                           const int64_t* __restrict__ src_offset, int J,
+                                           const uint32_t* __restrict__ w, Div32 d0, Div32 d1,
+                                           uint32_t* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / count;
+    const int64_t slot = src_offset ? src_offset[r] + (i - r * count) : i;
+    for (int j = 0; j < J; ++j) {
+      const uint32_t x = w[j * n + i];
+      out[(slot * J + j) * 2] = mod32(x, d0);
+      out[(slot * J + j) * 2 + 1] = mod32(x, d1);
+    }
+  }
+}
+
 // The per-call key table of hh_keys_kernel: key k's
 // correction words of levels cw_level, cw_level + 1 and its control-bit
 // corrections, value correction and party, index-major so that a wave of 64
@@ -658,14 +893,40 @@ int launch_hh_keys(const HHLevelArgs& a, hipStream_t s) {
         static_cast<char*>(tab) + (size_t)a.num_keys * 3 * sizeof(uint4));
     HIP_TRY(hipMemsetAsync(p.task_counter, 0, sizeof(unsigned int), s));
   }
-  hipLaunchKernelGGL(hh_keys_kernel, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s, p);
+  if (a.sk_rows > 0) {
+    const HHSketchParams q{a.sk_weights, a.sk_acc, make_div32((uint32_t)p.u_ranges)};
+    HIP_TRY(hipMemsetAsync(a.sk_acc, 0, (size_t)a.sk_rows * 2 * a.num_keys * sizeof(uint64_t), s));
+    if (a.sk_rows == 1)
+      hipLaunchKernelGGL(hh_keys_sketch_kernel<1>, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s,
+                         p, q);
+    else
+      hipLaunchKernelGGL(hh_keys_sketch_kernel<2>, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s,
+                         p, q);
+    hipLaunchKernelGGL(sketch_finish_kernel, dim3((unsigned)g), dim3(256), 0, s, a.num_keys,
+                       a.sk_rows, a.nl, p.div[0], p.div[1], a.sk_acc, a.sk_out);
+  } else {
+    hipLaunchKernelGGL(hh_keys_kernel, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s, p);
+  }
   const hipError_t e = hipGetLastError();
   if (tab) HIP_TRY(hipFreeAsync(tab, s));
   HIP_TRY(e);
   return kOk;
 }
 
+int launch_sketch_slot_weights(int64_t n, int64_t count, const int64_t* src_offset, int rows,
+                               const uint32_t* weights, const uint32_t mod[2], uint32_t* out,
+                               hipStream_t s) {
+  int64_t g = (n + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(sketch_slot_weights_kernel, dim3((unsigned)g), dim3(256), 0, s, n, count,
+                     src_offset, rows, weights, make_div32(mod[0]), make_div32(mod[1]), out);
+  HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
 int launch_hh_level(const HHLevelArgs& a, hipStream_t s) {
+  if (a.sk_rows > 0 && (!a.index_major || a.sk_rows > kHHSketchMaxRows))
+    return fail(kUnimplemented, "hh_keys_sketch_kernel: not the fused sketch's shape");
   if (a.nl < 1 || a.nl > 2 || (a.b != 1 && a.b != 2) || (a.nl == 2 && a.b != 2))
     return fail(kUnimplemented, "hh_level_kernel: unsupported value type");
   if (a.index_major) return launch_hh_keys(a, s);

@@ -657,6 +657,33 @@ __device__ __forceinline__ uint32_t divmod128(const uint32_t w[4], const Div32& 
 }
 
 
+// x mod N for any 32-bit x: (0 : x) << sh keeps its high word below 2^sh <= dn.
+__device__ __forceinline__ uint32_t mod32(uint32_t x, const Div32& d) {
+  const int sh = d.sh;
+  uint32_t r;
+  (void)div_2by1(sh ? x >> (32 - sh) : 0u, x << sh, d.dn, d.v, r);
+  return r >> sh;
+}
+
+// (a * y) mod N for a < N and any 32-bit y: a * y < N * 2^32, so the product
+// shifted by sh has its high word below N << sh = dn (div_2by1's precondition).
+__device__ __forceinline__ uint32_t mul_mod(uint32_t a, uint32_t y, const Div32& d) {
+  const uint64_t p = ((uint64_t)a * y) << d.sh;
+  uint32_t r;
+  (void)div_2by1((uint32_t)(p >> 32), (uint32_t)p, d.dn, d.v, r);
+  return r >> d.sh;
+}
+
+// s mod N for a 64-bit s: two division steps over its words.
+__device__ __forceinline__ uint32_t mod64(uint64_t s, const Div32& d) {
+  const int sh = d.sh;
+  const uint32_t hi = (uint32_t)(s >> 32), lo = (uint32_t)s;
+  uint32_t r = sh ? hi >> (32 - sh) : 0u;
+  (void)div_2by1(r, (hi << sh) | (sh ? lo >> (32 - sh) : 0u), d.dn, d.v, r);
+  (void)div_2by1(r, lo << sh, d.dn, d.v, r);
+  return r >> sh;
+}
+
 inline Div32 make_div32(uint32_t n) {
   Div32 d;
   d.n = n;

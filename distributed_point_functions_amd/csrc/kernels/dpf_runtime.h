@@ -151,7 +151,21 @@ struct HHLevelArgs {
   const dpf_aes_key* key_left;
   const dpf_aes_key* key_right;
   const dpf_aes_key* key_value;
+  // sk_rows > 0 (index_major only, <= kHHSketchMaxRows): the fused per-key
+  // sketch under sk_weights ([slot][sk_rows][2] uint32 reduced per modulus),
+  // through the accumulators sk_acc ([sk_rows][2][num_keys] uint64, cleared
+  // by the launch) into sk_out ([key][sk_rows][nl] uint32).
+  int sk_rows;
+  const uint32_t* sk_weights;
+  unsigned long long* sk_acc;
+  uint32_t* sk_out;
 };
+constexpr int kHHSketchMaxRows = 2;
+// out[(slot*rows + j)*2 + e] = weights[j*n + i] mod mod[e] for output i at slot
+// src_offset[i / count] + i % count (NULL: slot i).
+int launch_sketch_slot_weights(int64_t n, int64_t count, const int64_t* src_offset, int rows,
+                               const uint32_t* weights, const uint32_t mod[2], uint32_t* out,
+                               hipStream_t s);
 int launch_hh_level(const HHLevelArgs& a, hipStream_t s);
 int launch_hh_keys(const HHLevelArgs& a, hipStream_t s);   // index_major == 1
 

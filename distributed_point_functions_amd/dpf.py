@@ -468,6 +468,29 @@ class DistributedPointFunction:
                      batch_ctx, bool(sum_over_keys), out.data_ptr(),
                      out.numel() * out.element_size(), s.cuda_stream)
 
+    def evaluate_until_batch_sketch_to_device(self, hierarchy_level: int, prefixes, batch_ctx,
+                                              weights, sketch_out, sums_out=None,
+                                              stream=None) -> int:
+        """evaluate_until_batch_to_device with every key's linear sketch of its
+        own output vector y_k (n elements of nl IntModN<uint32, N_e> leaves):
+        `weights` is a torch device tensor of uint32 bits, shape (J, n) with
+        1 <= J <= 4 (any 32-bit values), and
+        sketch_out[k][j][e] = (sum_i (weights[j][i] mod N_e) * y_k[i][e]) mod N_e
+        is written as K * J * nl uint32 into the torch device tensor
+        `sketch_out`.  With `sums_out`, it also receives what sum_over_keys
+        writes.  The context is left as that call leaves it.  Returns n."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream(sketch_out.device)
+        pre = prefixes if isinstance(prefixes, np.ndarray) else u128_array(prefixes)
+        if weights.dim() != 2 or weights.element_size() != 4 or not weights.is_contiguous():
+            raise ValueError("weights must be a contiguous (J, n) tensor of 32-bit elements")
+        return _call(self._impl.evaluate_until_batch_sketch_to_device, int(hierarchy_level), pre,
+                     batch_ctx, weights.data_ptr(), int(weights.shape[0]), int(weights.shape[1]),
+                     sums_out.data_ptr() if sums_out is not None else 0,
+                     sums_out.numel() * sums_out.element_size() if sums_out is not None else 0,
+                     sketch_out.data_ptr(), sketch_out.numel() * sketch_out.element_size(),
+                     s.cuda_stream)
+
     def evaluate_next_batch_to_device(self, prefixes, batch_ctx, out, sum_over_keys: bool = False,
                                       stream=None) -> int:
         """EvaluateNext for every key of the batch (h:363-365)."""

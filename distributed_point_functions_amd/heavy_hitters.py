@@ -102,6 +102,7 @@ class Server:
         self.keys = device_batch
         self.ctx = dpf.create_batch_evaluation_context(device_batch)
         self.out = torch.empty(max_outputs * 8, dtype=torch.uint8, device=device)
+        self.sketch = None   # [client][weight row][element] uint32 bits of the last sketch call
 
     def reset(self) -> None:
         """Restarts at the first level; keeps the expansion cache's buffers."""
@@ -110,9 +111,50 @@ class Server:
     def release_expansion_cache(self) -> None:
         self.ctx.release_expansion_cache()
 
-    def evaluate(self, level: int, prefixes: Sequence[int], stream=None) -> int:
-        return self.dpf.evaluate_until_batch_to_device(level, prefixes, self.ctx, self.out,
-                                                       sum_over_keys=True, stream=stream)
+    def evaluate(self, level: int, prefixes: Sequence[int], stream=None, weights=None) -> int:
+        """The level's sums over the clients into `out`; with `weights` (uint32
+        (J, n), sketch_weights) also every client's sketch of its own output
+        vector, kept on the device in `sketch` (sketches() copies it out)."""
+        if weights is None:
+            return self.dpf.evaluate_until_batch_to_device(level, prefixes, self.ctx, self.out,
+                                                           sum_over_keys=True, stream=stream)
+        import torch
+        w = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.uint32).view(np.int32))
+        w = w.to(self.out.device)
+        self.sketch = torch.empty((self.keys.num_keys, w.shape[0], len(BETA)), dtype=torch.int32,
+                                  device=self.out.device)
+        return self.dpf.evaluate_until_batch_sketch_to_device(
+            level, prefixes, self.ctx, w, self.sketch, sums_out=self.out, stream=stream)
+
+    def sketches(self) -> np.ndarray:
+        """uint32 [client][weight row][element] of the last sketch call."""
+        return self.sketch.cpu().numpy().view(np.uint32)
+
+
+def sketch_weights(seed: int, level: int, n: int) -> np.ndarray:
+    """uint32 (2, n): row 0 = r, uniform in [0, N) from a generator seeded by
+    (seed, level) -- both servers derive the same rows --, row 1 = r^2 mod N."""
+    rng = np.random.default_rng([int(seed), int(level)])
+    r = rng.integers(0, MODULUS, size=int(n), dtype=np.uint64)
+    return np.stack([r, r * r % np.uint64(MODULUS)]).astype(np.uint32)
+
+
+def check_sketches(s0: np.ndarray, s1: np.ndarray) -> np.ndarray:
+    """bool[K]: which clients' output vectors pass the unit-vector test.  s0, s1:
+    the two servers' sketches, uint32 (K, 2, 2) under sketch_weights.  With
+    Z = s0 + s1 mod N -- for a vector y, Z[j][e] = sum_i w[j][i] * y[i][e] --
+    client k passes iff Z[0][0]^2 == Z[1][0] and Z[0][1] == BETA[1] * Z[0][0]
+    (mod N): both hold identically for y = BETA at one position and 0
+    elsewhere, and for y = 0 (a client whose prefix was pruned); a vector that
+    is neither passes with probability at most 2/N over r.  Reconstructing Z in
+    one process stands in for the servers' multiplication protocol, which
+    evaluates the same two identities on shares without opening Z."""
+    n = np.uint64(MODULUS)
+    z = (np.asarray(s0, dtype=np.uint32).astype(np.uint64) +
+         np.asarray(s1, dtype=np.uint32).astype(np.uint64)) % n
+    z = z.reshape(-1, 2, 2)
+    z00 = z[:, 0, 0]
+    return (z00 * z00 % n == z[:, 1, 0]) & (z[:, 0, 1] == np.uint64(BETA[1]) * z00 % n)
 
 
 def output_values(prefixes: Sequence[int], step: int, n: int) -> List[int]:
@@ -134,25 +176,41 @@ def select(values: Sequence[int], counts: np.ndarray, top_k: int) -> List[int]:
 
 def run(dpf, servers: Sequence[Server], logs: Sequence[int], top_k: int = 1024,
         aggregate: Optional[Callable] = None, stream=None,
-        record: Optional[list] = None, keep_cache: bool = False) -> List[int]:
+        record: Optional[list] = None, keep_cache: bool = False,
+        sketch_seed: Optional[int] = None, flagged: Optional[list] = None) -> List[int]:
     """One full heavy-hitters pass over every hierarchy level.  `aggregate(level,
     packed_tensor, n)` combines per-rank sums (default: single rank).
     Returns the final candidates; appends (level, values, counts, tags) to
     `record` when given.  The servers' expansion caches (up to 64 GiB per
     buffer at 2^20 clients) are given back after the last level unless
     `keep_cache` -- a caller running pass after pass keeps them (regrowing
-    them costs seconds per pass) and releases them itself afterwards."""
+    them costs seconds per pass) and releases them itself afterwards.
+
+    With `sketch_seed`, every level also computes each client's sketch under
+    sketch_weights(sketch_seed, level, n) on both servers (two servers, each
+    holding all the clients' keys of its party) and check_sketches tests them;
+    (level, [rejected client indices]) is appended to `flagged` when given.
+    The sums still include the rejected clients: taking a rejected client out
+    is the caller's step -- evaluate its key as its own one-key batch at the
+    same prefixes and subtract that from the sums."""
     prefixes: List[int] = []
     for h, log in enumerate(logs):
         step = log - (logs[h - 1] if h else 0)
         sums = []
+        weights = None
+        if sketch_seed is not None:
+            weights = sketch_weights(sketch_seed, h, len(prefixes) << step if prefixes else 1 << log)
         for srv in servers:
-            n = srv.evaluate(h, prefixes, stream)
+            n = srv.evaluate(h, prefixes, stream) if weights is None else \
+                srv.evaluate(h, prefixes, stream, weights=weights)
             part = srv.out[: n * 8]
             if aggregate is not None:
                 sums.append(np.asarray(aggregate(h, part, n)).reshape(-1).view(np.uint32))
             else:
                 sums.append(part.cpu().numpy().view(np.uint32))
+        if weights is not None and flagged is not None:
+            ok = check_sketches(servers[0].sketches(), servers[1].sketches())
+            flagged.append((h, np.nonzero(~ok)[0].tolist()))
         tot = np.zeros(sums[0].shape, dtype=np.uint64)
         for s in sums:
             tot = (tot + s.astype(np.uint64)) % MODULUS

@@ -114,7 +114,14 @@ def load(require_gpu: bool = False):
                             ("dpf_hip_last_dot_kernel", []),
                             ("dpf_hip_select_rows", [I64, I, I, P, I64, P, I, P, P, P]),
                             ("dpf_hip_select_workspace_bytes", [I, I]),
-                            ("dpf_hip_last_select_shape", [ctypes.POINTER(ctypes.c_int64)])):
+                            ("dpf_hip_last_select_shape", [ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_sketch_rows", [I64, I64, P, P, I, I, P, P, P]),
+                            ("dpf_hip_sketch_supported", [P]),
+                            ("dpf_hip_prefix_batch_sketch_fused", [P, I, I, I, I, I, I]),
+                            ("dpf_hip_sketch_slot_weights", [I64, I64, P, P, I, P, P, P]),
+                            ("dpf_hip_eval_prefix_batch_sketch",
+                             [I64, I64, I, I, I, I, I, P, P, P, P, I64, P, P, P, P, P, I64, P, P,
+                              P, P, P, P, P, I, P, I, P, P, P, I64, P, I, I, P, P, P, P])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = types
         if hasattr(L, "dpf_hip_last_dot_kernel"):
@@ -396,6 +403,22 @@ def select_rows(num_rows: int, record_words: int, num_queries: int, sel, sel_str
     check(L.dpf_hip_select_rows(num_rows, record_words, num_queries, _p(sel), sel_stride_bytes,
                                 _p(db), 1 if accumulate else 0, _p(workspace), _p(out),
                                 _stream(stream)))
+    return out
+
+
+def sketch_rows(num_keys: int, row_len: int, desc: ValueDesc, rows, weights, out=None,
+                weight_bits: int = 32, stream=None):
+    """out[k][j][e] = (sum_i (weights[j][i] mod N_e) * rows[k][i][e]) mod N_e for
+    `rows` = num_keys rows of row_len packed elements of a tuple of
+    IntModN<uint32> (device bytes) and `weights` (J, row_len) 32-bit; returns
+    (num_keys, J, num_leaves) as an int32 tensor (the bits of uint32)."""
+    import torch
+    L = load(require_gpu=True)
+    J = int(weights.shape[0])
+    if out is None:
+        out = torch.empty((num_keys, J, desc.num_leaves), dtype=torch.int32, device=rows.device)
+    check(L.dpf_hip_sketch_rows(num_keys, row_len, ctypes.byref(desc), _p(rows), J, weight_bits,
+                                _p(weights), _p(out), _stream(stream)))
     return out
 
 

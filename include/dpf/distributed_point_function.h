@@ -347,6 +347,20 @@ class DistributedPointFunction {
                                                   Span<const uint128> prefixes,
                                                   DeviceBatchContext& ctx, void* device_out,
                                                   int64_t capacity_bytes, void* stream) const;
+  // Sketch variant: besides (optionally) the key sums of
+  // EvaluateUntilBatchSumToDevice in device_sums, every key's linear sketch
+  // of its own output vector y_k = EvaluateUntil(hierarchy_level, prefixes,
+  // ctx_k) under num_weight_rows (1..4) rows of weights_per_row == n uint32
+  // weights (device, row-major):
+  //   device_sketch[(k*J + j)*nl + e] = (sum_i (w[j][i] mod N_e) * y_k[i][e]) mod N_e
+  // for value types whose nl leaves are all IntModN<uint32_t, N_e> (others:
+  // UNIMPLEMENTED).  Leaves the context exactly as the sum call does and
+  // returns n.  All argument checks run before the context is touched.
+  StatusOr<int64_t> EvaluateUntilBatchSketchToDevice(
+      int hierarchy_level, Span<const uint128> prefixes, DeviceBatchContext& ctx,
+      const uint32_t* device_weights, int num_weight_rows, int64_t weights_per_row,
+      void* device_sums /*may be null*/, int64_t sums_capacity_bytes, uint32_t* device_sketch,
+      int64_t sketch_capacity_bytes, void* stream) const;
   // Key k's context as the EvaluationContext proto EvaluateUntil would have
   // left (lazy serialization; `host_keys` is the batch `ctx` was uploaded from).
   StatusOr<EvaluationContext> ExportEvaluationContext(const DeviceBatchContext& ctx,
@@ -453,16 +467,18 @@ class DistributedPointFunction {
   // Shared core of the two batched EvaluateUntil entry points, and its steps
   // (csrc/host/batch_context.cc): the argument checks, the host-side plan of
   // the call, and the kernel launch with the output gather.
+  struct BatchSketch;  // the sketch output mode's arguments
   StatusOr<int64_t> EvaluateUntilBatchCore(int hierarchy_level, Span<const uint128> prefixes,
                                            DeviceBatchContext& ctx, bool sum, void* device_out,
-                                           int64_t capacity_bytes, void* stream) const;
+                                           int64_t capacity_bytes, void* stream,
+                                           const BatchSketch* sketch = nullptr) const;
   struct BatchCall;
   Status CheckUntilBatchArgs(int hierarchy_level, Span<const uint128> prefixes,
                              const DeviceBatchContext& ctx) const;
   Status PlanBatchCall(int hierarchy_level, int64_t num_prefixes, const DeviceBatchContext& ctx,
                        bool sum, BatchCall* call) const;
   Status LaunchBatchCall(int hierarchy_level, BatchCall& call, DeviceBatchContext& ctx, bool sum,
-                         void* device_out, void* stream) const;
+                         void* device_out, void* stream, const BatchSketch* sketch) const;
 
   std::unique_ptr<dpf_internal::ProtoValidator> validator_;
   std::vector<int> blocks_needed_;

@@ -256,6 +256,10 @@ class DeviceBatchContext {
   void* stage_ = nullptr;
   void* stage2_ = nullptr;
   size_t parent_cap_ = 0, workspace_cap_ = 0, stage_cap_ = 0, stage2_cap_ = 0;
+  // The fused sketch's slot-order weights and per-key accumulators.
+  void* sketch_w_ = nullptr;
+  void* sketch_acc_ = nullptr;
+  size_t sketch_w_cap_ = 0, sketch_acc_cap_ = 0;
 };
 
 }  // namespace distributed_point_functions

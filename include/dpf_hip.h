@@ -550,6 +550,73 @@ int dpf_hip_prefix_batch_max_expand(const dpf_value_desc* desc, int sum);
 int dpf_hip_sum_rows(int64_t num_rows, int64_t row_len, const dpf_value_desc* desc,
                      const void* in, void* out, void* stream);
 
+/* ---- per-key linear sketches of [key][element] rows -------------------------
+ * No reference counterpart.  For a value type whose leaves are all
+ * IntModN<uint32_t, N_e> sampled from at most two blocks (what
+ * dpf_hip_sketch_supported reports; up to five leaves), `in` holds num_keys
+ * rows of row_len packed elements and `weights` num_weights rows of row_len
+ * uint32 (any 32-bit value), row-major.  For k < num_keys, j < num_weights and
+ * leaf e:
+ *   out[(k*num_weights + j)*num_leaves + e] =
+ *       ( sum_{i < row_len} (weights[j*row_len + i] mod N_e) * in[k][i][e] ) mod N_e
+ * as uint32.  Exact integer arithmetic: the map is linear mod N_e, so the two
+ * parties' sketches of one key pair add up to weights[j][i*] * beta_e (0 when
+ * no element lies on alpha's path).  One wave reduces one key's row; no
+ * atomics, no workspace.  num_weights in [1, DPF_HIP_SKETCH_MAX_WEIGHTS] and
+ * row_len < 2^32, else 3 INVALID_ARGUMENT; weight_bits must be 32 (wider
+ * fields: 12 UNIMPLEMENTED), as is every other value type. */
+#define DPF_HIP_SKETCH_MAX_WEIGHTS 4
+int dpf_hip_sketch_rows(int64_t num_keys, int64_t row_len, const dpf_value_desc* desc,
+                        const void* in, int num_weights, int weight_bits, const void* weights,
+                        void* out, void* stream);
+/* 1 when dpf_hip_sketch_rows accepts this value type, else 0.  No device is
+ * touched. */
+int dpf_hip_sketch_supported(const dpf_value_desc* desc);
+
+/* The sketch fused into the key-sum pass of a batched prefix evaluation:
+ * dpf_hip_eval_prefix_batch_layout with sum != 0 in the shape its lanes-are-
+ * keys kernel takes (index_major, no walk, two expanded levels, start seeds
+ * given, one element per leaf, at most two IntModN<uint32_t> leaves), which
+ * besides the key sums leaves
+ *   sketch[(k*num_weights + j)*num_leaves + e] =
+ *       ( sum over slots of slot_weights[(slot*num_weights + j)*2 + e] * y_k[slot][e] ) mod N_e
+ * without storing any key's row.  slot_weights holds, for every slot (u << 2)
+ * + leaf of the launch, num_weights x 2 uint32 already reduced per modulus
+ * (dpf_hip_sketch_slot_weights writes them from weights in output order);
+ * `accumulators` is num_weights * 2 * num_keys uint64 of device scratch,
+ * cleared by the call.  Integer sums below 2^64 added with atomics: the
+ * result does not depend on their order.  Every other launch, and
+ * num_weights above 2: 12 UNIMPLEMENTED and nothing is launched -- store the
+ * rows and call dpf_hip_sketch_rows.  dpf_hip_last_batch_kernel reports
+ * "hh_keys_sketch". */
+int dpf_hip_eval_prefix_batch_sketch(
+    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
+    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
+    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
+    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
+    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
+    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
+    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
+    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
+    int num_weights, const uint32_t* slot_weights, uint64_t* accumulators, uint32_t* sketch,
+    void* stream);
+/* 1 when dpf_hip_eval_prefix_batch_sketch takes a launch of this shape, else
+ * 0.  DPF_BATCH_SKETCH_FUSED=0 (read per call; A/B and test hook) turns the
+ * fused path off, DPF_BATCH_NO_LEAN=1 too.  No device is touched. */
+int dpf_hip_prefix_batch_sketch_fused(const dpf_value_desc* desc, int walk_levels,
+                                      int expand_levels, int elements_per_leaf, int has_seeds_in,
+                                      int index_major, int num_weights);
+/* Slot-order weights for the fused call: output i = r * count + c (r <
+ * num_rows, c < count) lies at slot src_offset[r] + c of the launch (the
+ * output gather's offsets; NULL: slot i), and
+ *   out[(slot*num_weights + j)*2 + e] = weights[j*num_rows*count + i] mod N_e
+ * (e = 1 repeats modulus 0 for a single leaf).  The outputs must cover every
+ * slot once (no duplicate prefixes). */
+int dpf_hip_sketch_slot_weights(int64_t num_rows, int64_t count, const int64_t* src_offset,
+                                const dpf_value_desc* desc, int num_weights, const void* weights,
+                                void* out, void* stream);
+
 /* Per-key gather (h:822-835 for a key batch):
  * out[k*num_rows*count + i*count + j] = in[k*in_row_elems + src_offset[i] + j]. */
 int dpf_hip_gather_batched(int64_t num_keys, int64_t in_row_elems, int64_t num_rows,
