@@ -100,6 +100,81 @@ StatusOr<std::pair<DcfKey, DcfKey>> DistributedComparisonFunction::GenerateKeysI
   return result;
 }
 
+// ------------------------------------------------------------ batched keygen
+Status DistributedComparisonFunction::CheckKeyBatchArgs(Span<const uint128> alphas,
+                                                        Span<const Value> betas,
+                                                        Span<const uint128> root_seeds,
+                                                        std::vector<uint128>* dpf_alphas,
+                                                        std::vector<uint128>* leaves) const {
+  const int64_t n = static_cast<int64_t>(alphas.size());
+  if (betas.size() != 1 && static_cast<int64_t>(betas.size()) != n)
+    return InvalidArgumentError("`betas` must hold one value or one per alpha");
+  // The last bit of alpha is encoded in the last level's value (cc:95-97).
+  dpf_alphas->resize(n);
+  for (int64_t k = 0; k < n; ++k) (*dpf_alphas)[k] = alphas[k] >> 1;
+  return dpf_->CheckKeyBatchArgs(MakeConstSpan(*dpf_alphas), betas,
+                                 static_cast<int64_t>(betas.size()), true, root_seeds, leaves);
+}
+
+StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedComparisonFunction::GenerateKeyBatchHost(
+    Span<const uint128> alphas, const std::vector<uint128>& dpf_alphas,
+    const std::vector<uint128>& leaves, Span<const uint128> root_seeds, int num_threads) const {
+  // GenerateKeysImpl's dpf_values for every key, as leaves: level i takes beta
+  // where bit n-1-i of alpha is set and SetToZero(beta) elsewhere, which
+  // clears integer and IntModN leaves and leaves XorWrapper leaves alone.
+  const int n = parameters_.parameters().log_domain_size();
+  const int64_t keys = static_cast<int64_t>(alphas.size());
+  const auto& f = dpf_->flat_value_type(0);
+  const size_t nl = f.leaves.size();
+  const int64_t rows = static_cast<int64_t>(leaves.size() / nl);
+  std::vector<uint128> per_level(static_cast<size_t>(keys) * n * nl);
+  for (int64_t k = 0; k < keys; ++k) {
+    const uint128* beta = leaves.data() + (rows == 1 ? 0 : k) * nl;
+    for (int i = 0; i < n; ++i) {
+      const bool current_bit = (alphas[k] & (uint128{1} << (n - i - 1))) != 0;
+      uint128* dst = per_level.data() + (static_cast<size_t>(k) * n + i) * nl;
+      for (size_t l = 0; l < nl; ++l)
+        dst[l] = current_bit || f.leaves[l].kind == dpf_internal::kLeafXor ? beta[l] : uint128{0};
+    }
+  }
+  return dpf_->GenerateKeyBatchFromLeaves(MakeConstSpan(dpf_alphas), MakeConstSpan(per_level), keys,
+                                          root_seeds, num_threads);
+}
+
+StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedComparisonFunction::GenerateKeyBatch(
+    Span<const uint128> alphas, Span<const Value> betas, Span<const uint128> root_seeds,
+    int num_threads) const {
+  std::vector<uint128> dpf_alphas, leaves;
+  DPF_RETURN_IF_ERROR(CheckKeyBatchArgs(alphas, betas, root_seeds, &dpf_alphas, &leaves));
+  return GenerateKeyBatchHost(alphas, dpf_alphas, leaves, root_seeds, num_threads);
+}
+
+StatusOr<DistributedPointFunction::DeviceKeyBatchPair>
+DistributedComparisonFunction::GenerateKeyBatchToDevice(Span<const uint128> alphas,
+                                                        Span<const Value> betas,
+                                                        Span<const uint128> root_seeds,
+                                                        void* stream) const {
+  std::vector<uint128> dpf_alphas, leaves;
+  DPF_RETURN_IF_ERROR(CheckKeyBatchArgs(alphas, betas, root_seeds, &dpf_alphas, &leaves));
+  if (!dpf_->GeneratesKeysOnDevice()) {
+    std::pair<KeyBatch, KeyBatch> host;
+    DPF_ASSIGN_OR_RETURN(host, GenerateKeyBatchHost(alphas, dpf_alphas, leaves, root_seeds, 0));
+    DistributedPointFunction::DeviceKeyBatchPair out;
+    DPF_ASSIGN_OR_RETURN(out.first, DeviceKeyBatch::Upload(host.first, stream));
+    DPF_ASSIGN_OR_RETURN(out.second, DeviceKeyBatch::Upload(host.second, stream));
+    return out;
+  }
+  // One leaf per value: the kernel's DCF mode takes one beta per key.
+  const int64_t keys = static_cast<int64_t>(alphas.size());
+  if (static_cast<int64_t>(leaves.size()) != keys) {
+    const uint128 shared = leaves.empty() ? uint128{0} : leaves[0];
+    leaves.assign(keys, shared);
+  }
+  return dpf_->GenerateKeyBatchFromLeavesToDevice(alphas, MakeConstSpan(leaves), 2,
+                                                  parameters_.parameters().log_domain_size(),
+                                                  root_seeds, stream);
+}
+
 StatusOr<KeyBatch> DistributedComparisonFunction::MakeKeyBatch(
     Span<const DcfKey* const> keys) const {
   std::vector<const DpfKey*> dpf_keys;

@@ -99,13 +99,67 @@ struct PyKeyBatch {
     if (b->num_keys) std::memcpy(a.mutable_data(), b->party.data(), b->num_keys);
     return a;
   }
+  // The correction words, [key][level]: seeds as {low, high}, control bytes.
+  py::array_t<uint64_t> CwSeeds() const { return Blocks(b->cw_seed); }
+  py::array_t<uint8_t> CwLeft() const { return Bytes(b->cw_left); }
+  py::array_t<uint8_t> CwRight() const { return Bytes(b->cw_right); }
+  int NumHierarchyLevels() const { return static_cast<int>(b->value_correction.size()); }
+  // Level h's value corrections, [key][element * leaf] as {low, high}.
+  py::array_t<uint64_t> ValueCorrection(int h) const {
+    if (h < 0 || h >= NumHierarchyLevels()) throw std::invalid_argument("hierarchy level out of range");
+    return Blocks(b->value_correction[h]);
+  }
+  static py::array_t<uint64_t> Blocks(const std::vector<dpf_block>& v) {
+    py::array_t<uint64_t> a({static_cast<py::ssize_t>(v.size()), py::ssize_t{2}});
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * 16);
+    return a;
+  }
+  static py::array_t<uint8_t> Bytes(const std::vector<uint8_t>& v) {
+    py::array_t<uint8_t> a(static_cast<py::ssize_t>(v.size()));
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size());
+    return a;
+  }
 };
 
 struct PyDeviceKeyBatch {
   std::shared_ptr<DeviceKeyBatch> d;
   int64_t NumKeys() const { return d->num_keys(); }
   int64_t FirstKey() const { return d->first_key(); }
+  PyKeyBatch Download(uintptr_t stream) const {
+    py::gil_scoped_release nogil;
+    auto r = d->Download(reinterpret_cast<void*>(stream));
+    if (!r.ok()) {
+      py::gil_scoped_acquire g;
+      throw StatusError(r.status());
+    }
+    return PyKeyBatch{std::make_shared<KeyBatch>(std::move(*r))};
+  }
 };
+
+using U64Array = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>;
+std::vector<uint128> OptU128(const py::object& o) {
+  if (o.is_none()) return {};
+  return ToU128(o.cast<U64Array>());
+}
+py::tuple DevicePair(DistributedPointFunction::DeviceKeyBatchPair&& r) {
+  return py::make_tuple(PyDeviceKeyBatch{std::shared_ptr<DeviceKeyBatch>(r.first.release())},
+                        PyDeviceKeyBatch{std::shared_ptr<DeviceKeyBatch>(r.second.release())});
+}
+py::tuple HostPair(std::pair<KeyBatch, KeyBatch>&& r) {
+  return py::make_tuple(PyKeyBatch{std::make_shared<KeyBatch>(std::move(r.first))},
+                        PyKeyBatch{std::make_shared<KeyBatch>(std::move(r.second))});
+}
+// Runs f() without the GIL and unwraps its StatusOr.
+template <typename F>
+auto TakeNoGil(F f) {
+  py::gil_scoped_release nogil;
+  auto r = f();
+  if (!r.ok()) {
+    py::gil_scoped_acquire g;
+    throw StatusError(r.status());
+  }
+  return std::move(*r);
+}
 
 // Holds the device key batch alive as long as its context.
 struct PyBatchContext {
@@ -396,6 +450,29 @@ class PyDpf {
     return py::make_tuple(PyKeyBatch{std::make_shared<KeyBatch>(std::move(r.first))},
                           PyKeyBatch{std::make_shared<KeyBatch>(std::move(r.second))});
   }
+  py::tuple GenerateKeyBatchWithBetas(const U64Array& alphas, const std::vector<py::bytes>& betas,
+                                      const py::object& root_seeds, int threads) {
+    std::vector<Value> v;
+    for (const auto& b : betas) v.push_back(Parse<Value>(b));
+    const auto a = ToU128(alphas);
+    const auto seeds = OptU128(root_seeds);
+    return HostPair(TakeNoGil([&] {
+      return dpf_->GenerateKeyBatchWithBetas(MakeConstSpan(a), MakeConstSpan(v),
+                                             MakeConstSpan(seeds), threads);
+    }));
+  }
+  py::tuple GenerateKeyBatchToDevice(const U64Array& alphas, const std::vector<py::bytes>& betas,
+                                     const py::object& root_seeds, uintptr_t stream) {
+    std::vector<Value> v;
+    for (const auto& b : betas) v.push_back(Parse<Value>(b));
+    const auto a = ToU128(alphas);
+    const auto seeds = OptU128(root_seeds);
+    return DevicePair(TakeNoGil([&] {
+      return dpf_->GenerateKeyBatchToDevice(MakeConstSpan(a), MakeConstSpan(v),
+                                            MakeConstSpan(seeds), reinterpret_cast<void*>(stream));
+    }));
+  }
+  bool GeneratesKeysOnDevice() const { return dpf_->GeneratesKeysOnDevice(); }
   int64_t EvaluateAtBatchToDevice(const PyDeviceKeyBatch& keys, int level, uintptr_t points,
                                   int64_t points_per_key, bool shared, uintptr_t out,
                                   int64_t capacity, uintptr_t stream) {
@@ -535,6 +612,29 @@ class PyDcf {
     }
     return *r;
   }
+  py::tuple GenerateKeyBatch(const U64Array& alphas, const std::vector<py::bytes>& betas,
+                             const py::object& root_seeds, int threads) {
+    std::vector<Value> v;
+    for (const auto& b : betas) v.push_back(Parse<Value>(b));
+    const auto a = ToU128(alphas);
+    const auto seeds = OptU128(root_seeds);
+    return HostPair(TakeNoGil([&] {
+      return dcf_->GenerateKeyBatch(MakeConstSpan(a), MakeConstSpan(v), MakeConstSpan(seeds),
+                                    threads);
+    }));
+  }
+  py::tuple GenerateKeyBatchToDevice(const U64Array& alphas, const std::vector<py::bytes>& betas,
+                                     const py::object& root_seeds, uintptr_t stream) {
+    std::vector<Value> v;
+    for (const auto& b : betas) v.push_back(Parse<Value>(b));
+    const auto a = ToU128(alphas);
+    const auto seeds = OptU128(root_seeds);
+    return DevicePair(TakeNoGil([&] {
+      return dcf_->GenerateKeyBatchToDevice(MakeConstSpan(a), MakeConstSpan(v),
+                                            MakeConstSpan(seeds), reinterpret_cast<void*>(stream));
+    }));
+  }
+  bool GeneratesKeysOnDevice() const { return dcf_->dpf().GeneratesKeysOnDevice(); }
   int PackedSize() const { return dcf_->dpf().flat_value_type(0).packed_size; }
   std::vector<int> HierarchyToTree() const { return dcf_->dpf().hierarchy_to_tree(); }
 
@@ -552,10 +652,12 @@ py::array_t<uint64_t> FromU128(const std::vector<uint128>& v) {
   return a;
 }
 
+struct PyMicKeyBatch;
 struct PyDeviceMicKeyBatch {
   std::shared_ptr<DeviceMicKeyBatch> d;
   int64_t NumKeys() const { return d->num_keys(); }
   int NumIntervals() const { return d->num_intervals(); }
+  PyMicKeyBatch Download(uintptr_t stream) const;
 };
 
 struct PyMicKeyBatch {
@@ -573,8 +675,36 @@ struct PyMicKeyBatch {
   }
 };
 
+PyMicKeyBatch PyDeviceMicKeyBatch::Download(uintptr_t stream) const {
+  return PyMicKeyBatch{std::make_shared<MicKeyBatch>(
+      TakeNoGil([&] { return d->Download(reinterpret_cast<void*>(stream)); }))};
+}
+
 class PyMic {
  public:
+  py::tuple GenBatch(const U64Array& r_in, const U64Array& r_out, const py::object& root_seeds,
+                     const py::object& z0) {
+    const auto ri = ToU128(r_in), ro = ToU128(r_out);
+    const auto seeds = OptU128(root_seeds), z = OptU128(z0);
+    auto r = TakeNoGil([&] {
+      return mic_->GenBatch(MakeConstSpan(ri), MakeConstSpan(ro), MakeConstSpan(seeds),
+                            MakeConstSpan(z));
+    });
+    return py::make_tuple(PyMicKeyBatch{std::make_shared<MicKeyBatch>(std::move(r.first))},
+                          PyMicKeyBatch{std::make_shared<MicKeyBatch>(std::move(r.second))});
+  }
+  py::tuple GenBatchToDevice(const U64Array& r_in, const U64Array& r_out,
+                             const py::object& root_seeds, const py::object& z0, uintptr_t stream) {
+    const auto ri = ToU128(r_in), ro = ToU128(r_out);
+    const auto seeds = OptU128(root_seeds), z = OptU128(z0);
+    auto r = TakeNoGil([&] {
+      return mic_->GenBatchToDevice(MakeConstSpan(ri), MakeConstSpan(ro), MakeConstSpan(seeds),
+                                    MakeConstSpan(z), reinterpret_cast<void*>(stream));
+    });
+    return py::make_tuple(
+        PyDeviceMicKeyBatch{std::shared_ptr<DeviceMicKeyBatch>(r.first.release())},
+        PyDeviceMicKeyBatch{std::shared_ptr<DeviceMicKeyBatch>(r.second.release())});
+  }
   static PyMic Create(const py::bytes& params) {
     PyMic r;
     r.mic_ = std::shared_ptr<MultipleIntervalContainmentGate>(
@@ -640,7 +770,8 @@ PYBIND11_MODULE(_dpf_host, m) {
   py::register_exception<StatusError>(m, "StatusError");
   py::class_<PyDeviceKeyBatch>(m, "DeviceKeyBatch")
       .def_property_readonly("num_keys", &PyDeviceKeyBatch::NumKeys)
-      .def_property_readonly("first_key", &PyDeviceKeyBatch::FirstKey);
+      .def_property_readonly("first_key", &PyDeviceKeyBatch::FirstKey)
+      .def("download", &PyDeviceKeyBatch::Download);
   py::class_<PyBatchContext>(m, "DeviceBatchContext")
       .def_property_readonly("previous_hierarchy_level", &PyBatchContext::PreviousHierarchyLevel)
       .def_property_readonly("partial_evaluations_level", &PyBatchContext::PartialEvaluationsLevel)
@@ -670,6 +801,11 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def_property_readonly("num_levels", &PyKeyBatch::NumLevels)
       .def("seeds", &PyKeyBatch::Seeds)
       .def("party", &PyKeyBatch::Party)
+      .def_property_readonly("num_hierarchy_levels", &PyKeyBatch::NumHierarchyLevels)
+      .def("cw_seeds", &PyKeyBatch::CwSeeds)
+      .def("cw_left", &PyKeyBatch::CwLeft)
+      .def("cw_right", &PyKeyBatch::CwRight)
+      .def("value_correction", &PyKeyBatch::ValueCorrection)
       .def("upload", [](const PyKeyBatch& b, int64_t begin, int64_t end, uintptr_t stream) {
         auto d = Take(DeviceKeyBatch::Upload(*b.b, begin, end, reinterpret_cast<void*>(stream)));
         return PyDeviceKeyBatch{std::shared_ptr<DeviceKeyBatch>(d.release())};
@@ -696,6 +832,9 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("parse_key_batch", &PyDpf::ParseKeyBatch)
       .def("serialize_key_batch", &PyDpf::SerializeKeyBatch)
       .def("generate_key_batch", &PyDpf::GenerateKeyBatch)
+      .def("generate_key_batch_with_betas", &PyDpf::GenerateKeyBatchWithBetas)
+      .def("generate_key_batch_to_device", &PyDpf::GenerateKeyBatchToDevice)
+      .def("generates_keys_on_device", &PyDpf::GeneratesKeysOnDevice)
       .def("evaluate_at_batch_to_device", &PyDpf::EvaluateAtBatchToDevice)
       .def("evaluate_at_batch_sum_to_device", &PyDpf::EvaluateAtBatchSumToDevice)
       .def("create_batch_evaluation_context", &PyDpf::CreateBatchEvaluationContext)
@@ -717,12 +856,16 @@ PYBIND11_MODULE(_dpf_host, m) {
            py::arg("seed_0") = py::none(), py::arg("seed_1") = py::none())
       .def("evaluate", &PyDcf::Evaluate)
       .def("make_key_batch", &PyDcf::MakeKeyBatch)
+      .def("generate_key_batch", &PyDcf::GenerateKeyBatch)
+      .def("generate_key_batch_to_device", &PyDcf::GenerateKeyBatchToDevice)
+      .def("generates_keys_on_device", &PyDcf::GeneratesKeysOnDevice)
       .def("evaluate_batch_to_device", &PyDcf::EvaluateBatchToDevice)
       .def("packed_size", &PyDcf::PackedSize)
       .def("hierarchy_to_tree", &PyDcf::HierarchyToTree);
   py::class_<PyDeviceMicKeyBatch>(m, "DeviceMicKeyBatch")
       .def_property_readonly("num_keys", &PyDeviceMicKeyBatch::NumKeys)
-      .def_property_readonly("num_intervals", &PyDeviceMicKeyBatch::NumIntervals);
+      .def_property_readonly("num_intervals", &PyDeviceMicKeyBatch::NumIntervals)
+      .def("download", &PyDeviceMicKeyBatch::Download);
   py::class_<PyMicKeyBatch>(m, "MicKeyBatch")
       .def_property_readonly("num_keys", &PyMicKeyBatch::NumKeys)
       .def_property_readonly("num_intervals", &PyMicKeyBatch::NumIntervals)
@@ -739,6 +882,8 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("eval", &PyMic::Eval)
       .def("eval_batch", &PyMic::EvalBatch)
       .def("make_key_batch", &PyMic::MakeKeyBatch)
+      .def("gen_batch", &PyMic::GenBatch)
+      .def("gen_batch_to_device", &PyMic::GenBatchToDevice)
       .def("eval_batch_to_device", &PyMic::EvalBatchToDevice)
       .def("num_unique_offsets", &PyMic::NumUniqueOffsets);
   m.def("synthetic_levels", [](int log, int64_t count, double concentration, uint64_t seed, int mef) {

@@ -56,9 +56,11 @@ StatusOr<std::unique_ptr<DeviceKeyBatch>> DeviceKeyBatch::Upload(const KeyBatch&
   DPF_RETURN_IF_ERROR(UploadRows(&d->cw_left_, b.cw_left.data() + begin * L, n * L, stream));
   DPF_RETURN_IF_ERROR(UploadRows(&d->cw_right_, b.cw_right.data() + begin * L, n * L, stream));
   d->vcw_.assign(b.value_correction.size(), nullptr);
+  d->vcw_blocks_.assign(b.value_correction.size(), 0);
   for (size_t h = 0; h < b.value_correction.size(); ++h) {
     const auto& v = b.value_correction[h];
     const int64_t per_key = b.num_keys ? static_cast<int64_t>(v.size()) / b.num_keys : 0;
+    d->vcw_blocks_[h] = per_key;
     DPF_RETURN_IF_ERROR(UploadRows(&d->vcw_[h], v.data() + begin * per_key,
                                    n * per_key * sizeof(dpf_block), stream));
   }
@@ -208,30 +210,12 @@ StatusOr<DpfKey> DistributedPointFunction::KeyFromBatch(const KeyBatch& b, int64
 }
 
 // ------------------------------------------------------------ batched keygen
-StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBatch(
-    Span<const uint128> alphas, Span<const Value> beta, Span<const uint128> root_seeds,
-    int num_threads) const {
-  // Checks of GenerateKeysIncremental (cc:619-655), once for the shared beta.
-  const int H = static_cast<int>(parameters().size());
-  if (static_cast<int>(beta.size()) != H)
-    return InvalidArgumentError(
-        "`beta` has to have the same size as `parameters` passed at construction");
-  for (int i = 0; i < H; ++i) DPF_RETURN_IF_ERROR(validator_->ValidateValue(beta[i], i));
-  const int64_t n = static_cast<int64_t>(alphas.size());
-  if (!root_seeds.empty() && static_cast<int64_t>(root_seeds.size()) != 2 * n)
-    return InvalidArgumentError("root_seeds must be empty or hold two seeds per alpha");
-  const int last_log = parameters().back().log_domain_size();
-  for (int64_t k = 0; k < n; ++k)
-    if (last_log < 128 && alphas[k] >= (static_cast<uint128>(1) << last_log))
-      return InvalidArgumentError("`alpha` must be smaller than the output domain size");
-  std::vector<std::vector<uint128>> beta_leaves(H);
-  for (int h = 0; h < H; ++h) {
-    DPF_RETURN_IF_ERROR(CheckValueCorrectionKnown(h));
-    DPF_ASSIGN_OR_RETURN(beta_leaves[h], dpf_internal::ValueToLeaves(parameters()[h].value_type(), beta[h]));
-  }
+namespace {
+// Two root seeds per key: the caller's, or fresh ones -- RAND_bytes in the
+// reference (cc:656-658); getrandom(2) here.
+StatusOr<std::vector<uint128>> RootSeeds(Span<const uint128> root_seeds, int64_t n) {
   std::vector<uint128> seeds(root_seeds.begin(), root_seeds.end());
   if (seeds.empty() && n > 0) {
-    // RAND_bytes in the reference (cc:656-658); getrandom(2) here.
     seeds.resize(2 * n);
     size_t bytes = seeds.size() * sizeof(uint128), got = 0;
     auto* p = reinterpret_cast<uint8_t*>(seeds.data());
@@ -241,6 +225,76 @@ StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBat
       got += static_cast<size_t>(r);
     }
   }
+  return seeds;
+}
+}  // namespace
+
+Status DistributedPointFunction::CheckKeyBatchArgs(Span<const uint128> alphas,
+                                                   Span<const Value> beta, int64_t rows,
+                                                   bool value_per_row,
+                                                   Span<const uint128> root_seeds,
+                                                   std::vector<uint128>* leaves) const {
+  // Checks of GenerateKeysIncremental (cc:619-655), once per distinct beta.
+  const int H = static_cast<int>(parameters().size());
+  const int per_row = value_per_row ? 1 : H;
+  if (static_cast<int64_t>(beta.size()) != rows * per_row)
+    return InvalidArgumentError(
+        "`beta` has to have the same size as `parameters` passed at construction");
+  for (int64_t r = 0; r < rows; ++r)
+    for (int i = 0; i < per_row; ++i)
+      DPF_RETURN_IF_ERROR(validator_->ValidateValue(beta[r * per_row + i], i));
+  const int64_t n = static_cast<int64_t>(alphas.size());
+  if (!root_seeds.empty() && static_cast<int64_t>(root_seeds.size()) != 2 * n)
+    return InvalidArgumentError("root_seeds must be empty or hold two seeds per alpha");
+  const int last_log = parameters().back().log_domain_size();
+  for (int64_t k = 0; k < n; ++k)
+    if (last_log < 128 && alphas[k] >= (static_cast<uint128>(1) << last_log))
+      return InvalidArgumentError("`alpha` must be smaller than the output domain size");
+  for (int h = 0; h < H; ++h) DPF_RETURN_IF_ERROR(CheckValueCorrectionKnown(h));
+  leaves->clear();
+  for (int64_t r = 0; r < rows; ++r)
+    for (int i = 0; i < per_row; ++i) {
+      DPF_ASSIGN_OR_RETURN(std::vector<uint128> v,
+                           dpf_internal::ValueToLeaves(parameters()[i].value_type(),
+                                                       beta[r * per_row + i]));
+      leaves->insert(leaves->end(), v.begin(), v.end());
+    }
+  return OkStatus();
+}
+
+StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBatch(
+    Span<const uint128> alphas, Span<const Value> beta, Span<const uint128> root_seeds,
+    int num_threads) const {
+  std::vector<uint128> leaves;
+  DPF_RETURN_IF_ERROR(CheckKeyBatchArgs(alphas, beta, 1, false, root_seeds, &leaves));
+  return GenerateKeyBatchFromLeaves(alphas, MakeConstSpan(leaves), 1, root_seeds, num_threads);
+}
+
+StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBatchWithBetas(
+    Span<const uint128> alphas, Span<const Value> betas, Span<const uint128> root_seeds,
+    int num_threads) const {
+  const int64_t n = static_cast<int64_t>(alphas.size());
+  std::vector<uint128> leaves;
+  DPF_RETURN_IF_ERROR(CheckKeyBatchArgs(alphas, betas, n, false, root_seeds, &leaves));
+  return GenerateKeyBatchFromLeaves(alphas, MakeConstSpan(leaves), n, root_seeds, num_threads);
+}
+
+StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBatchFromLeaves(
+    Span<const uint128> alphas, Span<const uint128> leaves, int64_t rows,
+    Span<const uint128> root_seeds, int num_threads) const {
+  const int H = static_cast<int>(parameters().size());
+  const int64_t n = static_cast<int64_t>(alphas.size());
+  // Level h's leaves of row r: leaves[r * row_leaves + leaf_offset[h] ...).
+  std::vector<int> leaf_offset(H);
+  int row_leaves = 0;
+  for (int h = 0; h < H; ++h) {
+    leaf_offset[h] = row_leaves;
+    row_leaves += static_cast<int>(flat_[h].leaves.size());
+  }
+  if (static_cast<int64_t>(leaves.size()) != rows * row_leaves || (rows != 1 && rows != n))
+    return InvalidArgumentError("beta leaves do not match the batch");
+  const int last_log = parameters().back().log_domain_size();
+  DPF_ASSIGN_OR_RETURN(std::vector<uint128> seeds, RootSeeds(root_seeds, n));
   const int T = tree_levels_needed();
   const int L = T - 1;
   std::pair<KeyBatch, KeyBatch> out;
@@ -260,6 +314,10 @@ StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBat
   // One key pair (cc:656-687), written straight into row k of both batches.
   auto one = [&](int64_t k) -> Status {
     const uint128 alpha = alphas[k];
+    const uint128* row = leaves.data() + (rows == 1 ? 0 : k) * row_leaves;
+    auto beta_leaves = [&](int h) {
+      return Span<const uint128>(row + leaf_offset[h], flat_[h].leaves.size());
+    };
     uint128 s[2] = {seeds[2 * k], seeds[2 * k + 1]};
     bool t[2] = {false, true};
     out.first.seed[k] = ToBlock(s[0]);
@@ -278,8 +336,7 @@ StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBat
         const int shift = last_log - parameters()[h].log_domain_size();
         const uint128 alpha_prefix = shift < 128 ? alpha >> shift : 0;
         DPF_ASSIGN_OR_RETURN(std::vector<uint128> vc,
-                             ComputeValueCorrectionLeaves(h, s, alpha_prefix,
-                                                          MakeConstSpan(beta_leaves[h]), t[1]));
+                             ComputeValueCorrectionLeaves(h, s, alpha_prefix, beta_leaves(h), t[1]));
         put_vc(h, vc);
       }
       uint128 sc;
@@ -291,8 +348,7 @@ StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBat
       out.first.cw_right[o] = out.second.cw_right[o] = ccw[1];
     }
     DPF_ASSIGN_OR_RETURN(std::vector<uint128> last,
-                         ComputeValueCorrectionLeaves(H - 1, s, alpha,
-                                                      MakeConstSpan(beta_leaves[H - 1]), t[1]));
+                         ComputeValueCorrectionLeaves(H - 1, s, alpha, beta_leaves(H - 1), t[1]));
     put_vc(H - 1, last);
     return OkStatus();
   };
@@ -317,6 +373,164 @@ StatusOr<std::pair<KeyBatch, KeyBatch>> DistributedPointFunction::GenerateKeyBat
     for (auto& th : pool) th.join();
   }
   for (const Status& st : status) DPF_RETURN_IF_ERROR(st);
+  return out;
+}
+
+// ------------------------------------------------------------ keygen on the device
+bool DistributedPointFunction::GeneratesKeysOnDevice() const {
+  const int H = static_cast<int>(parameters().size());
+  if (H > 128 || tree_levels_needed() - 1 > 128) return false;
+  for (int h = 0; h < H; ++h) {
+    const dpf_value_desc desc = MakeDesc(flat_[h], blocks_needed_[h]);
+    if (!dpf_hip_gen_keys_supported(&desc)) return false;
+  }
+  return true;
+}
+
+StatusOr<std::unique_ptr<DeviceKeyBatch>> DeviceKeyBatch::Allocate(
+    int64_t n, int L, const std::vector<int64_t>& vcw_blocks) {
+  std::unique_ptr<DeviceKeyBatch> d(new DeviceKeyBatch());
+  d->num_keys_ = n;
+  d->num_levels_ = L;
+  d->vcw_blocks_ = vcw_blocks;
+  auto alloc = [](void** p, size_t bytes) {
+    return FromHip(dpf_hip_alloc(p, std::max<size_t>(bytes, 16)));
+  };
+  DPF_RETURN_IF_ERROR(alloc(&d->seed_, n * sizeof(dpf_block)));
+  DPF_RETURN_IF_ERROR(alloc(&d->party_, n));
+  DPF_RETURN_IF_ERROR(alloc(&d->cw_seed_, n * L * sizeof(dpf_block)));
+  DPF_RETURN_IF_ERROR(alloc(&d->cw_left_, n * L));
+  DPF_RETURN_IF_ERROR(alloc(&d->cw_right_, n * L));
+  d->vcw_.assign(vcw_blocks.size(), nullptr);
+  for (size_t h = 0; h < vcw_blocks.size(); ++h)
+    DPF_RETURN_IF_ERROR(alloc(&d->vcw_[h], n * vcw_blocks[h] * sizeof(dpf_block)));
+  return d;
+}
+
+StatusOr<KeyBatch> DeviceKeyBatch::Download(void* stream) const {
+  KeyBatch b;
+  const int64_t n = num_keys_;
+  const int L = num_levels_;
+  b.num_keys = n;
+  b.num_levels = L;
+  b.seed.resize(n);
+  b.party.resize(n);
+  b.cw_seed.resize(n * L);
+  b.cw_left.resize(n * L);
+  b.cw_right.resize(n * L);
+  b.value_correction.resize(vcw_.size());
+  auto get = [&](void* dst, const void* src, size_t bytes) -> Status {
+    if (bytes == 0) return OkStatus();
+    return FromHip(dpf_hip_memcpy_d2h(dst, src, bytes, stream));
+  };
+  DPF_RETURN_IF_ERROR(get(b.seed.data(), seed_, n * sizeof(dpf_block)));
+  DPF_RETURN_IF_ERROR(get(b.party.data(), party_, n));
+  DPF_RETURN_IF_ERROR(get(b.cw_seed.data(), cw_seed_, n * L * sizeof(dpf_block)));
+  DPF_RETURN_IF_ERROR(get(b.cw_left.data(), cw_left_, n * L));
+  DPF_RETURN_IF_ERROR(get(b.cw_right.data(), cw_right_, n * L));
+  for (size_t h = 0; h < vcw_.size(); ++h) {
+    b.value_correction[h].resize(n * vcw_blocks_[h]);
+    DPF_RETURN_IF_ERROR(get(b.value_correction[h].data(), vcw_[h],
+                            n * vcw_blocks_[h] * sizeof(dpf_block)));
+  }
+  HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
+  return b;
+}
+
+StatusOr<DistributedPointFunction::DeviceKeyBatchPair>
+DistributedPointFunction::GenerateKeyBatchToDevice(Span<const uint128> alphas,
+                                                   Span<const Value> beta,
+                                                   Span<const uint128> root_seeds,
+                                                   void* stream) const {
+  const int H = static_cast<int>(parameters().size());
+  const int64_t n = static_cast<int64_t>(alphas.size());
+  // H values are shared by all keys; anything else has to be one row per key.
+  const int64_t rows = static_cast<int64_t>(beta.size()) == H ? 1 : n;
+  std::vector<uint128> leaves;
+  DPF_RETURN_IF_ERROR(CheckKeyBatchArgs(alphas, beta, rows, false, root_seeds, &leaves));
+  if (!GeneratesKeysOnDevice()) {
+    // Host generation, then the upload: the same batches.
+    std::pair<KeyBatch, KeyBatch> host;
+    DPF_ASSIGN_OR_RETURN(host, GenerateKeyBatchFromLeaves(alphas, MakeConstSpan(leaves), rows,
+                                                          root_seeds, 0));
+    DeviceKeyBatchPair out;
+    DPF_ASSIGN_OR_RETURN(out.first, DeviceKeyBatch::Upload(host.first, stream));
+    DPF_ASSIGN_OR_RETURN(out.second, DeviceKeyBatch::Upload(host.second, stream));
+    return out;
+  }
+  return GenerateKeyBatchFromLeavesToDevice(alphas, MakeConstSpan(leaves), rows == 1 ? 0 : 1, 0,
+                                            root_seeds, stream);
+}
+
+StatusOr<DistributedPointFunction::DeviceKeyBatchPair>
+DistributedPointFunction::GenerateKeyBatchFromLeavesToDevice(Span<const uint128> alphas,
+                                                             Span<const uint128> leaves,
+                                                             int beta_mode, int dcf_bits,
+                                                             Span<const uint128> root_seeds,
+                                                             void* stream) const {
+  if (!GeneratesKeysOnDevice())
+    return UnimplementedError("key generation on the device needs integer or XorWrapper values");
+  const int H = static_cast<int>(parameters().size());
+  const int64_t n = static_cast<int64_t>(alphas.size());
+  const int L = tree_levels_needed() - 1;
+  const int64_t want = beta_mode == 0 ? H : (beta_mode == 1 ? n * H : n);
+  if (beta_mode < 0 || beta_mode > 2 || static_cast<int64_t>(leaves.size()) != want)
+    return InvalidArgumentError("beta leaves do not match the batch");
+  DPF_ASSIGN_OR_RETURN(std::vector<uint128> seeds, RootSeeds(root_seeds, n));
+  std::vector<int32_t> tree_level(H), log_domain(H), blocks(H);
+  std::vector<dpf_value_desc> desc(H);
+  std::vector<int64_t> vcw_blocks(H);
+  for (int h = 0; h < H; ++h) {
+    tree_level[h] = hierarchy_to_tree()[h];
+    log_domain[h] = parameters()[h].log_domain_size();
+    blocks[h] = blocks_needed_[h];
+    desc[h] = MakeDesc(flat_[h], blocks_needed_[h]);
+    vcw_blocks[h] = static_cast<int64_t>(flat_[h].elements_per_block * flat_[h].leaves.size());
+  }
+  DeviceKeyBatchPair out;
+  DPF_ASSIGN_OR_RETURN(out.first, DeviceKeyBatch::Allocate(n, L, vcw_blocks));
+  DPF_ASSIGN_OR_RETURN(out.second, DeviceKeyBatch::Allocate(n, L, vcw_blocks));
+  if (n == 0) return out;
+  // Per-party seeds and party bytes from the host, where the root seeds are.
+  std::vector<dpf_block> s0(n), s1(n);
+  for (int64_t k = 0; k < n; ++k) {
+    s0[k] = ToBlock(seeds[2 * k]);
+    s1[k] = ToBlock(seeds[2 * k + 1]);
+  }
+  const std::vector<uint8_t> p0(n, 0), p1(n, 1);
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(out.first->seed_, s0.data(), n * sizeof(dpf_block), stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(out.second->seed_, s1.data(), n * sizeof(dpf_block), stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(out.first->party_, p0.data(), n, stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(out.second->party_, p1.data(), n, stream));
+  // The kernel's inputs: alphas, both root seeds of every key, the beta leaves.
+  static_assert(sizeof(uint128) == sizeof(dpf_block), "uint128 is a block's memory image");
+  dpf_internal::DeviceBuffer in_alphas, in_seeds, in_beta;
+  DPF_RETURN_IF_ERROR(in_alphas.Upload(alphas.data(), alphas.size(), stream));
+  DPF_RETURN_IF_ERROR(in_seeds.Upload(seeds.data(), seeds.size(), stream));
+  DPF_RETURN_IF_ERROR(in_beta.Upload(leaves.data(), leaves.size(), stream));
+  std::vector<dpf_block*> vc(H);
+  for (int h = 0; h < H; ++h) vc[h] = static_cast<dpf_block*>(out.first->vcw_[h]);
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  HIP_RETURN_IF_ERROR(dpf_hip_gen_key_batch(
+      n, L, H, tree_level.data(), log_domain.data(), blocks.data(), desc.data(),
+      in_alphas.as<dpf_block>(), in_seeds.as<dpf_block>(), in_beta.as<dpf_block>(), beta_mode,
+      dcf_bits, &kl, &kr, &kv, static_cast<dpf_block*>(out.first->cw_seed_),
+      static_cast<uint8_t*>(out.first->cw_left_), static_cast<uint8_t*>(out.first->cw_right_),
+      vc.data(), stream));
+  // Both parties' keys hold the same correction words: written once, copied
+  // device to device, each batch owning its buffers.
+  auto copy = [&](void* dst, const void* src, size_t bytes) -> Status {
+    if (bytes == 0) return OkStatus();
+    return FromHip(dpf_hip_memcpy_d2d(dst, src, bytes, stream));
+  };
+  DPF_RETURN_IF_ERROR(copy(out.second->cw_seed_, out.first->cw_seed_, n * L * sizeof(dpf_block)));
+  DPF_RETURN_IF_ERROR(copy(out.second->cw_left_, out.first->cw_left_, n * L));
+  DPF_RETURN_IF_ERROR(copy(out.second->cw_right_, out.first->cw_right_, n * L));
+  for (int h = 0; h < H; ++h)
+    DPF_RETURN_IF_ERROR(copy(out.second->vcw_[h], out.first->vcw_[h],
+                             n * vcw_blocks[h] * sizeof(dpf_block)));
+  // The input buffers are freed on return: wait for the kernel that reads them.
+  HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
   return out;
 }
 

@@ -57,6 +57,33 @@ StatusOr<std::unique_ptr<DeviceMicKeyBatch>> DeviceMicKeyBatch::Upload(const Mic
   return d;
 }
 
+StatusOr<std::unique_ptr<DeviceMicKeyBatch>> DeviceMicKeyBatch::FromKeys(
+    std::unique_ptr<DeviceKeyBatch> keys, int num_intervals,
+    const std::vector<dpf_block>& mask_share, void* stream) {
+  if (!keys || static_cast<int64_t>(mask_share.size()) != keys->num_keys() * num_intervals)
+    return InvalidArgumentError("MicKeyBatch holds the wrong number of output mask shares");
+  std::unique_ptr<DeviceMicKeyBatch> d(new DeviceMicKeyBatch());
+  d->keys_ = std::move(keys);
+  d->num_intervals_ = num_intervals;
+  const size_t bytes = mask_share.size() * sizeof(dpf_block);
+  HIP_RETURN_IF_ERROR(dpf_hip_alloc(&d->mask_share_, std::max<size_t>(bytes, 256)));
+  if (bytes)
+    HIP_RETURN_IF_ERROR(dpf_hip_memcpy_h2d(d->mask_share_, mask_share.data(), bytes, stream));
+  return d;
+}
+
+StatusOr<MicKeyBatch> DeviceMicKeyBatch::Download(void* stream) const {
+  MicKeyBatch b;
+  DPF_ASSIGN_OR_RETURN(b.dcf, keys_->Download(stream));
+  b.num_intervals = num_intervals_;
+  b.mask_share.resize(static_cast<size_t>(keys_->num_keys()) * num_intervals_);
+  if (!b.mask_share.empty())
+    HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(b.mask_share.data(), mask_share_,
+                                           b.mask_share.size() * sizeof(dpf_block), stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(stream));
+  return b;
+}
+
 // ---------------------------------------------------------------- the gate
 MultipleIntervalContainmentGate::MultipleIntervalContainmentGate(
     MicParameters mic_parameters, std::unique_ptr<DistributedComparisonFunction> dcf)
@@ -127,6 +154,23 @@ StatusOr<std::pair<MicKey, MicKey>> MultipleIntervalContainmentGate::GenWithSeed
   return GenImpl(r_in, r_out, seeds, z_0.data());
 }
 
+uint128 MultipleIntervalContainmentGate::CorrectedOutputMask(int i, uint128 r_in,
+                                                             uint128 r_out) const {
+  // Fig. 14 Gen, lines 3-5 (Lemma 1, Lemma 2 and Theorem 3 of the paper).
+  const uint128 N = uint128{1} << mic_parameters_.log_group_size();
+  const uint128 mask = N - 1;
+  const uint128 p = lower_[i], q_prime = upper_next_[i];
+  const uint128 q = Bound(mic_parameters_.intervals(i).upper_bound());
+  const uint128 alpha_p = (p + r_in) & mask, alpha_q = (q + r_in) & mask;
+  const uint128 alpha_q_prime = (q + 1 + r_in) & mask;
+  uint128 z = r_out;
+  if (alpha_p > alpha_q) z += 1;
+  if (alpha_p > p) z -= 1;
+  if (alpha_q_prime > q_prime) z += 1;
+  if (alpha_q == N - 1) z += 1;
+  return z & mask;
+}
+
 StatusOr<std::pair<MicKey, MicKey>> MultipleIntervalContainmentGate::GenImpl(
     uint128 r_in, const std::vector<uint128>& r_out, const uint128* seeds, const uint128* z_0) {
   // cc:106-126
@@ -165,23 +209,102 @@ StatusOr<std::pair<MicKey, MicKey>> MultipleIntervalContainmentGate::GenImpl(
   *keys.first.mutable_dcfkey() = std::move(dcf_keys.first);
   *keys.second.mutable_dcfkey() = std::move(dcf_keys.second);
   for (int i = 0; i < m; ++i) {
-    // Lines 3-5 (Lemma 1, Lemma 2 and Theorem 3 of the paper).
-    const uint128 p = lower_[i], q_prime = upper_next_[i];
-    const uint128 q = Bound(mic_parameters_.intervals(i).upper_bound());
-    const uint128 alpha_p = (p + r_in) & mask, alpha_q = (q + r_in) & mask;
-    const uint128 alpha_q_prime = (q + 1 + r_in) & mask;
-    uint128 z = r_out[i];
-    if (alpha_p > alpha_q) z += 1;
-    if (alpha_p > p) z -= 1;
-    if (alpha_q_prime > q_prime) z += 1;
-    if (alpha_q == N - 1) z += 1;
-    z &= mask;
+    const uint128 z = CorrectedOutputMask(i, r_in, r_out[i]);
     const uint128 share_0 = (z_0 ? z_0[i] : random[i]) & mask;
     const uint128 share_1 = (z - share_0) & mask;
     SetProtoBlock(share_0, keys.first.add_output_mask_share()->mutable_value_uint128());
     SetProtoBlock(share_1, keys.second.add_output_mask_share()->mutable_value_uint128());
   }
   return keys;
+}
+
+// ------------------------------------------------------------ batched Gen
+Status MultipleIntervalContainmentGate::GenBatchInputs(Span<const uint128> r_in,
+                                                       Span<const uint128> r_out,
+                                                       Span<const uint128> z_0,
+                                                       std::vector<uint128>* gammas,
+                                                       std::vector<dpf_block>* share_0,
+                                                       std::vector<dpf_block>* share_1) const {
+  // GenImpl's checks (cc:106-126), for every gate.
+  const int64_t gates = static_cast<int64_t>(r_in.size());
+  const int m = mic_parameters_.intervals_size();
+  if (static_cast<int64_t>(r_out.size()) != gates * m)
+    return InvalidArgumentError(
+        "Count of output masks should be equal to the number of intervals");
+  if (!z_0.empty() && z_0.size() != r_out.size())
+    return InvalidArgumentError("Count of mask shares should be equal to the number of output masks");
+  const uint128 N = uint128{1} << mic_parameters_.log_group_size();
+  const uint128 mask = N - 1;
+  for (uint128 r : r_in)
+    if (r >= N) return InvalidArgumentError("Input mask should be between 0 and 2^log_group_size");
+  for (uint128 r : r_out)
+    if (r >= N) return InvalidArgumentError("Output mask should be between 0 and 2^log_group_size");
+  std::vector<uint128> random;
+  if (z_0.empty() && !r_out.empty()) {
+    random.resize(r_out.size());
+    auto* bytes = reinterpret_cast<uint8_t*>(random.data());
+    size_t want = random.size() * sizeof(uint128), got = 0;
+    while (got < want) {
+      const ssize_t r = getrandom(bytes + got, want - got, 0);
+      if (r <= 0) return InternalError("getrandom failed");
+      got += static_cast<size_t>(r);
+    }
+  }
+  const uint128* z0 = z_0.empty() ? random.data() : z_0.data();
+  gammas->resize(gates);
+  share_0->resize(r_out.size());
+  share_1->resize(r_out.size());
+  for (int64_t g = 0; g < gates; ++g) {
+    (*gammas)[g] = (N - 1 + r_in[g]) & mask;
+    for (int i = 0; i < m; ++i) {
+      const uint128 z = CorrectedOutputMask(i, r_in[g], r_out[g * m + i]);
+      const uint128 s0 = z0[g * m + i] & mask;
+      (*share_0)[g * m + i] = ToBlock(s0);
+      (*share_1)[g * m + i] = ToBlock((z - s0) & mask);
+    }
+  }
+  return OkStatus();
+}
+
+StatusOr<std::pair<MicKeyBatch, MicKeyBatch>> MultipleIntervalContainmentGate::GenBatch(
+    Span<const uint128> r_in, Span<const uint128> r_out, Span<const uint128> root_seeds,
+    Span<const uint128> z_0) const {
+  std::vector<uint128> gammas;
+  std::pair<MicKeyBatch, MicKeyBatch> out;
+  DPF_RETURN_IF_ERROR(
+      GenBatchInputs(r_in, r_out, z_0, &gammas, &out.first.mask_share, &out.second.mask_share));
+  Value beta;  // ToValue(uint128{1})
+  beta.mutable_integer()->mutable_value_uint128()->set_low(1);
+  std::pair<KeyBatch, KeyBatch> dcf;
+  DPF_ASSIGN_OR_RETURN(dcf, dcf_->GenerateKeyBatch(MakeConstSpan(gammas),
+                                                   Span<const Value>(&beta, 1), root_seeds));
+  out.first.dcf = std::move(dcf.first);
+  out.second.dcf = std::move(dcf.second);
+  out.first.num_intervals = out.second.num_intervals = mic_parameters_.intervals_size();
+  return out;
+}
+
+StatusOr<std::pair<std::unique_ptr<DeviceMicKeyBatch>, std::unique_ptr<DeviceMicKeyBatch>>>
+MultipleIntervalContainmentGate::GenBatchToDevice(Span<const uint128> r_in,
+                                                  Span<const uint128> r_out,
+                                                  Span<const uint128> root_seeds,
+                                                  Span<const uint128> z_0, void* stream) const {
+  std::vector<uint128> gammas;
+  std::vector<dpf_block> share_0, share_1;
+  DPF_RETURN_IF_ERROR(GenBatchInputs(r_in, r_out, z_0, &gammas, &share_0, &share_1));
+  Value beta;  // ToValue(uint128{1})
+  beta.mutable_integer()->mutable_value_uint128()->set_low(1);
+  DistributedPointFunction::DeviceKeyBatchPair dcf;
+  DPF_ASSIGN_OR_RETURN(dcf, dcf_->GenerateKeyBatchToDevice(MakeConstSpan(gammas),
+                                                           Span<const Value>(&beta, 1),
+                                                           root_seeds, stream));
+  const int m = mic_parameters_.intervals_size();
+  std::pair<std::unique_ptr<DeviceMicKeyBatch>, std::unique_ptr<DeviceMicKeyBatch>> out;
+  DPF_ASSIGN_OR_RETURN(out.first,
+                       DeviceMicKeyBatch::FromKeys(std::move(dcf.first), m, share_0, stream));
+  DPF_ASSIGN_OR_RETURN(out.second,
+                       DeviceMicKeyBatch::FromKeys(std::move(dcf.second), m, share_1, stream));
+  return out;
 }
 
 StatusOr<MicKeyBatch> MultipleIntervalContainmentGate::MakeKeyBatch(

@@ -63,6 +63,38 @@ class DistributedComparisonFunction:
     def make_key_batch(self, keys: Sequence[pb.DcfKey]):
         return D._call(self._impl.make_key_batch, [k.SerializeToString() for k in keys])
 
+    def _betas(self, betas):
+        vt = self.value_type()
+        return [(b if isinstance(b, pb.Value) else D.to_value(vt, b)).SerializeToString()
+                for b in betas]
+
+    def generate_key_batch(self, alphas: Sequence[int], betas: Sequence,
+                           root_seeds: Optional[np.ndarray] = None, threads: int = 0):
+        """Both parties' key batches for every alpha, on host threads: row k is
+        generate_keys(alphas[k], beta_k, seeds) through make_key_batch.  `betas`
+        holds one value for all keys or one per key; root_seeds: uint64 (2n, 2)
+        or None for fresh randomness."""
+        al = alphas if isinstance(alphas, np.ndarray) else D.u128_array(alphas)
+        return D._call(self._impl.generate_key_batch, al, self._betas(betas), root_seeds,
+                       int(threads))
+
+    def generate_key_batch_to_device(self, alphas: Sequence[int], betas: Sequence,
+                                     root_seeds: Optional[np.ndarray] = None, stream=None):
+        """The same batches generated in device memory on `stream`."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        al = alphas if isinstance(alphas, np.ndarray) else D.u128_array(alphas)
+        return D._call(self._impl.generate_key_batch_to_device, al, self._betas(betas),
+                       root_seeds, s.cuda_stream)
+
+    def generates_keys_on_device(self) -> bool:
+        return self._impl.generates_keys_on_device()
+
+    def download_key_batch(self, device_batch, stream=None):
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return D._call(device_batch.download, s.cuda_stream)
+
     def upload_key_batch(self, batch, begin: int = 0, end: Optional[int] = None, stream=None):
         import torch
         s = stream if stream is not None else torch.cuda.current_stream()

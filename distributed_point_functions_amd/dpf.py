@@ -425,6 +425,38 @@ class DistributedPointFunction:
         al = alphas if isinstance(alphas, np.ndarray) else u128_array(alphas)
         return _call(self._impl.generate_key_batch, al, self._betas(beta), root_seeds, int(threads))
 
+    def generate_key_batch_with_betas(self, alphas: Sequence[int], betas: Sequence,
+                                      root_seeds: Optional[np.ndarray] = None, threads: int = 0):
+        """generate_key_batch with a beta of its own for every key: `betas` holds
+        len(alphas) * H values, key-major."""
+        al = alphas if isinstance(alphas, np.ndarray) else u128_array(alphas)
+        return _call(self._impl.generate_key_batch_with_betas, al, self._betas(betas), root_seeds,
+                     int(threads))
+
+    def generate_key_batch_to_device(self, alphas: Sequence[int], beta: Sequence,
+                                     root_seeds: Optional[np.ndarray] = None, stream=None):
+        """Both parties' key batches generated in device memory on `stream`:
+        the same bytes as generate_key_batch (H betas) or
+        generate_key_batch_with_betas (len(alphas) * H betas) followed by an
+        upload.  Runs the key generation kernel where
+        generates_keys_on_device(), else generates on the host and uploads."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        al = alphas if isinstance(alphas, np.ndarray) else u128_array(alphas)
+        return _call(self._impl.generate_key_batch_to_device, al, self._betas(beta), root_seeds,
+                     s.cuda_stream)
+
+    def generates_keys_on_device(self) -> bool:
+        """Whether generate_key_batch_to_device runs on the GPU (every level's
+        value type is one integer or XorWrapper leaf) or falls back to the host."""
+        return self._impl.generates_keys_on_device()
+
+    def download_key_batch(self, device_batch, stream=None):
+        """The host image of a device key batch (inverse of upload_key_batch)."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return _call(device_batch.download, s.cuda_stream)
+
     def upload_key_batch(self, batch, begin: int = 0, end: Optional[int] = None, stream=None):
         import torch
         s = stream if stream is not None else torch.cuda.current_stream()

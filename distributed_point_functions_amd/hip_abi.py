@@ -117,6 +117,9 @@ def load(require_gpu: bool = False):
                             ("dpf_hip_last_select_shape", [ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_sketch_rows", [I64, I64, P, P, I, I, P, P, P]),
                             ("dpf_hip_sketch_supported", [P]),
+                            ("dpf_hip_gen_keys_supported", [P]),
+                            ("dpf_hip_gen_key_batch",
+                             [I64, I, I, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P]),
                             ("dpf_hip_prefix_batch_sketch_fused", [P, I, I, I, I, I, I]),
                             ("dpf_hip_sketch_slot_weights", [I64, I64, P, P, I, P, P, P]),
                             ("dpf_hip_eval_prefix_batch_sketch",

@@ -88,6 +88,33 @@ class MultipleIntervalContainmentGate:
     def make_key_batch(self, keys: Sequence[pb.MicKey]):
         return D._call(self._impl.make_key_batch, [k.SerializeToString() for k in keys])
 
+    def _gen_batch_args(self, r_in, r_out, root_seeds, z_0):
+        flat = [int(v) for row in r_out for v in row]
+        z = None if z_0 is None else D.u128_array([int(v) for row in z_0 for v in row])
+        return D.u128_array(list(r_in)), D.u128_array(flat), root_seeds, z
+
+    def gen_batch(self, r_in: Sequence[int], r_out: Sequence[Sequence[int]],
+                  root_seeds: Optional[np.ndarray] = None,
+                  z_0: Optional[Sequence[Sequence[int]]] = None):
+        """gen for many gates at once, straight into key batches: gate g takes
+        r_in[g], r_out[g], root_seeds[2g], root_seeds[2g+1] (uint64 (2n, 2)) and
+        z_0[g]; None draws fresh randomness.  Returns both parties' batches."""
+        return D._call(self._impl.gen_batch, *self._gen_batch_args(r_in, r_out, root_seeds, z_0))
+
+    def gen_batch_to_device(self, r_in: Sequence[int], r_out: Sequence[Sequence[int]],
+                            root_seeds: Optional[np.ndarray] = None,
+                            z_0: Optional[Sequence[Sequence[int]]] = None, stream=None):
+        """The same batches generated in device memory on `stream`."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return D._call(self._impl.gen_batch_to_device,
+                       *self._gen_batch_args(r_in, r_out, root_seeds, z_0), s.cuda_stream)
+
+    def download_key_batch(self, device_batch, stream=None):
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return D._call(device_batch.download, s.cuda_stream)
+
     def upload_key_batch(self, batch, stream=None):
         import torch
         s = stream if stream is not None else torch.cuda.current_stream()

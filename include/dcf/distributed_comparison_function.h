@@ -70,10 +70,34 @@ class DistributedComparisonFunction {
                                           void* stream) const;
   // SoA batch of the DpfKeys inside `keys` (validated like EvaluateAt does).
   StatusOr<KeyBatch> MakeKeyBatch(Span<const DcfKey* const> keys) const;
+  // Key generation for many alphas at once, straight into SoA form: row k of
+  // the two batches is GenerateKeysWithSeeds(alphas[k], beta_k, root_seeds[2k],
+  // root_seeds[2k+1]) passed through MakeKeyBatch.  `betas` holds one value
+  // for all keys or one per key; empty root_seeds are drawn as GenerateKeys
+  // draws them.  On `num_threads` host threads (0 = hardware concurrency).
+  StatusOr<std::pair<KeyBatch, KeyBatch>> GenerateKeyBatch(Span<const uint128> alphas,
+                                                           Span<const Value> betas,
+                                                           Span<const uint128> root_seeds,
+                                                           int num_threads = 0) const;
+  // The same batches generated in device memory on `stream`
+  // (DistributedPointFunction::GenerateKeyBatchToDevice; on the GPU where
+  // dpf().GeneratesKeysOnDevice(), else on the host and uploaded).
+  StatusOr<DistributedPointFunction::DeviceKeyBatchPair> GenerateKeyBatchToDevice(
+      Span<const uint128> alphas, Span<const Value> betas, Span<const uint128> root_seeds,
+      void* stream) const;
   const DcfParameters& parameters() const { return parameters_; }
   const DistributedPointFunction& dpf() const { return *dpf_; }
 
  private:
+  // The checks of the batched generators (those of the DPF's GenerateKeyBatch
+  // on alphas >> 1), the DPF's alphas and one row of beta leaves per beta.
+  Status CheckKeyBatchArgs(Span<const uint128> alphas, Span<const Value> betas,
+                           Span<const uint128> root_seeds, std::vector<uint128>* dpf_alphas,
+                           std::vector<uint128>* leaves) const;
+  // Host generation from checked arguments.
+  StatusOr<std::pair<KeyBatch, KeyBatch>> GenerateKeyBatchHost(
+      Span<const uint128> alphas, const std::vector<uint128>& dpf_alphas,
+      const std::vector<uint128>& leaves, Span<const uint128> root_seeds, int num_threads) const;
   DistributedComparisonFunction(DcfParameters parameters,
                                 std::unique_ptr<DistributedPointFunction> dpf);
   StatusOr<std::pair<DcfKey, DcfKey>> GenerateKeysImpl(uint128 alpha, const Value& beta,

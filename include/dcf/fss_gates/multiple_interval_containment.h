@@ -39,6 +39,13 @@ class DeviceMicKeyBatch {
  public:
   static StatusOr<std::unique_ptr<DeviceMicKeyBatch>> Upload(const MicKeyBatch& batch,
                                                              void* stream);
+  // A batch around DCF keys already in device memory (GenBatchToDevice):
+  // uploads the [key][interval] mask shares on `stream`.
+  static StatusOr<std::unique_ptr<DeviceMicKeyBatch>> FromKeys(
+      std::unique_ptr<DeviceKeyBatch> keys, int num_intervals,
+      const std::vector<dpf_block>& mask_share, void* stream);
+  // The inverse of Upload, once the work queued on `stream` has written the batch.
+  StatusOr<MicKeyBatch> Download(void* stream) const;
   DeviceMicKeyBatch(const DeviceMicKeyBatch&) = delete;
   DeviceMicKeyBatch& operator=(const DeviceMicKeyBatch&) = delete;
   ~DeviceMicKeyBatch();
@@ -88,10 +95,32 @@ class MultipleIntervalContainmentGate {
                                       void* device_out, int64_t capacity_bytes, void* stream);
   // The same through host vectors: [key][interval].
   StatusOr<std::vector<uint128>> EvalBatch(Span<const MicKey* const> keys, Span<const uint128> xs);
+  // Gen for many gates at once, straight into SoA form: gate g takes r_in[g]
+  // and r_out[g*m .. (g+1)*m), m the number of intervals, and is
+  // GenWithSeeds(r_in[g], r_out_g, root_seeds[2g], root_seeds[2g+1], z_0_g)
+  // passed through MakeKeyBatch.  Empty root_seeds and empty z_0 (else one
+  // party-0 share per output mask) are drawn as Gen draws them.
+  StatusOr<std::pair<MicKeyBatch, MicKeyBatch>> GenBatch(Span<const uint128> r_in,
+                                                         Span<const uint128> r_out,
+                                                         Span<const uint128> root_seeds,
+                                                         Span<const uint128> z_0) const;
+  // The same batches in device memory: the DCF keys through
+  // DistributedComparisonFunction::GenerateKeyBatchToDevice on `stream`, the
+  // mask shares computed on the host and uploaded.
+  StatusOr<std::pair<std::unique_ptr<DeviceMicKeyBatch>, std::unique_ptr<DeviceMicKeyBatch>>>
+  GenBatchToDevice(Span<const uint128> r_in, Span<const uint128> r_out,
+                   Span<const uint128> root_seeds, Span<const uint128> z_0, void* stream) const;
   const MicParameters& parameters() const { return mic_parameters_; }
   const DistributedComparisonFunction& dcf() const { return *dcf_; }
 
  private:
+  // The i-th output mask with the corrections of Fig. 14 Gen, lines 3-5.
+  uint128 CorrectedOutputMask(int i, uint128 r_in, uint128 r_out) const;
+  // GenImpl's checks for every gate of a batch, the DCF alphas and both
+  // parties' mask shares.
+  Status GenBatchInputs(Span<const uint128> r_in, Span<const uint128> r_out,
+                        Span<const uint128> z_0, std::vector<uint128>* gammas,
+                        std::vector<dpf_block>* share_0, std::vector<dpf_block>* share_1) const;
   MultipleIntervalContainmentGate(MicParameters mic_parameters,
                                   std::unique_ptr<DistributedComparisonFunction> dcf);
   StatusOr<std::pair<MicKey, MicKey>> GenImpl(uint128 r_in, const std::vector<uint128>& r_out,

@@ -314,6 +314,52 @@ class DistributedPointFunction {
                                                            Span<const Value> beta,
                                                            Span<const uint128> root_seeds,
                                                            int num_threads = 0) const;
+  // GenerateKeyBatch with a beta of its own for every key: key k takes
+  // betas[k*H .. (k+1)*H), H = parameters().size().
+  StatusOr<std::pair<KeyBatch, KeyBatch>> GenerateKeyBatchWithBetas(
+      Span<const uint128> alphas, Span<const Value> betas, Span<const uint128> root_seeds,
+      int num_threads = 0) const;
+  // The same two batches generated in device memory on `stream` (a
+  // hipStream_t, may be null): bit-identical to GenerateKeyBatch /
+  // GenerateKeyBatchWithBetas from the same root seeds followed by Upload.
+  // `beta` holds H values shared by all keys, or alphas.size() * H of them,
+  // key-major.  The argument checks are GenerateKeyBatch's and run before the
+  // device is touched.  The walk runs on the GPU where GeneratesKeysOnDevice();
+  // other value types are generated on the host and uploaded.  The batches
+  // are written in stream order, so evaluation queued on `stream` afterwards
+  // needs no synchronisation; DeviceKeyBatch::Download brings a batch back.
+  using DeviceKeyBatchPair =
+      std::pair<std::unique_ptr<DeviceKeyBatch>, std::unique_ptr<DeviceKeyBatch>>;
+  StatusOr<DeviceKeyBatchPair> GenerateKeyBatchToDevice(Span<const uint128> alphas,
+                                                        Span<const Value> beta,
+                                                        Span<const uint128> root_seeds,
+                                                        void* stream) const;
+  // True when every hierarchy level's value type is one the device generates
+  // (a single integer or XorWrapper leaf): GenerateKeyBatchToDevice then runs
+  // the key generation kernel, else it falls back to the host.
+  bool GeneratesKeysOnDevice() const;
+  // ---- the batched generators' pieces, shared with
+  // DistributedComparisonFunction (whose DPF alphas and betas derive from its own).
+  // GenerateKeyBatch's argument checks, in its order and with its messages, and
+  // the betas as flattened leaves.  `beta` holds rows * H values
+  // (value_per_row false: row r's level h at beta[r*H + h], leaves at
+  // (*leaves)[r*S + offset of level h], S = the levels' leaf counts summed) or,
+  // with value_per_row, one value per row that every level takes (rows * the
+  // leaf count of level 0).  rows is 1 (shared) or alphas.size().
+  Status CheckKeyBatchArgs(Span<const uint128> alphas, Span<const Value> beta, int64_t rows,
+                           bool value_per_row, Span<const uint128> root_seeds,
+                           std::vector<uint128>* leaves) const;
+  // Host generation from checked arguments: `leaves` as CheckKeyBatchArgs
+  // lays out rows * H values.
+  StatusOr<std::pair<KeyBatch, KeyBatch>> GenerateKeyBatchFromLeaves(
+      Span<const uint128> alphas, Span<const uint128> leaves, int64_t rows,
+      Span<const uint128> root_seeds, int num_threads) const;
+  // Device generation from checked arguments (GeneratesKeysOnDevice() only).
+  // beta_mode as dpf_hip_gen_key_batch: 0 leaves[h], 1 leaves[k*H + h], 2 the
+  // DCF of dcf_bits bits with `alphas` the DCF's and leaves[k].
+  StatusOr<DeviceKeyBatchPair> GenerateKeyBatchFromLeavesToDevice(
+      Span<const uint128> alphas, Span<const uint128> leaves, int beta_mode, int dcf_bits,
+      Span<const uint128> root_seeds, void* stream) const;
   // EvaluateAt(key_k, hierarchy_level, points_k) for every key of a device
   // batch.  `device_points` are raw domain points (uint128 memory images) in
   // device memory: points_per_key per key ([key][point]), or one shared set of

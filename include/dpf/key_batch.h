@@ -52,6 +52,11 @@ class DeviceKeyBatch {
   DeviceKeyBatch(const DeviceKeyBatch&) = delete;
   DeviceKeyBatch& operator=(const DeviceKeyBatch&) = delete;
   ~DeviceKeyBatch();
+  // The inverse of Upload: every array copied back to host memory once the
+  // work queued on `stream` (a hipStream_t, may be null) has written it.  What
+  // DistributedPointFunction::GenerateKeyBatchToDevice made is serialized
+  // through this and SerializeKeyBatch.
+  StatusOr<KeyBatch> Download(void* stream) const;
 
   int64_t num_keys() const { return num_keys_; }
   int num_levels() const { return num_levels_; }
@@ -68,7 +73,13 @@ class DeviceKeyBatch {
   int num_hierarchy_levels() const { return static_cast<int>(vcw_.size()); }
 
  private:
+  friend class DistributedPointFunction;
   DeviceKeyBatch() = default;
+  // Device arrays for n keys of L correction words, contents undefined;
+  // vcw_blocks[h] value-correction blocks per key at hierarchy level h.
+  static StatusOr<std::unique_ptr<DeviceKeyBatch>> Allocate(int64_t n, int L,
+                                                            const std::vector<int64_t>& vcw_blocks);
+  std::vector<int64_t> vcw_blocks_;  // value-correction blocks per key, per hierarchy level
   int64_t num_keys_ = 0, first_key_ = 0;
   int num_levels_ = 0;
   void* seed_ = nullptr;

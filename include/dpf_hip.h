@@ -676,6 +676,43 @@ int dpf_hip_mic_eval_batch(int64_t num_gates, int log_group_size, const dpf_bloc
                            const dpf_aes_key* key_left, const dpf_aes_key* key_right,
                            const dpf_aes_key* key_value, dpf_block* out, void* stream);
 
+/* ---- batched key generation (SURVEY.md 8f.4 on the device) -----------------
+ * GenerateKeysIncrementalWithSeeds (distributed_point_function.cc:619-687) for
+ * num_keys alphas at once, written in the KeyBatch layout
+ * (include/dpf/key_batch.h): key pair k gets alpha alphas[k] and the root seeds
+ * root_seeds[2k] (party 0) and root_seeds[2k + 1] (party 1); the correction
+ * words, which both parties' keys share, go to cw_seed / cw_left / cw_right
+ * [k*num_levels + j] and hierarchy level h's value correction to
+ * value_correction[h][k*E_h + e] (value_correction: host array of
+ * num_hierarchy_levels device pointers).  tree_level, log_domain, blocks and
+ * desc are host arrays of num_hierarchy_levels (hierarchy_to_tree, the levels'
+ * log domain sizes, blocks_needed and value types); num_levels is the last
+ * tree level, at most 128.  `beta` holds flattened leaves (device):
+ *   beta_mode 0: beta[h], shared by all keys;
+ *   beta_mode 1: beta[k*num_hierarchy_levels + h];
+ *   beta_mode 2: the DCF of log domain dcf_bits == num_hierarchy_levels
+ *     (dcf/distributed_comparison_function.cc:79-101): alphas[k] is the DCF's
+ *     alpha, the DPF's is alphas[k] >> 1, and level h takes beta[k] where bit
+ *     dcf_bits-1-h of alphas[k] is set, else zero -- an XorWrapper is never
+ *     zeroed, as in the reference.
+ * Bit-identical to host generation from the same seeds.  Value types: those
+ * dpf_hip_gen_keys_supported reports, at every level; others 12 UNIMPLEMENTED.
+ * num_keys == 0 returns 0; NULL pointers, negative counts, level tables that
+ * are no hierarchy and other beta modes 3 INVALID_ARGUMENT.  Every check runs
+ * before any device work. */
+int dpf_hip_gen_key_batch(int64_t num_keys, int num_levels, int num_hierarchy_levels,
+                          const int32_t* tree_level, const int32_t* log_domain,
+                          const int32_t* blocks, const dpf_value_desc* desc,
+                          const dpf_block* alphas, const dpf_block* root_seeds,
+                          const dpf_block* beta, int beta_mode, int dcf_bits,
+                          const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+                          const dpf_aes_key* key_value, dpf_block* cw_seed, uint8_t* cw_left,
+                          uint8_t* cw_right, dpf_block* const* value_correction, void* stream);
+/* 1 when dpf_hip_gen_key_batch generates keys of this value type (one integer
+ * or XorWrapper leaf of 8 to 128 bits, converted directly from one block),
+ * else 0.  No device is touched. */
+int dpf_hip_gen_keys_supported(const dpf_value_desc* desc);
+
 /* ---- timing helpers (hipEvents on the given stream) ------------------------ */
 int dpf_hip_event_create(void** ev);
 int dpf_hip_event_destroy(void* ev);
