@@ -15,7 +15,7 @@
 //   * ExpandSeeds + HashExpandedSeeds + correction (cc:271-349, 500-524;
 //     h:745-808) and the per-prefix gather (h:817-836).
 // The host does O(#prefixes) bookkeeping per call; every per-key step runs in
-// one dpf_hip_eval_prefix_batch launch (csrc/kernels/dpf_batch.hip).
+// one dpf_hip_prefix_batch_level launch (csrc/kernels/dpf_batch.hip).
 #include <algorithm>
 #include <cstdio>
 #include <string>
@@ -538,8 +538,7 @@ Status DistributedPointFunction::PlanBatchCall(int hierarchy_level, int64_t P,
 // A non-identity gather (dpf_hip_gather for one row, dpf_hip_gather_batched
 // for K) then writes the caller's buffer.
 //   sketch, fused (BatchCall::fused_sketch): the native key sum's launch
-//     through dpf_hip_eval_prefix_batch_sketch, which also writes the sketch
-//     buffer; the sums go to stage_ when the caller wants none;
+//     with num_weights > 0, which also writes the sketch buffer; the sums go to stage_ when the caller wants none;
 //   sketch, streamed: K rows into stage_, gathered per key into stage2_ unless
 //     the gather is the identity, then dpf_hip_sketch_rows over those rows into
 //     the sketch buffer and, with `sum`, dpf_hip_sum_rows into the caller's.
@@ -604,29 +603,53 @@ Status DistributedPointFunction::LaunchBatchCall(int hierarchy_level, BatchCall&
     start_ctrl = ctx.partial_control();
   }
   const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
-  // The one launch: dpf_hip_eval_prefix_batch_layout, or with the fused
-  // sketch dpf_hip_eval_prefix_batch_sketch (the same arguments and four more).
-  auto launch = [&](auto fn, auto... sketch_args) {
-    return fn(K, sh.U, sh.Wk + sh.s, sh.update_ctx && !target->gather ? sh.Wk : -1, sh.E,
-              sh.cached ? hierarchy_to_tree()[ctx.previous_hierarchy_level_] : c.start_level,
-              keys.num_levels(), keys.seed(), keys.party(), start_seeds, start_ctrl, start_stride,
-              reinterpret_cast<const int32_t*>(dtab),
-              tab.need_path ? reinterpret_cast<const dpf_block*>(dtab + tab.off_path) : nullptr,
-              tab.need_save ? reinterpret_cast<const int32_t*>(dtab + tab.off_save) : nullptr,
-              static_cast<dpf_block*>(ctx.next_seeds_), static_cast<uint8_t*>(ctx.next_ctrl_), sh.T,
-              keys.cw_seed(), keys.cw_left(), keys.cw_right(), &kl, &kr, &kv, &c.desc,
-              corrected_elements_per_block(hierarchy_level), keys.value_correction(hierarchy_level),
-              c.native_sum ? 1 : 0, c.native_sum ? static_cast<uint64_t*>(ctx.workspace_) : nullptr,
-              kernel_out, static_cast<dpf_block*>(target->leaf_seeds), target->stride,
-              target->permute ? static_cast<const int32_t*>(ctx.leaf_slot_) : nullptr,
-              ctx.index_major_ ? 1 : 0, sketch_args..., stream);
-  };
-  if (c.fused_sketch)
-    HIP_RETURN_IF_ERROR(launch(dpf_hip_eval_prefix_batch_sketch, sketch->rows,
-                               static_cast<const uint32_t*>(ctx.sketch_w_),
-                               static_cast<uint64_t*>(ctx.sketch_acc_), sketch->out));
-  else
-    HIP_RETURN_IF_ERROR(launch(dpf_hip_eval_prefix_batch_layout));
+  // The one launch; the fused sketch is four more members of its arguments.
+  dpf_prefix_batch_args args = {};
+  args.struct_size = sizeof(args);
+  args.num_keys = K;
+  args.num_starts = sh.U;
+  args.walk_levels = sh.Wk + sh.s;
+  args.save_after = sh.update_ctx && !target->gather ? sh.Wk : -1;
+  args.expand_levels = sh.E;
+  args.cw_first =
+      sh.cached ? hierarchy_to_tree()[ctx.previous_hierarchy_level_] : c.start_level;
+  args.cw_stride = keys.num_levels();
+  args.key_seed = keys.seed();
+  args.party = keys.party();
+  args.seeds_in = start_seeds;
+  args.control_in = start_ctrl;
+  args.in_stride = start_stride;
+  args.parent = reinterpret_cast<const int32_t*>(dtab);
+  if (tab.need_path) args.path = reinterpret_cast<const dpf_block*>(dtab + tab.off_path);
+  if (tab.need_save) args.save_index = reinterpret_cast<const int32_t*>(dtab + tab.off_save);
+  args.seeds_out = static_cast<dpf_block*>(ctx.next_seeds_);
+  args.control_out = static_cast<uint8_t*>(ctx.next_ctrl_);
+  args.out_stride = sh.T;
+  args.cw_seed = keys.cw_seed();
+  args.cw_left = keys.cw_left();
+  args.cw_right = keys.cw_right();
+  args.key_left = &kl;
+  args.key_right = &kr;
+  args.key_value = &kv;
+  args.desc = &c.desc;
+  args.elements_per_leaf = corrected_elements_per_block(hierarchy_level);
+  args.value_correction = keys.value_correction(hierarchy_level);
+  if (c.native_sum) {
+    args.sum = 1;
+    args.workspace = static_cast<uint64_t*>(ctx.workspace_);
+  }
+  args.out = kernel_out;
+  args.leaf_cache = static_cast<dpf_block*>(target->leaf_seeds);
+  args.leaf_stride = target->stride;
+  if (target->permute) args.leaf_slot = static_cast<const int32_t*>(ctx.leaf_slot_);
+  args.index_major = ctx.index_major_ ? 1 : 0;
+  if (c.fused_sketch) {
+    args.num_weights = sketch->rows;
+    args.slot_weights = static_cast<const uint32_t*>(ctx.sketch_w_);
+    args.accumulators = static_cast<uint64_t*>(ctx.sketch_acc_);
+    args.sketch = sketch->out;
+  }
+  HIP_RETURN_IF_ERROR(dpf_hip_prefix_batch_level(&args, stream));
 
   if (streamed) {
     const void* key_rows = kernel_out;

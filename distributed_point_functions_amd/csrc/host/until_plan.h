@@ -151,7 +151,7 @@ class StartSlotOf {
   const int32_t* phys_;
 };
 
-// The slot table of an in-place rewrite (dpf_hip_eval_prefix_batch_cached_slots):
+// The slot table of an in-place rewrite (leaf_slot of dpf_prefix_batch_args):
 // start node u = (tree index u >> s, sub-node) reads physical slot
 // start_slot[u >> s]; its 2^E leaves go to slot[(u << E) + l].  A slot read by
 // exactly one start node (s == 0) takes that node's leaf 0; every other leaf

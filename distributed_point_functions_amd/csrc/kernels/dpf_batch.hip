@@ -46,7 +46,7 @@ using namespace dpf_rt;
 
 namespace {
 
-// Which kernel the calling thread's last dpf_hip_eval_prefix_batch_cached ran
+// Which kernel the calling thread's last dpf_hip_prefix_batch_level ran
 // (dpf_hip_last_batch_kernel: dispatch checks in the tests).
 thread_local const char* g_last_batch_kernel = "";
 
@@ -698,32 +698,6 @@ int dpf_hip_prefix_batch_max_expand(const dpf_value_desc* desc, int sum) {
   return sum ? -1 : 3;
 }
 
-int dpf_hip_eval_prefix_batch(int64_t num_keys, int64_t num_starts, int walk_levels,
-                              int save_after, int expand_levels, int cw_first, int cw_stride,
-                              const dpf_block* key_seed, const uint8_t* party,
-                              const dpf_block* seeds_in, const uint8_t* control_in,
-                              int64_t in_stride, const int32_t* parent, const dpf_block* path,
-                              const int32_t* save_index, dpf_block* seeds_out,
-                              uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed,
-                              const uint8_t* cw_left, const uint8_t* cw_right,
-                              const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-                              const dpf_aes_key* key_value, const dpf_value_desc* desc,
-                              int elements_per_leaf, const dpf_block* value_correction, int sum,
-                              uint64_t* workspace, void* out, void* stream) {
-  return dpf_hip_eval_prefix_batch_cached(
-      num_keys, num_starts, walk_levels, save_after, expand_levels, cw_first, cw_stride, key_seed,
-      party, seeds_in, control_in, in_stride, parent, path, save_index, seeds_out, control_out,
-      out_stride, cw_seed, cw_left, cw_right, key_left, key_right, key_value, desc,
-      elements_per_leaf, value_correction, sum, workspace, out, nullptr, 0, stream);
-}
-
-int dpf_hip_gather_seeds(int64_t num_keys, int64_t num_rows, const int64_t* slot,
-                         const dpf_block* cache, int64_t cache_stride, dpf_block* seeds_out,
-                         uint8_t* control_out, void* stream) {
-  return dpf_hip_gather_seeds_layout(num_keys, num_rows, slot, cache, cache_stride, seeds_out,
-                                     control_out, 0, stream);
-}
-
 int dpf_hip_gather_seeds_layout(int64_t num_keys, int64_t num_rows, const int64_t* slot,
                                 const dpf_block* cache, int64_t cache_stride, dpf_block* seeds_out,
                                 uint8_t* control_out, int index_major, void* stream) {
@@ -752,42 +726,6 @@ int dpf_hip_gather_seeds_layout(int64_t num_keys, int64_t num_rows, const int64_
                      num_keys, num_rows, slot, cache, cache_stride, seeds_out, control_out, kpl);
   HIP_TRY(hipGetLastError());
   return kOk;
-}
-
-int dpf_hip_eval_prefix_batch_cached(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, void* stream) {
-  return dpf_hip_eval_prefix_batch_cached_slots(
-      num_keys, num_starts, walk_levels, save_after, expand_levels, cw_first, cw_stride, key_seed,
-      party, seeds_in, control_in, in_stride, parent, path, save_index, seeds_out, control_out,
-      out_stride, cw_seed, cw_left, cw_right, key_left, key_right, key_value, desc,
-      elements_per_leaf, value_correction, sum, workspace, out, leaf_cache, leaf_stride, nullptr,
-      stream);
-}
-
-int dpf_hip_eval_prefix_batch_cached_slots(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, void* stream) {
-  return dpf_hip_eval_prefix_batch_layout(
-      num_keys, num_starts, walk_levels, save_after, expand_levels, cw_first, cw_stride, key_seed,
-      party, seeds_in, control_in, in_stride, parent, path, save_index, seeds_out, control_out,
-      out_stride, cw_seed, cw_left, cw_right, key_left, key_right, key_value, desc,
-      elements_per_leaf, value_correction, sum, workspace, out, leaf_cache, leaf_stride, leaf_slot,
-      0, stream);
 }
 
 namespace {
@@ -820,33 +758,31 @@ int check_slot_table(int64_t num_starts, int expand_levels, const int32_t* paren
   return kOk;
 }
 
-// The checks of dpf_hip_eval_prefix_batch* that read no pointer but `desc`:
+// The checks of dpf_hip_prefix_batch_level that read no pointer but `desc`:
 // the value type and the level arithmetic.
-int check_batch_levels(const dpf_value_desc* desc, int sum, int64_t num_keys, int64_t num_starts,
-                       int walk_levels, int save_after, int expand_levels, int cw_first,
-                       int cw_stride, int elements_per_leaf) {
-  int st = validate_desc(desc);
+int check_batch_levels(const dpf_prefix_batch_args& a) {
+  int st = validate_desc(a.desc);
   if (st) return st;
-  const int max_e = dpf_hip_prefix_batch_max_expand(desc, sum);
+  const int max_e = dpf_hip_prefix_batch_max_expand(a.desc, a.sum);
   if (max_e < 0)
     return fail(kUnimplemented, "no on-device key sum for this value type (use store mode)");
-  if (num_keys < 0 || num_starts < 0 || num_starts > INT32_MAX || walk_levels < 0 ||
-      expand_levels < 0 || expand_levels > max_e || save_after < -1 || save_after > walk_levels ||
-      cw_first < 0 || cw_first + walk_levels + expand_levels > cw_stride ||
-      walk_levels > 128 || cw_stride > 4096)
+  if (a.num_keys < 0 || a.num_starts < 0 || a.num_starts > INT32_MAX || a.walk_levels < 0 ||
+      a.expand_levels < 0 || a.expand_levels > max_e || a.save_after < -1 ||
+      a.save_after > a.walk_levels || a.cw_first < 0 ||
+      a.cw_first + a.walk_levels + a.expand_levels > a.cw_stride || a.walk_levels > 128 ||
+      a.cw_stride > 4096)
     return fail(kInvalidArgument, "level arguments out of range");
-  if (elements_per_leaf < 1 || elements_per_leaf > desc->elements_per_block)
+  if (a.elements_per_leaf < 1 || a.elements_per_leaf > a.desc->elements_per_block)
     return fail(kInvalidArgument, "elements_per_leaf must be in [1, elements_per_block]");
   return kOk;
 }
 
 // The pointers a launch with work to do (keys and start nodes) reads or writes.
-int check_batch_pointers(const BatchLevelParams& p, int sum, const dpf_aes_key* key_left,
-                         const dpf_aes_key* key_right, const dpf_aes_key* key_value) {
-  if (!p.party || !p.vcw || !key_left || !key_right || !key_value || (!sum && !p.out) ||
-      (!p.seeds_in && !p.key_seed) || (p.seeds_in && !p.parent) ||
-      (p.walk_levels > 0 && !p.path) || (p.save_after >= 0 && (!p.seeds_out || !p.ctrl_out)) ||
-      (p.walk_levels + p.expand_levels > 0 && (!p.cw_seed || !p.cw_left || !p.cw_right)))
+int check_batch_pointers(const dpf_prefix_batch_args& a) {
+  if (!a.party || !a.value_correction || !a.key_left || !a.key_right || !a.key_value ||
+      (!a.sum && !a.out) || (!a.seeds_in && !a.key_seed) || (a.seeds_in && !a.parent) ||
+      (a.walk_levels > 0 && !a.path) || (a.save_after >= 0 && (!a.seeds_out || !a.control_out)) ||
+      (a.walk_levels + a.expand_levels > 0 && (!a.cw_seed || !a.cw_left || !a.cw_right)))
     return fail(kInvalidArgument, "NULL pointer");
   return kOk;
 }
@@ -867,75 +803,23 @@ void plan_key_chunks(BatchLevelParams* p) {
 
 // The expansion cache the launch writes: room for every leaf, and no overlap
 // with the start seeds except in place through a slot table.
-int attach_leaf_cache(BatchLevelParams* p, dpf_block* leaf_cache, int64_t leaf_stride,
-                      const int32_t* leaf_slot, hipStream_t s) {
-  if (leaf_stride < (p->num_starts << p->expand_levels))
+int check_leaf_cache(const dpf_prefix_batch_args& a, hipStream_t s) {
+  if (a.leaf_stride < (a.num_starts << a.expand_levels))
     return fail(kInvalidArgument, "expansion cache too small");
   // In place (leaf_cache == seeds_in) only through a slot table, whose
   // contract (include/dpf_hip.h) keeps every entry's read before its write.
-  const bool in_place =
-      leaf_slot && leaf_cache == p->seeds_in && p->in_stride == leaf_stride && !p->ctrl_in;
-  if (p->seeds_in && !in_place &&
-      (const void*)leaf_cache < (const void*)(p->seeds_in + p->num_keys * p->in_stride) &&
-      (const void*)p->seeds_in < (const void*)(leaf_cache + p->num_keys * leaf_stride))
+  const bool in_place = a.leaf_slot && a.leaf_cache == a.seeds_in &&
+                        a.in_stride == a.leaf_stride && !a.control_in;
+  if (a.seeds_in && !in_place &&
+      (const void*)a.leaf_cache < (const void*)(a.seeds_in + a.num_keys * a.in_stride) &&
+      (const void*)a.seeds_in < (const void*)(a.leaf_cache + a.num_keys * a.leaf_stride))
     return fail(kInvalidArgument, "expansion cache overlaps the start seeds");
-  p->leaf_seeds = leaf_cache;
-  p->leaf_stride = leaf_stride;
-  p->leaf_slot = leaf_slot;
-  if (leaf_slot && p->seeds_in && hook_is("DPF_HIP_CHECK_SLOTS", '1')) {
+  if (a.leaf_slot && a.seeds_in && hook_is("DPF_HIP_CHECK_SLOTS", '1')) {
     HIP_TRY(hipStreamSynchronize(s));
-    return check_slot_table(p->num_starts, p->expand_levels, p->parent, leaf_slot, leaf_stride);
+    return check_slot_table(a.num_starts, a.expand_levels, a.parent, a.leaf_slot, a.leaf_stride);
   }
   return kOk;
 }
-
-// The lean kernels' arguments (dpf_batch_hh.hip) for a launch that walks no
-// level and expands two: `b` bytes per IntModN<uint32_t> leaf.
-HHLevelArgs hh_args(const BatchLevelParams& p, const dpf_value_desc* desc, int b,
-                    const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-                    const dpf_aes_key* key_value) {
-  HHLevelArgs a;
-  memset(&a, 0, sizeof(a));
-  a.num_keys = p.num_keys;
-  a.num_starts = p.num_starts;
-  a.cw_level = p.cw_first;
-  a.cw_stride = p.cw_stride;
-  a.seeds_in = p.seeds_in;
-  a.ctrl_in = p.ctrl_in;
-  a.in_stride = p.in_stride;
-  a.parent = p.parent;
-  a.save = p.save_after == 0 && p.seeds_out;
-  a.save_index = p.save_index;
-  a.seeds_out = p.seeds_out;
-  a.ctrl_out = p.ctrl_out;
-  a.out_stride = p.out_stride;
-  a.cw_seed = p.cw_seed;
-  a.cw_left = p.cw_left;
-  a.cw_right = p.cw_right;
-  a.vcw = p.vcw;
-  a.vcw_stride = p.vcw_stride;
-  a.party = p.party;
-  a.wide = p.wide;
-  a.leaf_seeds = p.leaf_seeds;
-  a.leaf_stride = p.leaf_stride;
-  a.leaf_slot = p.leaf_slot;
-  a.nl = p.nl;
-  a.b = b;
-  a.index_major = p.index_major;
-  for (int k = 0; k < p.nl; ++k) a.mod[k] = (uint32_t)desc->mod_low[k];
-  a.key_left = key_left;
-  a.key_right = key_right;
-  a.key_value = key_value;
-  return a;
-}
-
-// The fused per-key sketch of a launch (dpf_hip_eval_prefix_batch_sketch).
-struct FusedSketch {
-  int rows;
-  const uint32_t* weights;
-  uint64_t* acc;
-  uint32_t* out;
-};
 
 // The launches hh_keys_kernel takes (dispatch_batch), which are the ones that
 // can carry the fused sketch.
@@ -949,10 +833,11 @@ bool lean_keys_shape(const dpf_value_desc* desc, int sum, int walk_levels, int e
 
 // Picks the kernel by value type and shape and launches it.  *sum_words: the
 // uint64 words per summed element the kernel left in the workspace.
-int dispatch_batch(const BatchLevelParams& p, const dpf_value_desc* desc, int sum,
-                   const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-                   const dpf_aes_key* key_value, hipStream_t s, int* sum_words,
-                   const FusedSketch* sk) {
+int dispatch_batch(const BatchLevelParams& p, const dpf_prefix_batch_args& a, hipStream_t s,
+                   int* sum_words) {
+  const dpf_value_desc* desc = a.desc;
+  const int sum = a.sum;
+  const bool sk = a.num_weights != 0;   // the fused per-key sketch
   int b = 0;
   // The steady state of heavy hitters (start seeds from the expansion cache
   // or a gather, no walk, two expanded levels, IntModN<uint32_t> sums): the
@@ -961,16 +846,9 @@ int dispatch_batch(const BatchLevelParams& p, const dpf_value_desc* desc, int su
   const bool no_lean = hook_is("DPF_BATCH_NO_LEAN", '1');
   if (sum && !no_lean && p.walk_levels == 0 && p.expand_levels == 2 && p.seeds_in && p.epl == 1 &&
       mod32_eligible(desc, &b) && p.nl <= 2 && (p.nl == 1 || b == 2)) {
-    HHLevelArgs a = hh_args(p, desc, b, key_left, key_right, key_value);
-    if (sk) {
-      a.sk_rows = sk->rows;
-      a.sk_weights = sk->weights;
-      a.sk_acc = reinterpret_cast<unsigned long long*>(sk->acc);
-      a.sk_out = sk->out;
-    }
-    const int st = launch_hh_level(a, s);
-    if (a.index_major) *sum_words = 1;   // hh_keys_kernel sums into one uint64 per element
-    g_last_batch_kernel = sk ? "hh_keys_sketch" : (a.index_major ? "hh_keys" : "hh_level");
+    const int st = launch_hh_level(a, b, s);
+    if (p.index_major) *sum_words = 1;   // hh_keys_kernel sums into one uint64 per element
+    g_last_batch_kernel = sk ? "hh_keys_sketch" : (p.index_major ? "hh_keys" : "hh_level");
     return st;
   }
   if (sk) return fail(kUnimplemented, "no fused sketch for this launch");
@@ -998,103 +876,6 @@ int dispatch_batch(const BatchLevelParams& p, const dpf_value_desc* desc, int su
   return launch_batch<GenericV, 3, false>(p, v, s);
 }
 }  // namespace
-
-static int eval_prefix_batch_layout(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
-    void* stream, const FusedSketch* sk) {
-  if (int st = check_batch_levels(desc, sum, num_keys, num_starts, walk_levels, save_after,
-                                  expand_levels, cw_first, cw_stride, elements_per_leaf))
-    return st;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t slots = (num_starts << expand_levels) * elements_per_leaf;
-  const int nl = desc->num_leaves;
-  int sum_words = 3;   // the 192-bit [slot][leaf][3] accumulators
-  if (sum) {
-    if (!workspace || !out) return fail(kInvalidArgument, "NULL pointer");
-    HIP_TRY(hipMemsetAsync(workspace, 0, (size_t)slots * nl * 3 * sizeof(uint64_t), s));
-  }
-  if (num_keys > 0 && num_starts > 0) {
-    BatchLevelParams p;
-    memset(&p, 0, sizeof(p));
-    p.num_keys = num_keys;
-    p.num_starts = num_starts;
-    p.walk_levels = walk_levels;
-    p.save_after = save_after;
-    p.expand_levels = expand_levels;
-    p.cw_first = cw_first;
-    p.cw_stride = cw_stride;
-    p.key_seed = key_seed;
-    p.party = party;
-    p.seeds_in = seeds_in;
-    p.ctrl_in = control_in;
-    p.in_stride = in_stride;
-    p.parent = parent;
-    p.path = path;
-    p.save_index = save_index;
-    p.seeds_out = save_after >= 0 ? seeds_out : nullptr;
-    p.ctrl_out = control_out;
-    p.out_stride = out_stride;
-    p.cw_seed = cw_seed;
-    p.cw_left = cw_left;
-    p.cw_right = cw_right;
-    p.vcw = value_correction;
-    p.vcw_stride = desc->elements_per_block * nl;
-    p.E = desc->elements_per_block;
-    p.epl = elements_per_leaf;
-    p.esz = packed_size(desc);
-    p.nl = nl;
-    p.out_row = slots * p.esz;
-    p.out = (char*)out;
-    p.wide = reinterpret_cast<unsigned long long*>(workspace);
-    p.index_major = index_major ? 1 : 0;
-    if (int st = check_batch_pointers(p, sum, key_left, key_right, key_value)) return st;
-    plan_key_chunks(&p);
-    if (leaf_cache)
-      if (int st = attach_leaf_cache(&p, leaf_cache, leaf_stride, leaf_slot, s)) return st;
-    p.rkl = expand_key(key_left);
-    p.rkr = expand_key(key_right);
-    p.rkv = expand_key(key_value);
-    p.rkd = xor_keys(p.rkl, p.rkr);
-    if (int st = dispatch_batch(p, desc, sum, key_left, key_right, key_value, s, &sum_words, sk))
-      return st;
-  }
-  if (sum && slots > 0) {
-    int64_t g = (slots + 255) / 256;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(finalize_sums_kernel, dim3((unsigned)g), dim3(256), 0, s, slots, *desc,
-                       reinterpret_cast<const unsigned long long*>(workspace), (char*)out,
-                       sum_words);
-    HIP_TRY(hipGetLastError());
-  }
-  return kOk;
-}
-
-int dpf_hip_eval_prefix_batch_layout(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
-    void* stream) {
-  return eval_prefix_batch_layout(
-      num_keys, num_starts, walk_levels, save_after, expand_levels, cw_first, cw_stride, key_seed,
-      party, seeds_in, control_in, in_stride, parent, path, save_index, seeds_out, control_out,
-      out_stride, cw_seed, cw_left, cw_right, key_left, key_right, key_value, desc,
-      elements_per_leaf, value_correction, sum, workspace, out, leaf_cache, leaf_stride, leaf_slot,
-      index_major, stream, nullptr);
-}
 
 int dpf_hip_prefix_batch_sketch_fused(const dpf_value_desc* desc, int walk_levels,
                                       int expand_levels, int elements_per_leaf, int has_seeds_in,
@@ -1126,33 +907,70 @@ int dpf_hip_sketch_slot_weights(int64_t num_rows, int64_t count, const int64_t* 
                                     static_cast<uint32_t*>(out), (hipStream_t)stream);
 }
 
-int dpf_hip_eval_prefix_batch_sketch(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
-    int num_weights, const uint32_t* slot_weights, uint64_t* accumulators, uint32_t* sketch,
-    void* stream) {
-  if (!dpf_hip_prefix_batch_sketch_fused(desc, walk_levels, expand_levels, elements_per_leaf,
-                                         seeds_in != nullptr, index_major, num_weights) ||
-      !sum)
-    return fail(kUnimplemented, "no fused sketch for this launch (dpf_hip_prefix_batch_sketch_fused)");
-  // Four outputs per start node, each added as a term below 2^32 to a uint64.
-  if (num_starts >= (int64_t{1} << 30)) return fail(kInvalidArgument, "too many start nodes");
-  if (num_keys > 0 && num_starts > 0 && (!slot_weights || !accumulators || !sketch))
-    return fail(kInvalidArgument, "NULL pointer");
-  const FusedSketch sk{num_weights, slot_weights, accumulators, sketch};
-  return eval_prefix_batch_layout(
-      num_keys, num_starts, walk_levels, save_after, expand_levels, cw_first, cw_stride, key_seed,
-      party, seeds_in, control_in, in_stride, parent, path, save_index, seeds_out, control_out,
-      out_stride, cw_seed, cw_left, cw_right, key_left, key_right, key_value, desc,
-      elements_per_leaf, value_correction, sum, workspace, out, leaf_cache, leaf_stride, leaf_slot,
-      index_major, stream, &sk);
+int dpf_hip_prefix_batch_level(const dpf_prefix_batch_args* args, void* stream) {
+  if (!args || args->struct_size != sizeof(dpf_prefix_batch_args))
+    return fail(kInvalidArgument, "dpf_prefix_batch_args: NULL or struct_size is not its sizeof");
+  const dpf_prefix_batch_args& a = *args;
+  if (a.num_weights != 0) {   // the fused sketch's own preconditions
+    if (!dpf_hip_prefix_batch_sketch_fused(a.desc, a.walk_levels, a.expand_levels,
+                                           a.elements_per_leaf, a.seeds_in != nullptr,
+                                           a.index_major, a.num_weights) ||
+        !a.sum)
+      return fail(kUnimplemented, "no fused sketch for this launch (dpf_hip_prefix_batch_sketch_fused)");
+    // Four outputs per start node, each added as a term below 2^32 to a uint64.
+    if (a.num_starts >= (int64_t{1} << 30)) return fail(kInvalidArgument, "too many start nodes");
+    if (a.num_keys > 0 && a.num_starts > 0 && (!a.slot_weights || !a.accumulators || !a.sketch))
+      return fail(kInvalidArgument, "NULL pointer");
+  }
+  if (int st = check_batch_levels(a)) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t slots = (a.num_starts << a.expand_levels) * a.elements_per_leaf;
+  const int nl = a.desc->num_leaves;
+  int sum_words = 3;   // the 192-bit [slot][leaf][3] accumulators
+  if (a.sum) {
+    if (!a.workspace || !a.out) return fail(kInvalidArgument, "NULL pointer");
+    HIP_TRY(hipMemsetAsync(a.workspace, 0, (size_t)slots * nl * 3 * sizeof(uint64_t), s));
+  }
+  if (a.num_keys > 0 && a.num_starts > 0) {
+    if (int st = check_batch_pointers(a)) return st;
+    if (a.leaf_cache)
+      if (int st = check_leaf_cache(a, s)) return st;
+    BatchLevelParams p;
+    memset(&p, 0, sizeof(p));
+    set_batch_tables(&p, a);
+    p.walk_levels = a.walk_levels;
+    p.save_after = a.save_after;
+    p.expand_levels = a.expand_levels;
+    p.cw_first = a.cw_first;
+    p.key_seed = a.key_seed;
+    p.path = a.path;
+    p.in_stride = a.in_stride;
+    p.out_stride = a.out_stride;
+    p.leaf_stride = a.leaf_stride;
+    p.index_major = a.index_major ? 1 : 0;
+    p.E = a.desc->elements_per_block;
+    p.epl = a.elements_per_leaf;
+    p.esz = packed_size(a.desc);
+    p.nl = nl;
+    p.out_row = slots * p.esz;
+    p.out = (char*)a.out;
+    p.wide = reinterpret_cast<unsigned long long*>(a.workspace);
+    plan_key_chunks(&p);
+    p.rkl = expand_key(a.key_left);
+    p.rkr = expand_key(a.key_right);
+    p.rkv = expand_key(a.key_value);
+    p.rkd = xor_keys(p.rkl, p.rkr);
+    if (int st = dispatch_batch(p, a, s, &sum_words)) return st;
+  }
+  if (a.sum && slots > 0) {
+    int64_t g = (slots + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(finalize_sums_kernel, dim3((unsigned)g), dim3(256), 0, s, slots, *a.desc,
+                       reinterpret_cast<const unsigned long long*>(a.workspace), (char*)a.out,
+                       sum_words);
+    HIP_TRY(hipGetLastError());
+  }
+  return kOk;
 }
 
 const char* dpf_hip_last_batch_kernel(void) { return g_last_batch_kernel; }

@@ -820,11 +820,12 @@ __global__ void hh_key_table_kernel(int64_t K, int cw_level, int cw_stride,
 
 namespace dpf_rt {
 
-int launch_hh_keys(const HHLevelArgs& a, hipStream_t s) {
+int launch_hh_keys(const dpf_prefix_batch_args& a, int b, hipStream_t s) {
   HHKeysParams p;
   memset(&p, 0, sizeof(p));
-  p.num_keys = a.num_keys;
-  p.num_starts = a.num_starts;
+  set_batch_tables(&p, a);
+  p.cw_level = a.cw_first;
+  const int nl = a.desc->num_leaves;
   const int64_t groups = (a.num_keys + 63) / 64;
   // At least ~4 tasks per wave slot of the chip (64 when they are taken
   // dynamically -- 2^20-client pass 17.16 / 16.71 / 16.39 / 16.28 s at 8 /
@@ -840,27 +841,11 @@ int launch_hh_keys(const HHLevelArgs& a, hipStream_t s) {
   p.u_per_range = (a.num_starts + ranges - 1) / ranges;
   p.u_ranges = (a.num_starts + p.u_per_range - 1) / p.u_per_range;
   p.num_waves = groups * p.u_ranges;
-  p.cw_level = a.cw_level;
-  p.cw_stride = a.cw_stride;
-  p.nl = a.nl;
-  p.b = a.b;
-  p.seeds_in = a.seeds_in;
-  p.ctrl_in = a.ctrl_in;
-  p.parent = a.parent;
-  p.save = a.save;
-  p.save_index = a.save_index;
-  p.seeds_out = a.seeds_out;
-  p.ctrl_out = a.ctrl_out;
-  p.cw_seed = a.cw_seed;
-  p.cw_left = a.cw_left;
-  p.cw_right = a.cw_right;
-  p.vcw = a.vcw;
-  p.vcw_stride = a.vcw_stride;
-  p.party = a.party;
-  p.sums = a.wide;
-  p.leaf_seeds = a.leaf_seeds;
-  p.leaf_slot = a.leaf_slot;
-  for (int i = 0; i < 2; ++i) p.div[i] = make_div32(a.mod[i < a.nl ? i : 0]);
+  p.nl = nl;
+  p.b = b;
+  p.save = a.save_after == 0 && p.seeds_out;
+  p.sums = reinterpret_cast<unsigned long long*>(a.workspace);
+  for (int i = 0; i < 2; ++i) p.div[i] = make_div32((uint32_t)a.desc->mod_low[i < nl ? i : 0]);
   p.rkl = expand_key(a.key_left);
   p.rkr = expand_key(a.key_right);
   p.rkv = expand_key(a.key_value);
@@ -885,25 +870,27 @@ int launch_hh_keys(const HHLevelArgs& a, hipStream_t s) {
   int64_t g = (a.num_keys + 255) / 256;
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(hh_key_table_kernel, dim3((unsigned)g), dim3(256), 0, s, a.num_keys,
-                     a.cw_level, a.cw_stride, a.cw_seed, a.cw_left, a.cw_right, a.vcw,
-                     a.vcw_stride, a.nl, a.party, static_cast<uint4*>(tab));
+                     p.cw_level, p.cw_stride, p.cw_seed, p.cw_left, p.cw_right, p.vcw,
+                     p.vcw_stride, nl, p.party, static_cast<uint4*>(tab));
   p.key_tab = static_cast<const uint4*>(tab);
   if (dynamic) {
     p.task_counter = reinterpret_cast<unsigned int*>(
         static_cast<char*>(tab) + (size_t)a.num_keys * 3 * sizeof(uint4));
     HIP_TRY(hipMemsetAsync(p.task_counter, 0, sizeof(unsigned int), s));
   }
-  if (a.sk_rows > 0) {
-    const HHSketchParams q{a.sk_weights, a.sk_acc, make_div32((uint32_t)p.u_ranges)};
-    HIP_TRY(hipMemsetAsync(a.sk_acc, 0, (size_t)a.sk_rows * 2 * a.num_keys * sizeof(uint64_t), s));
-    if (a.sk_rows == 1)
+  if (a.num_weights > 0) {
+    const HHSketchParams q{a.slot_weights, reinterpret_cast<unsigned long long*>(a.accumulators),
+                           make_div32((uint32_t)p.u_ranges)};
+    HIP_TRY(hipMemsetAsync(a.accumulators, 0,
+                           (size_t)a.num_weights * 2 * a.num_keys * sizeof(uint64_t), s));
+    if (a.num_weights == 1)
       hipLaunchKernelGGL(hh_keys_sketch_kernel<1>, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s,
                          p, q);
     else
       hipLaunchKernelGGL(hh_keys_sketch_kernel<2>, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s,
                          p, q);
     hipLaunchKernelGGL(sketch_finish_kernel, dim3((unsigned)g), dim3(256), 0, s, a.num_keys,
-                       a.sk_rows, a.nl, p.div[0], p.div[1], a.sk_acc, a.sk_out);
+                       a.num_weights, nl, p.div[0], p.div[1], q.acc, a.sketch);
   } else {
     hipLaunchKernelGGL(hh_keys_kernel, dim3((unsigned)grid), dim3(kHHKeysBlock), 0, s, p);
   }
@@ -924,16 +911,20 @@ int launch_sketch_slot_weights(int64_t n, int64_t count, const int64_t* src_offs
   return kOk;
 }
 
-int launch_hh_level(const HHLevelArgs& a, hipStream_t s) {
-  if (a.sk_rows > 0 && (!a.index_major || a.sk_rows > kHHSketchMaxRows))
+int launch_hh_level(const dpf_prefix_batch_args& a, int b, hipStream_t s) {
+  const int nl = a.desc->num_leaves;
+  if (a.num_weights > 0 && (!a.index_major || a.num_weights > kHHSketchMaxRows))
     return fail(kUnimplemented, "hh_keys_sketch_kernel: not the fused sketch's shape");
-  if (a.nl < 1 || a.nl > 2 || (a.b != 1 && a.b != 2) || (a.nl == 2 && a.b != 2))
+  if (nl < 1 || nl > 2 || (b != 1 && b != 2) || (nl == 2 && b != 2))
     return fail(kUnimplemented, "hh_level_kernel: unsupported value type");
-  if (a.index_major) return launch_hh_keys(a, s);
+  if (a.index_major) return launch_hh_keys(a, b, s);
   HHParams p;
   memset(&p, 0, sizeof(p));
-  p.num_keys = a.num_keys;
-  p.num_starts = a.num_starts;
+  set_batch_tables(&p, a);
+  p.cw_level = a.cw_first;
+  p.in_stride = a.in_stride;
+  p.out_stride = a.out_stride;
+  p.leaf_stride = a.leaf_stride;
   p.waves_per_chunk = (a.num_starts + 63) / 64;
   // ~4 tasks per wave slot, or DPF_HH_DYNAMIC (default 64) taken dynamically
   // (0: the fixed grid-stride share).
@@ -946,30 +937,11 @@ int launch_hh_level(const HHLevelArgs& a, hipStream_t s) {
   p.chunk_keys = (a.num_keys + chunks - 1) / chunks;
   chunks = (a.num_keys + p.chunk_keys - 1) / p.chunk_keys;
   p.num_threads = chunks * p.waves_per_chunk * 64;
-  p.cw_level = a.cw_level;
-  p.cw_stride = a.cw_stride;
-  p.save = a.save;
-  p.nl = a.nl;
-  p.b = a.b;
-  p.seeds_in = a.seeds_in;
-  p.ctrl_in = a.ctrl_in;
-  p.in_stride = a.in_stride;
-  p.parent = a.parent;
-  p.save_index = a.save_index;
-  p.seeds_out = a.seeds_out;
-  p.ctrl_out = a.ctrl_out;
-  p.out_stride = a.out_stride;
-  p.cw_seed = a.cw_seed;
-  p.cw_left = a.cw_left;
-  p.cw_right = a.cw_right;
-  p.vcw = a.vcw;
-  p.vcw_stride = a.vcw_stride;
-  p.party = a.party;
-  p.wide = a.wide;
-  p.leaf_seeds = a.leaf_seeds;
-  p.leaf_stride = a.leaf_stride;
-  p.leaf_slot = a.leaf_slot;
-  for (int i = 0; i < a.nl; ++i) p.div[i] = make_div32(a.mod[i]);
+  p.save = a.save_after == 0 && p.seeds_out;
+  p.nl = nl;
+  p.b = b;
+  p.wide = reinterpret_cast<unsigned long long*>(a.workspace);
+  for (int i = 0; i < nl; ++i) p.div[i] = make_div32((uint32_t)a.desc->mod_low[i]);
   p.rkl = expand_key(a.key_left);
   p.rkr = expand_key(a.key_right);
   p.rkv = expand_key(a.key_value);

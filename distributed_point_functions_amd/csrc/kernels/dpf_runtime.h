@@ -115,59 +115,48 @@ int dot_type(const dpf_value_desc* d, int* words, int* xor_type);
 int launch_dot_fold(int row_words, int xor_type, int accumulate, const void* workspace, void* out,
                     hipStream_t s);
 
-// One steady-state heavy-hitters level (dpf_batch_hh.hip): start seeds from
-// the expansion cache or gathered partial evaluations, no path walk, two
-// expanded levels, Tuple/IntModN<uint32_t> values summed over the keys.
-struct HHLevelArgs {
-  int64_t num_keys, num_starts;
-  int cw_level, cw_stride;
-  const dpf_block* seeds_in;
-  const uint8_t* ctrl_in;    // NULL: control bit in bit 0 of the seed
-  int64_t in_stride;
-  const int32_t* parent;
-  int save;                   // 1: store each start node as the key's partial evaluation
-  const int32_t* save_index;  // NULL (with save): start node u at index u
-  dpf_block* seeds_out;
-  uint8_t* ctrl_out;
-  int64_t out_stride;
-  const dpf_block* cw_seed;
-  const uint8_t* cw_left;
-  const uint8_t* cw_right;
-  const dpf_block* vcw;
-  int vcw_stride;
-  const uint8_t* party;
-  unsigned long long* wide;
-  dpf_block* leaf_seeds;
-  int64_t leaf_stride;
-  const int32_t* leaf_slot;  // NULL: leaf i of start node u at slot (u << 2) + i
-  // 0: per-key tables key-major, element (k, j) at k*stride + j; sums into
-  //    the 192-bit [slot][leaf][3] workspace (hh_level_kernel).
-  // 1: index-major, element (k, j) at j*num_keys + k (the device batch
-  //    context's layout); lanes are keys (hh_keys_kernel) and the sums go to
-  //    one uint64 per [slot][leaf] (finalize with words == 1).
-  int index_major;
-  int nl, b;
-  uint32_t mod[2];
-  const dpf_aes_key* key_left;
-  const dpf_aes_key* key_right;
-  const dpf_aes_key* key_value;
-  // sk_rows > 0 (index_major only, <= kHHSketchMaxRows): the fused per-key
-  // sketch under sk_weights ([slot][sk_rows][2] uint32 reduced per modulus),
-  // through the accumulators sk_acc ([sk_rows][2][num_keys] uint64, cleared
-  // by the launch) into sk_out ([key][sk_rows][nl] uint32).
-  int sk_rows;
-  const uint32_t* sk_weights;
-  unsigned long long* sk_acc;
-  uint32_t* sk_out;
-};
 constexpr int kHHSketchMaxRows = 2;
 // out[(slot*rows + j)*2 + e] = weights[j*n + i] mod mod[e] for output i at slot
 // src_offset[i / count] + i % count (NULL: slot i).
 int launch_sketch_slot_weights(int64_t n, int64_t count, const int64_t* src_offset, int rows,
                                const uint32_t* weights, const uint32_t mod[2], uint32_t* out,
                                hipStream_t s);
-int launch_hh_level(const HHLevelArgs& a, hipStream_t s);
-int launch_hh_keys(const HHLevelArgs& a, hipStream_t s);   // index_major == 1
+// One steady-state heavy-hitters level (dpf_batch_hh.hip) of the launch `a`:
+// start seeds from the expansion cache or gathered partial evaluations, no
+// path walk, two expanded levels, `b` blocks sampled per
+// Tuple/IntModN<uint32_t> value, summed over the keys.
+//   a.index_major == 0: sums into the 192-bit [slot][leaf][3] workspace
+//     (hh_level_kernel);
+//   a.index_major != 0: lanes are keys (hh_keys_kernel) and the sums go to one
+//     uint64 per [slot][leaf] (finalize with words == 1); with a.num_weights >
+//     0 (<= kHHSketchMaxRows) the fused per-key sketch too.
+int launch_hh_level(const dpf_prefix_batch_args& a, int b, hipStream_t s);
+int launch_hh_keys(const dpf_prefix_batch_args& a, int b, hipStream_t s);
+
+// The per-key tables of a batched prefix evaluation out of the C ABI's struct
+// into a kernel's parameter block: the members that BatchLevelParams
+// (dpf_batch.hip), HHParams and HHKeysParams (dpf_batch_hh.hip) all declare,
+// each in the order its kernel was tuned with.  The one copy of them.
+template <class Params>
+void set_batch_tables(Params* p, const dpf_prefix_batch_args& a) {
+  p->num_keys = a.num_keys;
+  p->num_starts = a.num_starts;
+  p->cw_stride = a.cw_stride;
+  p->seeds_in = a.seeds_in;
+  p->ctrl_in = a.control_in;
+  p->parent = a.parent;
+  p->save_index = a.save_index;
+  p->seeds_out = a.save_after >= 0 ? a.seeds_out : nullptr;
+  p->ctrl_out = a.control_out;
+  p->cw_seed = a.cw_seed;
+  p->cw_left = a.cw_left;
+  p->cw_right = a.cw_right;
+  p->vcw = a.value_correction;
+  p->vcw_stride = a.desc->elements_per_block * a.desc->num_leaves;
+  p->party = a.party;
+  p->leaf_seeds = a.leaf_cache;   // NULL: no cache is written, leaf_slot is not read
+  p->leaf_slot = a.leaf_slot;
+}
 
 }  // namespace dpf_rt
 

@@ -54,6 +54,31 @@ class ValueDesc(ctypes.Structure):
     ]
 
 
+class PrefixBatchArgs(ctypes.Structure):
+    """dpf_prefix_batch_args, member by member; prefix_batch_args() makes one."""
+    _P, _I, _I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_keys", _I64), ("num_starts", _I64),
+                ("walk_levels", _I), ("save_after", _I), ("expand_levels", _I), ("cw_first", _I),
+                ("cw_stride", _I), ("key_seed", _P), ("party", _P), ("seeds_in", _P),
+                ("control_in", _P), ("in_stride", _I64), ("parent", _P), ("path", _P),
+                ("save_index", _P), ("seeds_out", _P), ("control_out", _P), ("out_stride", _I64),
+                ("cw_seed", _P), ("cw_left", _P), ("cw_right", _P),
+                ("key_left", ctypes.POINTER(AesKey)), ("key_right", ctypes.POINTER(AesKey)),
+                ("key_value", ctypes.POINTER(AesKey)), ("desc", ctypes.POINTER(ValueDesc)),
+                ("elements_per_leaf", _I), ("value_correction", _P), ("sum", _I),
+                ("workspace", _P), ("out", _P), ("leaf_cache", _P), ("leaf_stride", _I64),
+                ("leaf_slot", _P), ("index_major", _I), ("num_weights", _I),
+                ("slot_weights", _P), ("accumulators", _P), ("sketch", _P)]
+
+
+def prefix_batch_args(**members) -> PrefixBatchArgs:
+    """A zeroed dpf_prefix_batch_args with struct_size and `members` set (keys
+    and descriptor as ctypes.pointer(...), device pointers as integers)."""
+    a = PrefixBatchArgs(**members)
+    a.struct_size = ctypes.sizeof(PrefixBatchArgs)
+    return a
+
+
 def header_functions() -> list:
     """Names of every function the C ABI header declares."""
     txt = open(HEADER).read()
@@ -122,9 +147,8 @@ def load(require_gpu: bool = False):
                              [I64, I, I, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P]),
                             ("dpf_hip_prefix_batch_sketch_fused", [P, I, I, I, I, I, I]),
                             ("dpf_hip_sketch_slot_weights", [I64, I64, P, P, I, P, P, P]),
-                            ("dpf_hip_eval_prefix_batch_sketch",
-                             [I64, I64, I, I, I, I, I, P, P, P, P, I64, P, P, P, P, P, I64, P, P,
-                              P, P, P, P, P, I, P, I, P, P, P, I64, P, I, I, P, P, P, P])):
+                            ("dpf_hip_prefix_batch_max_expand", [P, I]),
+                            ("dpf_hip_prefix_batch_level", [ctypes.POINTER(PrefixBatchArgs), P])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = types
         if hasattr(L, "dpf_hip_last_dot_kernel"):

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define DPF_HIP_ABI_VERSION 1
+#define DPF_HIP_ABI_VERSION 2
 #define DPF_MAX_LEAVES 16
 
 typedef struct dpf_block {
@@ -319,7 +319,7 @@ int dpf_hip_octet_schedule(int64_t num_items, int k0, int subtree_depth, int min
 int dpf_hip_last_expand_schedule(int64_t* out);
 
 /* Diagnostic: which kernel the calling thread's last
- * dpf_hip_eval_prefix_batch(_cached) launched: "hh_level" (the lean
+ * dpf_hip_prefix_batch_level launched: "hh_level" (the lean
  * heavy-hitters kernel: cached or gathered start seeds, two expanded levels,
  * IntModN<uint32_t> sums), "batch_level/fast", "batch_level/mod32" or
  * "batch_level/generic"; "" before the first call. */
@@ -414,7 +414,9 @@ int dpf_hip_sum_shares_u64(int64_t num_keys, int64_t row_len, int bits, int xor_
  * of a batch with a device-resident context: the
  * path walk of ComputePartialEvaluations (cc:351-453, EvaluateSeeds
  * evaluate_prg_hwy.cc:452-486), ExpandSeeds (cc:271-349), HashExpandedSeeds
- * (cc:500-524) and the value correction (h:785-808), fused.
+ * (cc:500-524) and the value correction (h:785-808), fused.  The call takes
+ * its arguments in one struct, dpf_prefix_batch_args (zero it, set struct_size
+ * and the members the launch needs; stream apart).
  *
  * For key k < num_keys and start node u < num_starts:
  *   start  = (seeds_in[k*in_stride + parent[u]], control_in[...]), or key k's
@@ -440,22 +442,10 @@ int dpf_hip_sum_shares_u64(int64_t num_keys, int64_t row_len, int bits, int xor_
  *           uint64 and is cleared by the call.  Returns 12 UNIMPLEMENTED for
  *           value types without an on-device key sum
  *           (dpf_hip_prefix_batch_max_expand(desc, 1) < 0): use sum == 0 and
- *           dpf_hip_sum_rows. */
-int dpf_hip_eval_prefix_batch(int64_t num_keys, int64_t num_starts, int walk_levels,
-                              int save_after, int expand_levels, int cw_first, int cw_stride,
-                              const dpf_block* key_seed, const uint8_t* party,
-                              const dpf_block* seeds_in, const uint8_t* control_in,
-                              int64_t in_stride, const int32_t* parent, const dpf_block* path,
-                              const int32_t* save_index, dpf_block* seeds_out,
-                              uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed,
-                              const uint8_t* cw_left, const uint8_t* cw_right,
-                              const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-                              const dpf_aes_key* key_value, const dpf_value_desc* desc,
-                              int elements_per_leaf, const dpf_block* value_correction, int sum,
-                              uint64_t* workspace, void* out, void* stream);
-
-/* dpf_hip_eval_prefix_batch that also writes the expansion cache: every tree
- * leaf of the call (2^expand_levels per start node u) to
+ *           dpf_hip_sum_rows.
+ *
+ * The expansion cache (leaf_cache != NULL): every tree leaf of the call
+ * (2^expand_levels per start node u) also goes to
  * leaf_cache[k*leaf_stride + (u << expand_levels) + l] (leaf_stride >=
  * num_starts << expand_levels), the node's seed with its control bit in bit 0
  * (clear in every non-root seed).  The next level's tree nodes are among these
@@ -464,73 +454,93 @@ int dpf_hip_eval_prefix_batch(int64_t num_keys, int64_t num_starts, int walk_lev
  * instead of re-deriving them by a path walk from the partial evaluations two
  * calls back (distributed_point_function.cc:351-453).
  * The leaves must not be the root (depth > 0).  leaf_cache must not overlap
- * seeds_in (the caller double-buffers).  leaf_cache == NULL: no cache. */
-int dpf_hip_eval_prefix_batch_cached(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, void* stream);
-
-/* dpf_hip_eval_prefix_batch_cached with the cache rewritten IN PLACE:
- * leaf l of start node u goes to leaf_cache[k*leaf_stride + leaf_slot[(u <<
- * expand_levels) + l]] (leaf_slot: device, num_starts << expand_levels
- * entries), and leaf_cache may be seeds_in itself (in_stride == leaf_stride,
- * control_in == NULL).  Contract on the table: a slot that
+ * seeds_in (the caller double-buffers) except through a slot table.
+ *
+ * The slot table (leaf_slot != NULL; device, num_starts << expand_levels
+ * entries) rewrites the cache IN PLACE: leaf l of start node u goes to
+ * leaf_cache[k*leaf_stride + leaf_slot[(u << expand_levels) + l]], and
+ * leaf_cache may be seeds_in itself (in_stride == leaf_stride, control_in ==
+ * NULL).  Contract on the table: a slot that
  * some start node reads (parent[u]) may appear only among the leaves of that
  * start node, and only if no other start node reads it; every other entry is
  * a slot no start node reads.  Each (key, start node) is one thread that
  * reads its start seed before it writes any leaf, so no entry is overwritten
  * before it has been read -- no gather of the start seeds and no second
  * cache buffer (the heavy-hitters steady state at 2^20
- * clients, where a 64 GiB spare does not fit).  leaf_slot == NULL: exactly
- * dpf_hip_eval_prefix_batch_cached.  DPF_HIP_CHECK_SLOTS=1 checks the table
- * against this contract on the host first (INVALID_ARGUMENT if broken). */
-int dpf_hip_eval_prefix_batch_cached_slots(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, void* stream);
-
-/* dpf_hip_eval_prefix_batch_cached_slots with the layout of its per-key
- * tables chosen.  index_major == 0 is exactly that function: element (key k,
- * slot j) of seeds_in / control_in, seeds_out / control_out and leaf_cache at
- * k*stride + j.  index_major == 1 puts it at j*num_keys + k for all three
+ * clients, where a 64 GiB spare does not fit).  DPF_HIP_CHECK_SLOTS=1 checks
+ * the table against this contract on the host first (INVALID_ARGUMENT if
+ * broken).
+ *
+ * The layout of the per-key tables: with index_major == 0 element (key k,
+ * slot j) of seeds_in / control_in, seeds_out / control_out and leaf_cache is
+ * at k*stride + j.  index_major == 1 puts it at j*num_keys + k for all three
  * (in_stride, out_stride and leaf_stride then only give the slots per key):
  * the layout of the device batch context (DeviceBatchContext), in which 64
  * consecutive keys at one slot are one 1 KiB access.  With index_major == 1
  * the heavy-hitters steady state (no walk, two expanded levels, sum mode,
  * IntModN<uint32_t> tuples) runs with lanes = keys ("hh_keys" in
- * dpf_hip_last_batch_kernel); outputs are identical in both layouts. */
-int dpf_hip_eval_prefix_batch_layout(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
-    void* stream);
+ * dpf_hip_last_batch_kernel); outputs are identical in both layouts.
+ *
+ * The fused sketch (num_weights > 0; 0: none): a launch with sum != 0 in the
+ * shape the lanes-are-keys kernel takes (index_major, no walk, two expanded
+ * levels, start seeds given, one element per leaf, at most two
+ * IntModN<uint32_t> leaves) besides the key sums leaves
+ *   sketch[(k*num_weights + j)*num_leaves + e] =
+ *       ( sum over slots of slot_weights[(slot*num_weights + j)*2 + e] * y_k[slot][e] ) mod N_e
+ * without storing any key's row.  slot_weights holds, for every slot (u << 2)
+ * + leaf of the launch, num_weights x 2 uint32 already reduced per modulus
+ * (dpf_hip_sketch_slot_weights writes them from weights in output order);
+ * `accumulators` is num_weights * 2 * num_keys uint64 of device scratch,
+ * cleared by the call.  Integer sums below 2^64 added with atomics: the
+ * result does not depend on their order.  Every other launch, and
+ * num_weights above 2: 12 UNIMPLEMENTED and nothing is launched -- store the
+ * rows and call dpf_hip_sketch_rows.  dpf_hip_last_batch_kernel reports
+ * "hh_keys_sketch". */
+typedef struct dpf_prefix_batch_args {
+  uint32_t struct_size; /* sizeof(dpf_prefix_batch_args) */
+  int64_t num_keys, num_starts;
+  int walk_levels, save_after, expand_levels, cw_first, cw_stride;
+  const dpf_block* key_seed;
+  const uint8_t* party;
+  const dpf_block* seeds_in;
+  const uint8_t* control_in;
+  int64_t in_stride;
+  const int32_t* parent;
+  const dpf_block* path;
+  const int32_t* save_index;
+  dpf_block* seeds_out;
+  uint8_t* control_out;
+  int64_t out_stride;
+  const dpf_block* cw_seed;
+  const uint8_t* cw_left;
+  const uint8_t* cw_right;
+  const dpf_aes_key* key_left;
+  const dpf_aes_key* key_right;
+  const dpf_aes_key* key_value;
+  const dpf_value_desc* desc;
+  int elements_per_leaf;
+  const dpf_block* value_correction;
+  int sum;
+  uint64_t* workspace;
+  void* out;
+  dpf_block* leaf_cache;
+  int64_t leaf_stride;
+  const int32_t* leaf_slot;
+  int index_major;
+  int num_weights;
+  const uint32_t* slot_weights;
+  uint64_t* accumulators;
+  uint32_t* sketch;
+} dpf_prefix_batch_args;
+/* args == NULL or args->struct_size != sizeof(dpf_prefix_batch_args): 3
+ * INVALID_ARGUMENT, before anything else is read. */
+int dpf_hip_prefix_batch_level(const dpf_prefix_batch_args* args, void* stream);
 
 /* seeds_out[k*num_rows + i] / control_out[k*num_rows + i] = the seed (bit 0
  * cleared) and control bit (bit 0) of cache[k*cache_stride + slot[i]]: a
- * call's start seeds from the previous call's expansion cache. */
-int dpf_hip_gather_seeds(int64_t num_keys, int64_t num_rows, const int64_t* slot,
-                         const dpf_block* cache, int64_t cache_stride, dpf_block* seeds_out,
-                         uint8_t* control_out, void* stream);
-/* dpf_hip_gather_seeds with index_major == 1: seeds_out / control_out[i*num_keys
- * + k] from cache[slot[i]*num_keys + k] (cache_stride unused). */
+ * call's start seeds from the previous call's expansion cache.  With
+ * index_major == 1: seeds_out / control_out[i*num_keys + k] from
+ * cache[slot[i]*num_keys + k] (cache_stride unused). */
 int dpf_hip_gather_seeds_layout(int64_t num_keys, int64_t num_rows, const int64_t* slot,
                                 const dpf_block* cache, int64_t cache_stride, dpf_block* seeds_out,
                                 uint8_t* control_out, int index_major, void* stream);
@@ -541,7 +551,7 @@ int dpf_hip_gather_seeds_layout(int64_t num_keys, int64_t num_rows, const int64_
 int dpf_hip_memcpy_d2h_strided(void* dst, const void* src, size_t elem_bytes,
                                size_t src_stride_bytes, int64_t count, void* stream);
 
-/* Largest expand_levels dpf_hip_eval_prefix_batch accepts for this value type
+/* Largest expand_levels dpf_hip_prefix_batch_level accepts for this value type
  * (register-resident subtree), or -1 if `sum` mode is not available. */
 int dpf_hip_prefix_batch_max_expand(const dpf_value_desc* desc, int sum);
 
@@ -573,37 +583,10 @@ int dpf_hip_sketch_rows(int64_t num_keys, int64_t row_len, const dpf_value_desc*
  * touched. */
 int dpf_hip_sketch_supported(const dpf_value_desc* desc);
 
-/* The sketch fused into the key-sum pass of a batched prefix evaluation:
- * dpf_hip_eval_prefix_batch_layout with sum != 0 in the shape its lanes-are-
- * keys kernel takes (index_major, no walk, two expanded levels, start seeds
- * given, one element per leaf, at most two IntModN<uint32_t> leaves), which
- * besides the key sums leaves
- *   sketch[(k*num_weights + j)*num_leaves + e] =
- *       ( sum over slots of slot_weights[(slot*num_weights + j)*2 + e] * y_k[slot][e] ) mod N_e
- * without storing any key's row.  slot_weights holds, for every slot (u << 2)
- * + leaf of the launch, num_weights x 2 uint32 already reduced per modulus
- * (dpf_hip_sketch_slot_weights writes them from weights in output order);
- * `accumulators` is num_weights * 2 * num_keys uint64 of device scratch,
- * cleared by the call.  Integer sums below 2^64 added with atomics: the
- * result does not depend on their order.  Every other launch, and
- * num_weights above 2: 12 UNIMPLEMENTED and nothing is launched -- store the
- * rows and call dpf_hip_sketch_rows.  dpf_hip_last_batch_kernel reports
- * "hh_keys_sketch". */
-int dpf_hip_eval_prefix_batch_sketch(
-    int64_t num_keys, int64_t num_starts, int walk_levels, int save_after, int expand_levels,
-    int cw_first, int cw_stride, const dpf_block* key_seed, const uint8_t* party,
-    const dpf_block* seeds_in, const uint8_t* control_in, int64_t in_stride,
-    const int32_t* parent, const dpf_block* path, const int32_t* save_index, dpf_block* seeds_out,
-    uint8_t* control_out, int64_t out_stride, const dpf_block* cw_seed, const uint8_t* cw_left,
-    const uint8_t* cw_right, const dpf_aes_key* key_left, const dpf_aes_key* key_right,
-    const dpf_aes_key* key_value, const dpf_value_desc* desc, int elements_per_leaf,
-    const dpf_block* value_correction, int sum, uint64_t* workspace, void* out,
-    dpf_block* leaf_cache, int64_t leaf_stride, const int32_t* leaf_slot, int index_major,
-    int num_weights, const uint32_t* slot_weights, uint64_t* accumulators, uint32_t* sketch,
-    void* stream);
-/* 1 when dpf_hip_eval_prefix_batch_sketch takes a launch of this shape, else
- * 0.  DPF_BATCH_SKETCH_FUSED=0 (read per call; A/B and test hook) turns the
- * fused path off, DPF_BATCH_NO_LEAN=1 too.  No device is touched. */
+/* 1 when dpf_hip_prefix_batch_level takes a launch of this shape with
+ * num_weights > 0 (the fused sketch), else 0.  DPF_BATCH_SKETCH_FUSED=0 (read
+ * per call; A/B and test hook) turns the fused path off, DPF_BATCH_NO_LEAN=1
+ * too.  No device is touched. */
 int dpf_hip_prefix_batch_sketch_fused(const dpf_value_desc* desc, int walk_levels,
                                       int expand_levels, int elements_per_leaf, int has_seeds_in,
                                       int index_major, int num_weights);

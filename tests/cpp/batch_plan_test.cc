@@ -29,7 +29,7 @@ static int failures = 0;
   } while (0)
 
 // ---------------------------------------------------------------- slot table
-// The contract of dpf_hip_eval_prefix_batch_cached_slots' table, restated:
+// The contract of dpf_hip_prefix_batch_level's slot table, restated:
 // start node u (of T << s) reads slot start_slot[u >> s] and writes its 2^E
 // leaves to slot[(u << E) + l].  Every slot is below the stride; no slot is
 // written twice; a slot some start node reads is written only as a leaf of

@@ -460,9 +460,9 @@ def test_hh_keys_kernel_key_groups(n_keys, mode, monkeypatch):
 
 def test_permuted_cache_slot_tables_pass_the_contract_check(monkeypatch):
     """DPF_HIP_CHECK_SLOTS=1: every slot table the context builds for an
-    in-place rewrite satisfies the contract of
-    dpf_hip_eval_prefix_batch_cached_slots (checked on the host before each
-    launch) -- in both table layouts."""
+    in-place rewrite satisfies the slot-table contract of
+    dpf_hip_prefix_batch_level (checked on the host before each launch) -- in
+    both table layouts."""
     monkeypatch.setenv("DPF_HIP_CHECK_SLOTS", "1")
     monkeypatch.setenv("DPF_BATCH_CACHE_MODE", "permute")
     levels, plan = HH5
@@ -498,17 +498,18 @@ def test_broken_slot_table_is_rejected(bad, monkeypatch):
     out = torch.zeros(K * (U << E) * 8, dtype=torch.uint8, device=dev)
     desc = H.value_desc([(H.LEAF_INT, 64, 0)], True, 2, 1)
     kl, kr, kv = H.aes_key(1), H.aes_key(2), H.aes_key(3)
-    P, I64, I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-    f = L.dpf_hip_eval_prefix_batch_layout
-    f.argtypes = [I64, I64, I, I, I, I, I, P, P, P, P, I64, P, P, P, P, P, I64, P, P, P, P, P, P,
-                  P, I, P, I, P, P, P, I64, P, I, P]
     for index_major in (0, 1):
-        rc = f(K, U, 0, -1, E, 0, 2, key_seed.data_ptr(), party.data_ptr(), cache.data_ptr(), None,
-               stride, parent.data_ptr(), None, None, None, None, 0, cw_seed.data_ptr(),
-               cw_l.data_ptr(), cw_r.data_ptr(), ctypes.byref(kl), ctypes.byref(kr),
-               ctypes.byref(kv), ctypes.byref(desc), 2, vcw.data_ptr(), 0, None, out.data_ptr(),
-               cache.data_ptr(), stride, leaf_slot.data_ptr(), index_major,
-               H._stream(None))
+        a = H.prefix_batch_args(
+            num_keys=K, num_starts=U, walk_levels=0, save_after=-1, expand_levels=E, cw_first=0,
+            cw_stride=2, key_seed=key_seed.data_ptr(), party=party.data_ptr(),
+            seeds_in=cache.data_ptr(), in_stride=stride, parent=parent.data_ptr(),
+            cw_seed=cw_seed.data_ptr(), cw_left=cw_l.data_ptr(), cw_right=cw_r.data_ptr(),
+            key_left=ctypes.pointer(kl), key_right=ctypes.pointer(kr),
+            key_value=ctypes.pointer(kv), desc=ctypes.pointer(desc), elements_per_leaf=2,
+            value_correction=vcw.data_ptr(), sum=0, out=out.data_ptr(),
+            leaf_cache=cache.data_ptr(), leaf_stride=stride, leaf_slot=leaf_slot.data_ptr(),
+            index_major=index_major)
+        rc = L.dpf_hip_prefix_batch_level(ctypes.byref(a), H._stream(None))
         assert rc == 3, (bad, rc)
         assert "slot table" in L.dpf_hip_last_error().decode()
     torch.cuda.synchronize()
