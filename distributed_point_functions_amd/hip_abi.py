@@ -466,6 +466,32 @@ def eval_points(n, points_per_key, levels, key_seed, party, tree_index, block_in
     return out
 
 
+def gen_key_batch(num_keys: int, num_levels: int, tree_level: Sequence[int],
+                  log_domain: Sequence[int], blocks: Sequence[int], descs: Sequence[ValueDesc],
+                  alphas, root_seeds, beta, beta_mode: int, dcf_bits: int, keys, cw_seed, cw_left,
+                  cw_right, value_correction: Sequence, stream=None) -> None:
+    """Both parties' correction words of num_keys key pairs into caller-owned
+    device buffers: `tree_level`, `log_domain`, `blocks` and `descs` hold one
+    entry per hierarchy level; `alphas` (num_keys blocks), `root_seeds`
+    ([key][party] blocks) and `beta` (blocks: per level, per key and level, or
+    per key for beta_mode 0, 1, 2) are device tensors; `cw_seed` (num_keys *
+    num_levels blocks), `cw_left` / `cw_right` (as many bytes, any alignment)
+    and value_correction[h] (num_keys * elements per block blocks) are written."""
+    L = load(require_gpu=True)
+    H = len(descs)
+    if not (len(tree_level) == len(log_domain) == len(blocks) == len(value_correction) == H):
+        raise DpfHipError(3, "gen_key_batch: one table entry per hierarchy level")
+    I32 = ctypes.c_int32 * H
+    desc = (ValueDesc * H)(*descs)
+    vc = (ctypes.c_void_p * H)(*[_p(t) for t in value_correction])
+    kl, kr, kv = (aes_key(k) for k in keys)
+    check(L.dpf_hip_gen_key_batch(num_keys, num_levels, H, I32(*tree_level), I32(*log_domain),
+                                  I32(*blocks), desc, _p(alphas), _p(root_seeds), _p(beta),
+                                  beta_mode, dcf_bits, ctypes.byref(kl), ctypes.byref(kr),
+                                  ctypes.byref(kv), _p(cw_seed), _p(cw_left), _p(cw_right), vc,
+                                  _stream(stream)))
+
+
 class Event:
     """hipEvent on an explicit stream (torch.cuda.Event only sees torch's stream)."""
 

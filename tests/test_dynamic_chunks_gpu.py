@@ -1,5 +1,5 @@
-"""The chunked work loop (take_chunk, dpf_device.h) of the DCF, MIC, point and
-batch kernels on an MI355X.
+"""The chunked work loop (take_chunk, dpf_device.h) of the DCF, MIC, point,
+batch and key generation kernels on an MI355X.
 
 Every AES-bound launcher hands its waves 64-item chunks from a per-workgroup
 counter once the launch holds 4 chunks per wave of the chip
@@ -20,6 +20,13 @@ for byte, and the default run's rows at item 0, the last item, both sides of
 two workgroup-range boundaries (b * per_wg * 64, per_wg from the diagnostic),
 the last owning workgroup's short range and the cut-off chunk must equal the
 references (oracle.py, mic_model.py).  All comparisons are bit-exact.
+
+Key generation (keygen_kernel, DPF_KEYGEN_DYNAMIC) is the last section.  Its
+item is a lane, two per key pair, and it writes several arrays per call: its
+cases carve them out of one arena with an untouched gap after each
+(keygen_common.KeygenArena) and compare every array of both schedules with the
+host generator's batch, the boundary key pairs with the oracle's keys, and
+evaluate every key pair at and next to its alpha.
 """
 import numpy as np
 import pytest
@@ -27,8 +34,11 @@ import pytest
 import mic_model as MM
 import oracle as O
 import ref_grids as G
+from keygen_common import (assert_arrays_equal, batch_arrays, boundary_key_pairs, gen_into_arena,
+                           oracle_arrays, rows_of, seed_ints)
 from test_dcf_cpu import make as make_dcf
 from test_host_api_cpu import leaves_value
+from test_key_batch_cpu import make as make_dpf
 from test_kernels_gpu import GENERIC_TYPES, _desc, _rand_blocks, _rand_value
 from test_key_batch_gpu import _dev_points, _rand_u128, _setup
 from test_mic_cpu import gate
@@ -587,3 +597,238 @@ def test_batch_level_kernel_chunked(H, no_cache, sum_mode, monkeypatch):
         bk = sorted({bk[round(j * (len(bk) - 1) / 7)] for j in range(8)})
     for k in bk:
         np.testing.assert_array_equal(got[k], oracle_row(k), err_msg=f"key {k}")
+
+
+# --------------------------------------------------------------------------
+# Key generation
+# --------------------------------------------------------------------------
+
+def _keygen_count():
+    """T / 2 + 113 key pairs: T + 226 lanes, the smallest count just above the
+    threshold whose T / 64 + 4 chunks leave the last owning workgroup a short
+    range (8 of per_wg = 65 chunks on 256 CUs, three workgroups without any)
+    and whose last chunk is cut inside a wave (34 lanes, 17 key pairs).
+    _boundary_items asserts the first two conditions for the chip it runs on:
+    they hold from 69 CUs up (per_wg is 65 wherever 4 < CUs)."""
+    K = _threshold() // 2 + 113
+    assert -(-2 * K // 64) == _threshold() // 64 + 4 and 2 * K % 64 == 34
+    return K
+
+
+def _keygen_inputs(seed, K, top, fixed):
+    """(K, 2) uint64 alphas below 2^top (`fixed` first, random after) and
+    (2 K, 2) root seeds, [key][party]."""
+    rng = np.random.default_rng(seed)
+    alphas = np.zeros((K, 2), np.uint64)
+    alphas[:, 0] = rng.integers(0, 1 << top, size=K, dtype=np.uint64)
+    alphas[:len(fixed), 0] = fixed
+    seeds = rng.integers(0, 1 << 63, size=(2 * K, 2), dtype=np.uint64)
+    return rng, alphas, seeds
+
+
+def _beta_pool(rng, vt, K, first=()):
+    """One beta leaf per key as a uint64 array and as Values: `first`, then
+    random draws from a pool of 1024 random leaves (one Value object per pool
+    entry; building K of them would take longer than the launch under test)."""
+    bits = O.leaves(vt)[0][1]
+    assert bits <= 64
+    pool = rng.integers(0, 1 << (bits - 1), size=1024, dtype=np.uint64) * np.uint64(2) + \
+        rng.integers(0, 2, size=1024, dtype=np.uint64)
+    pool[:len(first)] = np.array(first, np.uint64)
+    pick = rng.integers(0, 1024, size=K)
+    pick[:len(first)] = np.arange(len(first))
+    values = [leaves_value(vt, [int(v)]) for v in pool]
+    return pool[pick], [values[i] for i in pick]
+
+
+def _keygen_two_schedules(H, monkeypatch, run):
+    """run(fill) -> the arrays of one key generation call, under the default
+    hooks (must report chunks > 0) and with DPF_KEYGEN_DYNAMIC=0 (must report
+    0), prefilled with different bytes where the caller owns the buffers.
+    Returns the default run's arrays and its chunks per workgroup once every
+    array of the two runs is equal."""
+    hook = "DPF_KEYGEN_DYNAMIC"
+    got, per_wg = [], 0
+    for fill, off in ((0xAB, False), (0x54, True)):
+        if off:
+            monkeypatch.setenv(hook, "0")
+        else:
+            monkeypatch.delenv(hook, raising=False)
+        arrays, chunks = run(fill)
+        if off:
+            assert chunks == 0, (hook, chunks)
+        else:
+            assert chunks > 0, (hook, chunks)
+            per_wg = chunks
+        got.append(arrays)
+    monkeypatch.delenv(hook)
+    assert got[0].keys() == got[1].keys()
+    assert_arrays_equal(got[0], got[1], "DPF_KEYGEN_DYNAMIC=0 against the default")
+    return got[0], per_wg
+
+
+def _abi_runner(H, P, K, d_alphas, d_seeds, d_beta, beta_mode):
+    import torch
+
+    def run(fill):
+        arena = gen_into_arena(H, P, K, d_alphas, d_seeds, d_beta, beta_mode, fill)
+        chunks = H.last_dynamic_chunks()
+        torch.cuda.synchronize()
+        return arena.arrays(), chunks     # asserts the gaps and the guard
+    return run
+
+
+def _shares(dev, evaluate, pts, ppk, size):
+    """Both parties' packed outputs at `pts` (ppk per key) as (K * ppk, size)."""
+    import torch
+    outs = []
+    d_pts = torch.from_numpy(np.ascontiguousarray(pts).view(np.int64)).cuda()
+    for d in dev:
+        out = torch.empty(len(pts) * size, dtype=torch.uint8, device="cuda")
+        assert evaluate(d, d_pts, ppk, out) == len(pts)
+        torch.cuda.synchronize()
+        outs.append(out.cpu().numpy())
+    return outs
+
+
+def _recombine(vt, a, b):
+    kind, bits, _ = O.leaves(vt)[0]
+    dt = {32: np.uint32, 64: np.uint64}[bits]
+    return a.view(dt) ^ b.view(dt) if kind == O.LEAF_XOR else a.view(dt) + b.view(dt)
+
+
+def _points(cols):
+    """(K * len(cols), 2) uint64 points, key-major, from per-key columns."""
+    pts = np.zeros((len(cols[0]), len(cols), 2), np.uint64)
+    for j, c in enumerate(cols):
+        pts[:, j, 0] = c
+    return pts.reshape(-1, 2)
+
+
+def _check_dpf_keys(dpf, levels, dev, alphas, betas):
+    """Every key pair: shares of betas[h][k] at alpha's prefix of level h and
+    of 0 at the prefix with its lowest bit flipped."""
+    top = levels[-1][0]
+    for h, (log, vt, _) in enumerate(levels):
+        prefix = alphas[:, 0] >> np.uint64(top - log)
+        outs = _shares(dev, lambda d, p, n, o: dpf.evaluate_at_batch_to_device(d, h, p, n, o),
+                       _points([prefix, prefix ^ np.uint64(1)]), 2, dpf.packed_size(h))
+        got = _recombine(vt, *outs).reshape(-1, 2)
+        np.testing.assert_array_equal(got[:, 0], betas[h].astype(got.dtype), err_msg=f"level {h}")
+        assert not got[:, 1].any(), f"level {h}"
+
+
+def _oracle_rows(P, got, K, per_wg, okey, limit=48):
+    """The boundary key pairs against the oracle's single-key generation.  The
+    two cases that take longer than the other tests of this module (their host
+    generator reads one Value per key) keep 24: the first and the last pair,
+    the cut-off chunk, both sides of the two boundaries and two more."""
+    ks = boundary_key_pairs(K, per_wg, limit)
+    assert_arrays_equal(rows_of(got, ks, K), oracle_arrays(P, [okey(k) for k in ks]),
+                        "boundary key pairs")
+
+
+def test_keygen_kernel_chunked_shared_betas(H, monkeypatch):
+    """beta_mode 0 through the C ABI, one uint32 level of log domain 7: L = 5,
+    one run of four levels and a tail of one, and, L being odd, control bytes
+    4-aligned for every second key only.  Beta all ones; alphas 0, all ones and
+    random."""
+    levels = [(7, ("int", 32), 0)]
+    vt, beta = levels[0][1], (1 << 32) - 1
+    P = O.OracleParams(levels)
+    assert P.tree_levels_needed - 1 == 5
+    K = _keygen_count()
+    rng, alphas, seeds = _keygen_inputs(7, K, 7, [0, 127])
+    values = [leaves_value(vt, [beta])]
+    run = _abi_runner(H, P, K, H.to_device_blocks(alphas), H.to_device_blocks(seeds),
+                      H.to_device_blocks(np.array([[beta, 0]], np.uint64)), 0)
+    got, per_wg = _keygen_two_schedules(H, monkeypatch, run)
+    dpf = make_dpf(levels)
+    host = dpf.generate_key_batch(alphas, values, root_seeds=seeds)
+    assert_arrays_equal(got, batch_arrays(host[0]), "host batch")
+    _oracle_rows(P, got, K, per_wg,
+                 lambda k: O.generate_keys(P, int(alphas[k, 0]), [[beta]], *seed_ints(seeds, k))[0])
+    del host
+    # The same call through the API: the same bytes, and the keys they hold.
+    dev = dpf.generate_key_batch_to_device(alphas, values, root_seeds=seeds)
+    assert H.last_dynamic_chunks() == per_wg
+    assert_arrays_equal(got, batch_arrays(dpf.download_key_batch(dev[0])), "API")
+    _check_dpf_keys(dpf, levels, dev, alphas, [np.full(K, beta, np.uint64)])
+
+
+def test_keygen_kernel_chunked_per_key_betas(H, monkeypatch):
+    """beta_mode 1 through generate_key_batch_to_device and download_key_batch:
+    uint32 at log domain 5 under XorWrapper<uint64> at 9, tree levels [3, 8],
+    L = 8, two full runs.  Betas 0 and all ones for the first two keys, random
+    after.  A DeviceKeyBatch of this size generates, downloads and evaluates."""
+    levels = [(5, ("int", 32), 0), (9, ("xor", 64), 0)]
+    P = O.OracleParams(levels)
+    assert list(P.hierarchy_to_tree) == [3, 8] and P.tree_levels_needed - 1 == 8
+    K = _keygen_count()
+    rng, alphas, seeds = _keygen_inputs(9, K, 9, [0, 511])
+    betas, cols = [], []
+    for _, vt, _ in levels:
+        b, v = _beta_pool(rng, vt, K, first=[0, (1 << O.leaves(vt)[0][1]) - 1])
+        betas.append(b)
+        cols.append(v)
+    values = [v for pair in zip(*cols) for v in pair]      # key-major
+    dpf = make_dpf(levels)
+    assert dpf.generates_keys_on_device()
+    kept = {}
+
+    def run(fill):
+        dev = dpf.generate_key_batch_to_device(alphas, values, root_seeds=seeds)
+        chunks = H.last_dynamic_chunks()
+        kept.setdefault("dev", dev)                        # the default run's keys
+        parties = [batch_arrays(dpf.download_key_batch(d)) for d in dev]
+        return {f"{name}/{p}": a for p in (0, 1) for name, a in parties[p].items()}, chunks
+
+    got, per_wg = _keygen_two_schedules(H, monkeypatch, run)
+    host = dpf.generate_key_batch_with_betas(alphas, values, root_seeds=seeds)
+    for p in (0, 1):
+        mine = {name[:-2]: a for name, a in got.items() if name.endswith(f"/{p}")}
+        assert_arrays_equal(mine, batch_arrays(host[p]), f"host batch, party {p}")
+        assert set(mine) == set(batch_arrays(host[p]))     # seeds and party bytes too
+        _oracle_rows(P, mine, K, per_wg,
+                     lambda k: O.generate_keys(P, int(alphas[k, 0]),
+                                               [[int(b[k])] for b in betas],
+                                               *seed_ints(seeds, k))[p], limit=24)
+    del host
+    _check_dpf_keys(dpf, levels, kept["dev"], alphas, betas)
+
+
+def test_keygen_kernel_chunked_dcf(H, monkeypatch):
+    """beta_mode 2 through the C ABI: the uint64 DCF of log domain 8, H = 8,
+    L = 7 with a tail of three, one beta per key, every alpha of [0, 256)
+    among the keys.  Evaluated at alpha - 1, alpha and 255: beta below alpha,
+    else 0."""
+    n, vt = 8, ("int", 64)
+    P = O.dcf_params(n, vt)
+    assert len(P.log_domain) == 8 and P.tree_levels_needed - 1 == 7
+    K = _keygen_count()
+    rng, alphas, seeds = _keygen_inputs(8, K, n, np.arange(256))
+    assert set(alphas[:, 0].tolist()) == set(range(256))
+    beta, values = _beta_pool(rng, vt, K, first=[0, (1 << 64) - 1])
+    d_beta = np.zeros((K, 2), np.uint64)
+    d_beta[:, 0] = beta
+    run = _abi_runner(H, P, K, H.to_device_blocks(alphas), H.to_device_blocks(seeds),
+                      H.to_device_blocks(d_beta), 2)
+    got, per_wg = _keygen_two_schedules(H, monkeypatch, run)
+    dcf = make_dcf(vt, n)
+    host = dcf.generate_key_batch(alphas, values, root_seeds=seeds)
+    assert_arrays_equal(got, batch_arrays(host[0]), "host batch")
+    _oracle_rows(P, got, K, per_wg,
+                 lambda k: O.dcf_generate_keys(P, int(alphas[k, 0]), [int(beta[k])],
+                                               *seed_ints(seeds, k))[0], limit=24)
+    del host
+    dev = dcf.generate_key_batch_to_device(alphas, values, root_seeds=seeds)
+    assert H.last_dynamic_chunks() == per_wg
+    assert_arrays_equal(got, batch_arrays(dcf.download_key_batch(dev[0])), "API")
+    a = alphas[:, 0]
+    cols = [(a - np.uint64(1)) & np.uint64(255), a, np.full(K, 255, np.uint64)]
+    outs = _shares(dev, lambda d, p, m, o: dcf.evaluate_batch_to_device(d, p, m, o),
+                   _points(cols), 3, dcf.packed_size())
+    rec = _recombine(vt, *outs).reshape(K, 3)
+    for j, x in enumerate(cols):
+        np.testing.assert_array_equal(rec[:, j], np.where(x < a, beta, np.uint64(0)),
+                                      err_msg=f"point {j}")

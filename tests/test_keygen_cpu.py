@@ -14,8 +14,9 @@ import ref_grids as G
 from distributed_point_functions_amd import dpf as D
 from distributed_point_functions_amd import hip_abi
 from distributed_point_functions_amd import mic as M
-from keygen_common import (assert_batch_equals_oracle, assert_batches_equal, batch_arrays,
-                           seed_ints)
+from keygen_common import (EDGE_LEVELS, KeygenArena, assert_arrays_equal,
+                           assert_batch_equals_oracle, assert_batches_equal, batch_arrays,
+                           boundary_key_pairs, oracle_arrays, rows_of, seed_ints)
 from test_dcf_cpu import make as make_dcf
 from test_host_api_cpu import leaves_value
 from test_key_batch_cpu import make, seeds_array
@@ -93,10 +94,17 @@ def _per_key_betas(levels, n, rng):
     return out
 
 
-@pytest.mark.parametrize("levels", [HIER, WIDE], ids=["hier", "log128"])
+@pytest.mark.parametrize("levels", [HIER, WIDE] + [lv for lv, _ in EDGE_LEVELS],
+                         ids=["hier", "log128"] + [f"edge{i}" for i in range(len(EDGE_LEVELS))])
 def test_with_betas_rows_equal_single_keygen_and_oracle(levels):
+    """The host generator on HIER, WIDE and the level-table edges of
+    keygen_common.EDGE_LEVELS (the device tests of those lean on this batch);
+    the alphas 0 and all ones have bit 127 clear and set."""
     dpf = make(levels)
     P = O.OracleParams(levels)
+    for lv, tree in EDGE_LEVELS:
+        if lv == levels:
+            assert dpf.hierarchy_to_tree() == tree == list(P.hierarchy_to_tree)
     rng = np.random.default_rng(levels[-1][0])
     n = 9
     alphas = _alphas(rng, n, levels[-1][0])
@@ -140,6 +148,118 @@ def test_generators_share_generate_key_batchs_errors():
             gen([1, 256], good)
         with pytest.raises(D.DpfStatusError, match="root_seeds must be empty or hold two seeds per"):
             gen([1, 2], good, root_seeds=np.zeros((3, 2), np.uint64))
+
+
+# ---------------------------------------------------------------- test helpers
+def _filled_arena(batch, fill, offsets=None):
+    """A CPU arena holding the correction words of a host batch."""
+    import torch
+    want = batch_arrays(batch)
+    H = batch.num_hierarchy_levels
+    elements = [len(want[f"vc{h}"]) // batch.num_keys for h in range(H)]
+    arena = KeygenArena(batch.num_keys, batch.num_levels, elements, fill, device="cpu",
+                        offsets=offsets)
+    for name in arena.spans:
+        arena.tensor(name).copy_(torch.from_numpy(np.ascontiguousarray(want[name]).view(np.uint8)
+                                                  .reshape(-1)))
+    return arena, want
+
+
+@pytest.mark.parametrize("offsets", [None, {"cw_left": 3, "cw_right": 1}], ids=["aligned", "offset"])
+def test_arena_comparison_and_gap_check_can_fail(offsets):
+    """The comparisons of the device tests on a CPU tensor: the arena's arrays
+    equal the batch they were filled from, by name; one flipped byte in any one
+    array fails the comparison; one byte written into any gap, before the first
+    array or into the guard fails the gap check."""
+    dpf = make(HIER)
+    rng = np.random.default_rng(11)
+    n = 5
+    beta = [leaves_value(vt, [h + 3]) for h, (_, vt, _) in enumerate(HIER)]
+    batch = dpf.generate_key_batch(_alphas(rng, n, 8), beta, root_seeds=seeds_array(rng, n))[0]
+    arena, want = _filled_arena(batch, 0xAB, offsets)
+    assert set(arena.spans) == set(want) - {"seed", "party"}
+    assert_arrays_equal(arena.arrays(), want)
+    starts = sorted(s for s, _ in arena.spans.values())
+    ends = sorted(s + nb for s, nb in arena.spans.values())
+    assert starts[0] >= KeygenArena.GAP
+    assert all(a - b >= KeygenArena.GAP for a, b in zip(starts[1:], ends))
+    assert arena.size - ends[-1] >= KeygenArena.GAP + KeygenArena.GUARD
+    for name, (start, nbytes) in arena.spans.items():
+        rel = (0 if offsets is None else offsets.get(name, 0))
+        assert (arena.raw.data_ptr() + arena.base + start) % 16 == rel, name
+        # A flipped byte: the first, the last.
+        for at in (0, nbytes - 1):
+            t = arena.tensor(name)
+            t[at] ^= 1
+            with pytest.raises(AssertionError, match=name):
+                assert_arrays_equal(arena.arrays(), want)
+            t[at] ^= 1
+        # A byte written next to the array, on either side.
+        for at in (start - 1, start + nbytes, start + nbytes + KeygenArena.GAP - 1):
+            cell = arena.raw[arena.base + at:arena.base + at + 1]
+            cell.fill_(0x54)
+            with pytest.raises(AssertionError, match="outside the arrays"):
+                arena.arrays()
+            cell.fill_(0xAB)
+    for at in (0, arena.size - KeygenArena.GUARD, arena.size - 1):
+        cell = arena.raw[arena.base + at:arena.base + at + 1]
+        cell.fill_(0)
+        with pytest.raises(AssertionError, match="outside the arrays"):
+            arena.arrays()
+        cell.fill_(0xAB)
+    assert_arrays_equal(arena.arrays(), want)
+    # A missing or an extra array fails too.
+    less = {k: v for k, v in arena.arrays().items() if k != "vc1"}
+    with pytest.raises(AssertionError):
+        assert_arrays_equal(less, want)
+
+
+def test_rows_of_picks_the_oracles_keys():
+    levels = EDGE_LEVELS[4][0]
+    dpf = make(levels)
+    P = O.OracleParams(levels)
+    rng = np.random.default_rng(3)
+    n = 9
+    alphas = _alphas(rng, n, 5)
+    betas = _per_key_betas(levels, n, rng)
+    seeds = seeds_array(rng, n)
+    values = [leaves_value(vt, betas[k][h]) for k in range(n) for h, (_, vt, _) in enumerate(levels)]
+    b0, _ = dpf.generate_key_batch_with_betas(alphas, values, root_seeds=seeds)
+    ks = [0, 4, 8]
+    okeys = [O.generate_keys(P, alphas[k], betas[k], *seed_ints(seeds, k))[0] for k in ks]
+    assert_arrays_equal(rows_of(batch_arrays(b0), ks, n), oracle_arrays(P, okeys))
+    with pytest.raises(AssertionError):
+        assert_arrays_equal(rows_of(batch_arrays(b0), [0, 4, 7], n), oracle_arrays(P, okeys))
+
+
+@pytest.mark.parametrize("cus", [256, 304, 80])
+def test_boundary_key_pairs(cus, monkeypatch):
+    """At the key generation cases' size on a chip of `cus` compute units: the
+    pairs are those of _boundary_items' lanes, at most 48, with the first, the
+    last, the whole cut-off chunk and both sides of a workgroup boundary."""
+    import test_dynamic_chunks_gpu as C
+    monkeypatch.setattr(C, "_cus", lambda: cus)
+    T = 4 * cus * 1024
+    K = T // 2 + 113
+    chunks = -(-2 * K // 64)
+    assert chunks == T // 64 + 4 and 2 * K % 64 == 34
+    per_wg = -(-chunks // cus)
+    lanes = C._boundary_items(2 * K, per_wg)
+    got = boundary_key_pairs(K, per_wg)
+    assert got == sorted(set(got)) and len(got) <= 48
+    assert set(got) <= {u // 2 for u in lanes}
+    assert got[0] == 0 and got[-1] == K - 1
+    assert set(range(K - 17, K)) <= set(got)          # the last chunk's 34 lanes
+    span = per_wg * 64 // 2
+    assert {span - 1, span} <= set(got)
+    owners = -(-chunks // per_wg)
+    assert any((owners - 1) * span <= k < K - 17 for k in got)
+    # A tighter limit keeps the same pairs and samples fewer of the rest.
+    few = boundary_key_pairs(K, per_wg, limit=24)
+    assert len(few) == 24 and set(few) <= {u // 2 for u in lanes}
+    assert set(range(K - 17, K)) | {0, span - 1, span} <= set(few)
+    # A short list is returned whole.
+    assert boundary_key_pairs(K, per_wg, limit=10 ** 6) == sorted({u // 2 for u in lanes})
 
 
 # ---------------------------------------------------------------- DCF

@@ -11,7 +11,8 @@ import oracle as O
 import ref_grids as G
 from distributed_point_functions_amd import dpf as D
 from distributed_point_functions_amd import mic as M
-from keygen_common import (assert_batch_equals_oracle, assert_batches_equal, batch_arrays,
+from keygen_common import (EDGE_LEVELS, KeygenArena, assert_arrays_equal,
+                           assert_batch_equals_oracle, assert_batches_equal, batch_arrays,
                            seed_ints)
 from test_dcf_cpu import make as make_dcf
 from test_host_api_cpu import leaves_value
@@ -33,6 +34,10 @@ CASES = [
     ([(11, ("int", 128), 0)], (33,)),          # L = 11: tail of three
     ([(7, ("xor", 64), 0)], (33,)),            # L = 6: tail of two
     (MIXED, (33, 513)),
+    # The level-table edges: the shift by 128 (alphas with bit 127 set and clear),
+    # every width at an inner level with 4, 3, 2, 1 and 0 index bits, and value
+    # corrections from consecutive tree levels.
+    *[(levels, (33,)) for levels, _ in EDGE_LEVELS],
 ]
 
 
@@ -71,18 +76,28 @@ def _evaluate(dpf, dev, h, pts, ppk, stream=None):
     return _ints(out.cpu().numpy(), size)
 
 
-def _check_point_function(dpf, levels, d0, d1, alphas, beta_of):
-    """Shares sum to beta at alpha and to 0 at its neighbours, at every level."""
+def _check_point_function(dpf, levels, d0, d1, alphas, beta_of, only=None):
+    """Shares sum to beta at alpha and to 0 at its neighbours, at every level
+    (of `only`): the prefix with its lowest bit and with every bit flipped and,
+    where the level's block holds several elements, the point of the prefix's
+    own block whose index differs in the top bit (a level of log domain 0 has
+    the one point 0)."""
     top = levels[-1][0]
+    tree = dpf.hierarchy_to_tree()
     for h, (log, vt, _) in enumerate(levels):
+        if only is not None and h not in only:
+            continue
         kind, bits, _ = O.leaves(vt)[0]
+        index_bits = log - tree[h]
+        assert 0 <= index_bits and (1 << index_bits) <= 128 // bits
+        flips = (0, 1 if log else 0, (1 << log) - 1, (1 << index_bits) >> 1)
         prefixes = [a >> (top - log) for a in alphas]
-        pts = [p ^ d for p in prefixes for d in (0, 1, (1 << log) - 1 if log else 0)]
-        y0, y1 = _evaluate(dpf, d0, h, pts, 3), _evaluate(dpf, d1, h, pts, 3)
+        pts = [p ^ d for p in prefixes for d in flips]
+        y0, y1 = _evaluate(dpf, d0, h, pts, 4), _evaluate(dpf, d1, h, pts, 4)
         for k, p in enumerate(prefixes):
-            for j in range(3):
-                x = pts[3 * k + j]
-                a, b = y0[3 * k + j], y1[3 * k + j]
+            for j in range(4):
+                x = pts[4 * k + j]
+                a, b = y0[4 * k + j], y1[4 * k + j]
                 got = a ^ b if kind == O.LEAF_XOR else (a + b) % (1 << bits)
                 assert got == (beta_of(k, h) if x == p else 0), (h, k, j)
 
@@ -150,6 +165,61 @@ def test_unsupported_value_types_fall_back_to_the_host():
     dev = dpf.generate_key_batch_to_device(alphas, values, root_seeds=seeds)
     for party in (0, 1):
         assert_batches_equal(dpf.download_key_batch(dev[party]), host[party])
+
+
+def test_129_hierarchy_levels_fall_back_to_the_host():
+    """Log domains 0..128 are valid parameters with more hierarchy levels than
+    the kernel's tables hold: the keys are generated on the host."""
+    levels = [(i, ("int", 64), 0) for i in range(129)]
+    dpf = make(levels)
+    assert not dpf.generates_keys_on_device()
+    rng = np.random.default_rng(129)
+    n = 33
+    alphas = _alphas(rng, n, 128)
+    seeds = seeds_array(rng, n)
+    betas = [int(b) for b in rng.integers(1, 1 << 62, size=129)]
+    values = [leaves_value(("int", 64), [b]) for b in betas]
+    host = dpf.generate_key_batch(alphas, values, root_seeds=seeds)
+    dev = dpf.generate_key_batch_to_device(alphas, values, root_seeds=seeds)
+    for party in (0, 1):
+        assert_batches_equal(dpf.download_key_batch(dev[party]), host[party], f"party {party}")
+    _check_point_function(dpf, levels, dev[0], dev[1], alphas, lambda k, h: betas[h],
+                          only=(0, 64, 128))
+
+
+@pytest.mark.parametrize("log", [6, 7], ids=["L4", "L5"])
+def test_unaligned_control_arrays(log):
+    """The C ABI takes any uint8_t* for cw_left and cw_right.  With L = 4 every
+    control store of an aligned base is one dword and none of an offset base
+    is; with L = 5 the keys alternate.  Every array of every placement equals
+    the host batch, and nothing outside the arrays is written."""
+    from distributed_point_functions_amd import hip_abi
+    from keygen_common import gen_into_arena
+    import torch
+    hip_abi.load(require_gpu=True)
+    levels = [(log, ("int", 32), 0)]
+    P = O.OracleParams(levels)
+    assert P.tree_levels_needed - 1 == log - 2
+    dpf = make(levels)
+    rng = np.random.default_rng(log)
+    n = 33
+    alphas = _alphas(rng, n, log)
+    seeds = seeds_array(rng, n)
+    beta = (1 << 32) - 1
+    host = dpf.generate_key_batch(alphas, [leaves_value(("int", 32), [beta])], root_seeds=seeds)
+    want = batch_arrays(host[0])
+    for name in ("cw_seed", "cw_left", "cw_right", "vc0"):   # both parties hold the same
+        np.testing.assert_array_equal(batch_arrays(host[1])[name], want[name])
+    d_alphas = hip_abi.to_device_blocks(D.u128_array(alphas))
+    d_seeds = hip_abi.to_device_blocks(seeds)
+    d_beta = hip_abi.to_device_blocks(D.u128_array([beta]))
+    for fill, (left, right) in zip((0xAB, 0x54, 0xC3, 0x3C), ((0, 0), (1, 2), (2, 3), (3, 1))):
+        arena = gen_into_arena(hip_abi, P, n, d_alphas, d_seeds, d_beta, 0, fill,
+                               offsets={"cw_left": left, "cw_right": right})
+        torch.cuda.synchronize()
+        assert arena.tensor("cw_left").data_ptr() % 4 == left
+        assert arena.tensor("cw_right").data_ptr() % 4 == right
+        assert_arrays_equal(arena.arrays(), want, f"offsets {left}, {right}")
 
 
 def test_generation_and_evaluation_share_a_stream_without_a_sync():
