@@ -200,8 +200,9 @@ def build_tools(force=False):
     (tests/cpp/mic_gate_test.cc), the database fold's
     (tests/cpp/dot_api_test.cc), the bit-selected fold's
     (tests/cpp/select_api_test.cc), the batched sketch's
-    (tests/cpp/sketch_api_test.cc) and the batched key generators'
-    (tests/cpp/keygen_api_test.cc)."""
+    (tests/cpp/sketch_api_test.cc), the batched key generators'
+    (tests/cpp/keygen_api_test.cc) and the full-domain DCF's
+    (tests/cpp/dcf_expand_api_test.cc)."""
     hdrs = _files(os.path.join(INCLUDE), (".h",))
     cxx = os.environ.get("CXX", "g++")
     for src, name in ((os.path.join(ROOT, "tools", "dpf_benchmark.cc"), "dpf_benchmark"),
@@ -213,7 +214,9 @@ def build_tools(force=False):
                       (os.path.join(ROOT, "tests", "cpp", "sketch_api_test.cc"),
                        "sketch_api_test"),
                       (os.path.join(ROOT, "tests", "cpp", "keygen_api_test.cc"),
-                       "keygen_api_test")):
+                       "keygen_api_test"),
+                      (os.path.join(ROOT, "tests", "cpp", "dcf_expand_api_test.cc"),
+                       "dcf_expand_api_test")):
         out = os.path.join(LIBDIR, name)
         if force or _stale(out, [src, os.path.join(LIBDIR, "libdpf.so")] + hdrs):
             _run([cxx, "-O2", "-std=c++20", "-Wall", f"-I{INCLUDE}", src, "-o", out,

@@ -4,10 +4,14 @@
 #include "dcf/distributed_comparison_function.h"
 
 #include <algorithm>
+#include <cstdlib>
+#include <limits>
+#include <optional>
 
 #include "dpf/key_batch.h"
 #include "dpf_hip.h"
 #include "host_util.h"
+#include "shard_plan.h"
 
 namespace distributed_point_functions {
 
@@ -235,6 +239,266 @@ Status DistributedComparisonFunction::Launch(int64_t num_keys, int64_t points_pe
       points, cw_seed, cw_left, cw_right, cw_stride, vcw.data(), &kl, &kr, &kv, &desc, device_out,
       stream));
   return OkStatus();
+}
+
+// ------------------------------------------------------- full-domain evaluation
+// A key batch in device memory as dpf_hip_dcf_expand takes it.
+struct DistributedComparisonFunction::DeviceKeys {
+  int64_t num_keys = 0;
+  const dpf_block* seed = nullptr;
+  const uint8_t* party = nullptr;
+  const dpf_block* cw_seed = nullptr;
+  const uint8_t* cw_left = nullptr;
+  const uint8_t* cw_right = nullptr;
+  int cw_stride = 0;
+  std::vector<const dpf_block*> vcw;   // per level
+};
+
+namespace {
+
+// The slab hook of the database folds (DPF_DOT_SLAB_LOG, read per call; test
+// hook): the log2 of a slab's rows, in place of the scratch bound.
+std::optional<int> DotSlabLogHook() {
+  const char* v = std::getenv("DPF_DOT_SLAB_LOG");
+  return v && *v ? std::optional<int>(std::atoi(v)) : std::nullopt;
+}
+
+}  // namespace
+
+bool DistributedComparisonFunction::EvaluatesFullDomainOnDevice() const {
+  const int n = parameters_.parameters().log_domain_size();
+  std::vector<int32_t> depth(n);
+  for (int i = 0; i < n; ++i) depth[i] = dpf_->hierarchy_to_tree()[i];
+  const dpf_value_desc desc = MakeDesc(dpf_->flat_value_type(0), dpf_->blocks_needed(0));
+  return dpf_hip_dcf_expand_supported(&desc, n, depth.data()) != 0;
+}
+
+Status DistributedComparisonFunction::CheckFullDomainType() const {
+  if (EvaluatesFullDomainOnDevice()) return OkStatus();
+  return UnimplementedError(
+      "full-domain DCF evaluation is implemented for one integer or XorWrapper value of 8, 16, "
+      "32, 64 or 128 bits");
+}
+
+Status DistributedComparisonFunction::LaunchFullDomain(const DeviceKeys& keys, int shard_bits,
+                                                       int64_t shard, void* device_out,
+                                                       void* stream) const {
+  const int n = parameters_.parameters().log_domain_size();
+  const dpf_value_desc desc = MakeDesc(dpf_->flat_value_type(0), dpf_->blocks_needed(0));
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  HIP_RETURN_IF_ERROR(dpf_hip_dcf_expand(keys.num_keys, n, shard_bits, shard, keys.seed, keys.party,
+                                         keys.cw_seed, keys.cw_left, keys.cw_right,
+                                         keys.cw_stride, keys.vcw.data(), &kl, &kr, &kv, &desc,
+                                         device_out, stream));
+  return OkStatus();
+}
+
+Status DistributedComparisonFunction::UploadKey(const KeyBatch& batch,
+                                                dpf_internal::PackedUploads& up, void* stream,
+                                                DeviceKeys* keys) const {
+  const int n = parameters_.parameters().log_domain_size();
+  const int L = batch.num_levels;
+  std::vector<dpf_block> vcw_all;
+  std::vector<size_t> vcw_off(n);
+  for (int i = 0; i < n; ++i) {
+    vcw_off[i] = vcw_all.size();
+    vcw_all.insert(vcw_all.end(), batch.value_correction[i].begin(),
+                   batch.value_correction[i].end());
+  }
+  DPF_RETURN_IF_ERROR(up.Reset());
+  const size_t o_seed = up.Add(batch.seed.data(), 1);
+  const size_t o_party = up.Add(batch.party.data(), 1);
+  const size_t o_cws = up.Add(batch.cw_seed.data(), L);
+  const size_t o_cwl = up.Add(batch.cw_left.data(), L);
+  const size_t o_cwr = up.Add(batch.cw_right.data(), L);
+  const size_t o_vcw = up.Add(vcw_all.data(), vcw_all.size());
+  DPF_RETURN_IF_ERROR(up.Commit(stream));
+  keys->num_keys = 1;
+  keys->seed = up.Ptr<dpf_block>(o_seed);
+  keys->party = up.Ptr<uint8_t>(o_party);
+  keys->cw_seed = up.Ptr<dpf_block>(o_cws);
+  keys->cw_left = up.Ptr<uint8_t>(o_cwl);
+  keys->cw_right = up.Ptr<uint8_t>(o_cwr);
+  keys->cw_stride = L;
+  keys->vcw.resize(n);
+  for (int i = 0; i < n; ++i) keys->vcw[i] = up.Ptr<dpf_block>(o_vcw) + vcw_off[i];
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedComparisonFunction::EvaluateFullDomainToDevice(
+    const DcfKey& key, int64_t shard, int64_t num_shards, void* device_out,
+    int64_t capacity_bytes, void* stream) {
+  const int n = parameters_.parameters().log_domain_size();
+  const DcfKey* kp = &key;
+  DPF_ASSIGN_OR_RETURN(KeyBatch batch, MakeKeyBatch(Span<const DcfKey* const>(&kp, 1)));
+  DPF_ASSIGN_OR_RETURN(const int k, dpf_internal::ShardLevels(shard, num_shards, n - 1, n, 0));
+  const int64_t total = int64_t{1} << (n - k);
+  const auto& f = dpf_->flat_value_type(0);
+  if (!device_out || capacity_bytes / f.packed_size < total)
+    return InvalidArgumentError("device output buffer too small");
+  DPF_RETURN_IF_ERROR(CheckFullDomainType());
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  DeviceKeys keys;
+  DPF_RETURN_IF_ERROR(UploadKey(batch, s->packed, stream, &keys));
+  DPF_RETURN_IF_ERROR(LaunchFullDomain(keys, k, shard, device_out, stream));
+  DPF_RETURN_IF_ERROR(s->packed.MarkUsed(stream));
+  return total;
+}
+
+StatusOr<int64_t> DistributedComparisonFunction::EvaluateFullDomainBatchToDevice(
+    const DeviceKeyBatch& keys, int64_t shard, int64_t num_shards, void* device_out,
+    int64_t capacity_bytes, void* stream) const {
+  const int n = parameters_.parameters().log_domain_size();
+  if (keys.num_levels() != dpf_->tree_levels_needed() - 1 || keys.num_hierarchy_levels() != n)
+    return InvalidArgumentError("key batch does not match this DistributedComparisonFunction");
+  DPF_ASSIGN_OR_RETURN(const int k, dpf_internal::ShardLevels(shard, num_shards, n - 1, n, 0));
+  const int64_t row = int64_t{1} << (n - k);
+  const auto& f = dpf_->flat_value_type(0);
+  if (keys.num_keys() > std::numeric_limits<int64_t>::max() / (row * f.packed_size))
+    return InvalidArgumentError("device output buffer too small");
+  const int64_t total = keys.num_keys() * row;
+  if (total > 0 && (!device_out || capacity_bytes / f.packed_size < total))
+    return InvalidArgumentError("device output buffer too small");
+  DPF_RETURN_IF_ERROR(CheckFullDomainType());
+  if (total == 0) return int64_t{0};
+  DeviceKeys d;
+  d.num_keys = keys.num_keys();
+  d.seed = keys.seed();
+  d.party = keys.party();
+  d.cw_seed = keys.cw_seed();
+  d.cw_left = keys.cw_left();
+  d.cw_right = keys.cw_right();
+  d.cw_stride = keys.num_levels();
+  d.vcw.resize(n);
+  for (int i = 0; i < n; ++i) d.vcw[i] = keys.value_correction(i);
+  DPF_RETURN_IF_ERROR(LaunchFullDomain(d, k, shard, device_out, stream));
+  return total;
+}
+
+StatusOr<std::vector<uint8_t>> DistributedComparisonFunction::EvaluateFullDomainPacked(
+    const DcfKey& key, const ValueType* requested_type) {
+  const int n = parameters_.parameters().log_domain_size();
+  if (requested_type) {
+    DPF_ASSIGN_OR_RETURN(bool eq, dpf_internal::ValueTypesAreEqual(
+                                      *requested_type, parameters_.parameters().value_type()));
+    if (!eq) return InvalidArgumentError("Value type T doesn't match parameters at `hierarchy_level`");
+  }
+  const DcfKey* kp = &key;
+  DPF_ASSIGN_OR_RETURN(KeyBatch batch, MakeKeyBatch(Span<const DcfKey* const>(&kp, 1)));
+  DPF_RETURN_IF_ERROR(dpf_internal::ShardLevels(0, 1, n - 1, n, 0).status());
+  DPF_RETURN_IF_ERROR(CheckFullDomainType());
+  const auto& f = dpf_->flat_value_type(0);
+  const size_t bytes = (size_t{1} << n) * f.packed_size;
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  void* small = s->small_out.Get(bytes);   // small results: written to page-locked memory
+  if (!small) DPF_RETURN_IF_ERROR(s->out.Reserve(bytes));
+  void* const dev_out = small ? small : s->out.get();
+  DeviceKeys keys;
+  DPF_RETURN_IF_ERROR(UploadKey(batch, s->packed, nullptr, &keys));
+  DPF_RETURN_IF_ERROR(LaunchFullDomain(keys, 0, 0, dev_out, nullptr));
+  DPF_RETURN_IF_ERROR(s->packed.MarkUsed(nullptr));
+  std::vector<uint8_t> out(bytes);
+  if (small) {
+    HIP_RETURN_IF_ERROR(dpf_hip_stream_sync(nullptr));
+    std::memcpy(out.data(), small, bytes);
+  } else {
+    HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), s->out.get(), out.size(), nullptr));
+  }
+  return out;
+}
+
+// What a range dot call is once its arguments have passed the host checks.
+struct DistributedComparisonFunction::RangeDotCall {
+  KeyBatch batch;
+  int shard_bits = 0;
+  dpf_internal::SlabPlan slab{0, 1, 0};
+  int workspace_bytes = 0;
+};
+
+Status DistributedComparisonFunction::CheckRangeDot(const DcfKey& key, int64_t shard,
+                                                    int64_t num_shards, const void* device_db,
+                                                    int64_t db_bytes, int64_t record_words,
+                                                    bool has_out, const void* device_out,
+                                                    int64_t out_bytes, RangeDotCall* call) const {
+  const int n = parameters_.parameters().log_domain_size();
+  const DcfKey* kp = &key;
+  DPF_ASSIGN_OR_RETURN(call->batch, MakeKeyBatch(Span<const DcfKey* const>(&kp, 1)));
+  DPF_ASSIGN_OR_RETURN(call->shard_bits,
+                       dpf_internal::ShardLevels(shard, num_shards, n - 1, n, 0));
+  if (record_words < 1 || record_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
+    return InvalidArgumentError("`record_words` must be in [1, 1024]");
+  const int W = static_cast<int>(record_words);
+  const int64_t rows = int64_t{1} << (n - call->shard_bits);   // records of this shard
+  constexpr int64_t kWord = 8;
+  if (rows > std::numeric_limits<int64_t>::max() / (kWord * W) || db_bytes < rows * kWord * W)
+    return InvalidArgumentError("database buffer too small");
+  if (has_out && out_bytes < kWord * W)
+    return InvalidArgumentError("device output buffer too small");
+  if (!device_db || (has_out && !device_out))
+    return InvalidArgumentError("`device_db` and `device_out` must not be null");
+  DPF_RETURN_IF_ERROR(CheckFullDomainType());
+  const dpf_value_desc desc = MakeDesc(dpf_->flat_value_type(0), dpf_->blocks_needed(0));
+  if (desc.kind[0] != DPF_LEAF_INT || desc.bits[0] != 64)
+    return UnimplementedError("EvaluateRangeDot is implemented for uint64_t");
+  call->workspace_bytes = dpf_hip_expand_dot_workspace_bytes(&desc, W);
+  if (call->workspace_bytes < 0) return UnimplementedError(dpf_hip_last_error());
+  // 2^j slabs of the shard, each a sub-shard whose share vector fits the
+  // scratch bound; a slab keeps at least two outputs (one last-level node).
+  DPF_ASSIGN_OR_RETURN(call->slab, dpf_internal::PlanSlabs(rows, 2, 8 * kWord, DotSlabLogHook()));
+  return OkStatus();
+}
+
+Status DistributedComparisonFunction::RunRangeDot(const RangeDotCall& call, int64_t shard,
+                                                  const void* device_db, int64_t record_words,
+                                                  void* device_out, void* stream) {
+  constexpr int64_t kWord = 8;
+  const int W = static_cast<int>(record_words);
+  const dpf_value_desc desc = MakeDesc(dpf_->flat_value_type(0), dpf_->blocks_needed(0));
+  const dpf_internal::SlabPlan& slab = call.slab;
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  DeviceKeys keys;
+  DPF_RETURN_IF_ERROR(UploadKey(call.batch, s->packed, stream, &keys));
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace, call.workspace_bytes, stream));
+  DPF_RETURN_IF_ERROR(s->out.Reserve(static_cast<size_t>(slab.slab_rows * kWord)));
+  for (int64_t i = 0; i < slab.slabs; ++i) {
+    DPF_RETURN_IF_ERROR(LaunchFullDomain(keys, call.shard_bits + slab.j, (shard << slab.j) | i,
+                                         s->out.get(), stream));
+    HIP_RETURN_IF_ERROR(dpf_hip_dot_rows(
+        slab.slab_rows, W, &desc, s->out.get(),
+        static_cast<const char*>(device_db) + i * slab.slab_rows * kWord * W, i > 0,
+        s->workspace.get(), device_out, stream));
+  }
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  return s->packed.MarkUsed(stream);
+}
+
+StatusOr<int64_t> DistributedComparisonFunction::EvaluateRangeDotToDevice(
+    const DcfKey& key, int64_t shard, int64_t num_shards, const void* device_db, int64_t db_bytes,
+    int64_t record_words, void* device_out, int64_t out_bytes, void* stream) {
+  RangeDotCall call;
+  DPF_RETURN_IF_ERROR(CheckRangeDot(key, shard, num_shards, device_db, db_bytes, record_words,
+                                    true, device_out, out_bytes, &call));
+  DPF_RETURN_IF_ERROR(RunRangeDot(call, shard, device_db, record_words, device_out, stream));
+  return record_words;
+}
+
+StatusOr<std::vector<uint64_t>> DistributedComparisonFunction::EvaluateRangeDot(
+    const DcfKey& key, const void* device_db, int64_t db_bytes, int64_t record_words) {
+  // Checked before the result buffer is allocated: host errors touch no device.
+  RangeDotCall call;
+  DPF_RETURN_IF_ERROR(CheckRangeDot(key, 0, 1, device_db, db_bytes, record_words, false, nullptr,
+                                    0, &call));
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);
+  const size_t bytes = static_cast<size_t>(record_words) * 8;
+  DPF_RETURN_IF_ERROR(s->gathered.Reserve(bytes));
+  DPF_RETURN_IF_ERROR(RunRangeDot(call, 0, device_db, record_words, s->gathered.get(), nullptr));
+  std::vector<uint64_t> result(static_cast<size_t>(record_words));
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(result.data(), s->gathered.get(), bytes, nullptr));
+  return result;
 }
 
 StatusOr<std::vector<uint8_t>> DistributedComparisonFunction::EvaluateByLevels(

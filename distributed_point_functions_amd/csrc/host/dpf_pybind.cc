@@ -612,6 +612,51 @@ class PyDcf {
     }
     return *r;
   }
+  int64_t EvaluateFullDomainToDevice(const py::bytes& key_bytes, int64_t shard, int64_t num_shards,
+                                     uintptr_t out, int64_t capacity, uintptr_t stream) {
+    const DcfKey key = Parse<DcfKey>(key_bytes);
+    return TakeNoGil([&] {
+      return dcf_->EvaluateFullDomainToDevice(key, shard, num_shards, reinterpret_cast<void*>(out),
+                                              capacity, reinterpret_cast<void*>(stream));
+    });
+  }
+  int64_t EvaluateFullDomainBatchToDevice(const PyDeviceKeyBatch& keys, int64_t shard,
+                                          int64_t num_shards, uintptr_t out, int64_t capacity,
+                                          uintptr_t stream) {
+    return TakeNoGil([&] {
+      return dcf_->EvaluateFullDomainBatchToDevice(*keys.d, shard, num_shards,
+                                                   reinterpret_cast<void*>(out), capacity,
+                                                   reinterpret_cast<void*>(stream));
+    });
+  }
+  py::array_t<uint8_t> EvaluateFullDomainPacked(const py::bytes& key_bytes, const py::object& vt) {
+    const DcfKey key = Parse<DcfKey>(key_bytes);
+    auto t = OptType(vt);
+    return ToArray(TakeNoGil([&] { return dcf_->EvaluateFullDomainPacked(key, t.get()); }));
+  }
+  bool EvaluatesFullDomainOnDevice() const { return dcf_->EvaluatesFullDomainOnDevice(); }
+  int64_t EvaluateRangeDotToDevice(const py::bytes& key_bytes, int64_t shard, int64_t num_shards,
+                                   uintptr_t db, int64_t db_bytes, int64_t record_words,
+                                   uintptr_t out, int64_t out_bytes, uintptr_t stream) {
+    const DcfKey key = Parse<DcfKey>(key_bytes);
+    return TakeNoGil([&] {
+      return dcf_->EvaluateRangeDotToDevice(key, shard, num_shards,
+                                            reinterpret_cast<const void*>(db), db_bytes,
+                                            record_words, reinterpret_cast<void*>(out), out_bytes,
+                                            reinterpret_cast<void*>(stream));
+    });
+  }
+  py::array_t<uint64_t> EvaluateRangeDot(const py::bytes& key_bytes, uintptr_t db, int64_t db_bytes,
+                                         int64_t record_words) {
+    const DcfKey key = Parse<DcfKey>(key_bytes);
+    const std::vector<uint64_t> v = TakeNoGil([&] {
+      return dcf_->EvaluateRangeDot(key, reinterpret_cast<const void*>(db), db_bytes,
+                                    record_words);
+    });
+    py::array_t<uint64_t> a(static_cast<py::ssize_t>(v.size()));
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * 8);
+    return a;
+  }
   py::tuple GenerateKeyBatch(const U64Array& alphas, const std::vector<py::bytes>& betas,
                              const py::object& root_seeds, int threads) {
     std::vector<Value> v;
@@ -860,6 +905,12 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("generate_key_batch_to_device", &PyDcf::GenerateKeyBatchToDevice)
       .def("generates_keys_on_device", &PyDcf::GeneratesKeysOnDevice)
       .def("evaluate_batch_to_device", &PyDcf::EvaluateBatchToDevice)
+      .def("evaluate_full_domain_to_device", &PyDcf::EvaluateFullDomainToDevice)
+      .def("evaluate_full_domain_batch_to_device", &PyDcf::EvaluateFullDomainBatchToDevice)
+      .def("evaluate_full_domain_packed", &PyDcf::EvaluateFullDomainPacked)
+      .def("evaluates_full_domain_on_device", &PyDcf::EvaluatesFullDomainOnDevice)
+      .def("evaluate_range_dot_to_device", &PyDcf::EvaluateRangeDotToDevice)
+      .def("evaluate_range_dot", &PyDcf::EvaluateRangeDot)
       .def("packed_size", &PyDcf::PackedSize)
       .def("hierarchy_to_tree", &PyDcf::HierarchyToTree);
   py::class_<PyDeviceMicKeyBatch>(m, "DeviceMicKeyBatch")

@@ -1,7 +1,8 @@
 """Python mirror of the reference's DistributedComparisonFunction
 (dcf/distributed_comparison_function.h:30-105), backed by the host C++ class
 of csrc/host/distributed_comparison_function.cc whose evaluation runs in the
-gfx950 kernel dpf_hip_dcf_eval_batch.  Same names (snake_case), argument
+gfx950 kernel dpf_hip_dcf_eval_batch (point by point) or dpf_hip_dcf_expand
+(the whole domain).  Same names (snake_case), argument
 meaning and errors (DpfStatusError with the reference's messages)."""
 from __future__ import annotations
 
@@ -110,6 +111,58 @@ class DistributedComparisonFunction:
         return D._call(self._impl.evaluate_batch_to_device, device_batch, points.data_ptr(),
                        int(points_per_key), bool(shared_points), out.data_ptr(),
                        out.numel() * out.element_size(), s.cuda_stream)
+
+    # ---- full-domain evaluation (one depth-first walk of the key's tree) ----
+    def evaluates_full_domain_on_device(self) -> bool:
+        """True for the value types the full-domain kernel takes (one integer or
+        XorWrapper of 8 to 128 bits); the calls below are UNIMPLEMENTED for
+        every other type -- no per-point path stands in for them."""
+        return self._impl.evaluates_full_domain_on_device()
+
+    def evaluate_full_domain_to_device(self, key: pb.DcfKey, out, shard: int = 0,
+                                       num_shards: int = 1, stream=None) -> int:
+        """The shares of evaluate(key, x) at every x of shard `shard` of
+        `num_shards` (a power of two; the x whose top bits are `shard`), packed
+        [x - first_x] into the device tensor `out`; returns the element count."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        return D._call(self._impl.evaluate_full_domain_to_device, key.SerializeToString(),
+                       int(shard), int(num_shards), out.data_ptr(),
+                       out.numel() * out.element_size(), s.cuda_stream)
+
+    def evaluate_full_domain_batch_to_device(self, device_batch, out, shard: int = 0,
+                                             num_shards: int = 1, stream=None) -> int:
+        """The same for every key of a device batch: packed [key][x - first_x]."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        return D._call(self._impl.evaluate_full_domain_batch_to_device, device_batch, int(shard),
+                       int(num_shards), out.data_ptr(), out.numel() * out.element_size(),
+                       s.cuda_stream)
+
+    def evaluate_full_domain_packed(self, key: pb.DcfKey,
+                                    value_type: Optional[pb.ValueType] = None) -> np.ndarray:
+        """The whole domain on the host: uint8 (2^n, packed_size)."""
+        out = D._call(self._impl.evaluate_full_domain_packed, key.SerializeToString(),
+                      None if value_type is None else value_type.SerializeToString())
+        return out.reshape(-1, self._impl.packed_size())
+
+    def evaluate_range_dot_to_device(self, key: pb.DcfKey, db, record_words: int, out,
+                                     shard: int = 0, num_shards: int = 1, stream=None) -> int:
+        """Private range query (uint64 DCFs): out[w] = sum over the shard's x of
+        f(x) * db[x - first_x][w] mod 2^64; the two parties' results add to
+        beta * sum(db[x][w] for x < alpha).  `db` is the shard's records as a
+        device tensor of record_words uint64 each."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        return D._call(self._impl.evaluate_range_dot_to_device, key.SerializeToString(),
+                       int(shard), int(num_shards), db.data_ptr(),
+                       db.numel() * db.element_size(), int(record_words), out.data_ptr(),
+                       out.numel() * out.element_size(), s.cuda_stream)
+
+    def evaluate_range_dot(self, key: pb.DcfKey, db, record_words: int) -> np.ndarray:
+        """The whole domain's fold on the host: uint64 (record_words,)."""
+        return D._call(self._impl.evaluate_range_dot, key.SerializeToString(), db.data_ptr(),
+                       db.numel() * db.element_size(), int(record_words))
 
     def packed_size(self) -> int:
         return self._impl.packed_size()

@@ -147,6 +147,11 @@ def load(require_gpu: bool = False):
                              [I64, I, I, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P]),
                             ("dpf_hip_prefix_batch_sketch_fused", [P, I, I, I, I, I, I]),
                             ("dpf_hip_sketch_slot_weights", [I64, I64, P, P, I, P, P, P]),
+                            ("dpf_hip_dcf_expand_supported", [P, I, P]),
+                            ("dpf_hip_dcf_expand",
+                             [I64, I, I, I64, P, P, P, P, P, I, P, P, P, P, P, P, P]),
+                            ("dpf_hip_dcf_expand_plan",
+                             [I64, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_prefix_batch_max_expand", [P, I]),
                             ("dpf_hip_prefix_batch_level", [ctypes.POINTER(PrefixBatchArgs), P])):
             if hasattr(L, name):
@@ -220,6 +225,16 @@ def last_dynamic_chunks() -> int:
     n = ctypes.c_int64(-1)
     check(load().dpf_hip_last_dynamic_chunks(ctypes.byref(n)))
     return n.value
+
+
+def dcf_expand_plan(num_keys: int, num_levels: int, shard_bits: int, compute_units: int) -> dict:
+    """The launch plan of dpf_hip_dcf_expand for that shape (no GPU needed):
+    {"G", "walk", "items", "items_per_key", "top_G", "top_items"}; top_G is
+    -1 when no first launch leaves the items their roots."""
+    out = (ctypes.c_int64 * 6)()
+    check(load().dpf_hip_dcf_expand_plan(num_keys, num_levels, shard_bits, compute_units, out))
+    return {"G": out[0], "walk": out[1], "items": out[2], "items_per_key": out[3],
+            "top_G": out[4], "top_items": out[5]}
 
 
 def clock_probe(on: bool) -> None:

@@ -22,6 +22,7 @@ namespace distributed_point_functions {
 
 namespace dpf_internal {
 class DeviceScratch;
+class PackedUploads;
 }
 
 class DistributedComparisonFunction {
@@ -68,6 +69,55 @@ class DistributedComparisonFunction {
                                           int64_t points_per_key, bool shared_points,
                                           void* device_out, int64_t capacity_bytes,
                                           void* stream) const;
+  // ---- full-domain evaluation ------------------------------------------------
+  // Evaluate(key, x) at every x of the domain in one depth-first walk of the
+  // key's tree (dpf_hip_dcf_expand: 2^(n+1) - 3 AES for 2^n outputs, against
+  // (2n - 1) * 2^n point by point).  Only for the value types
+  // EvaluatesFullDomainOnDevice() reports -- one integer or XorWrapper of 8 to
+  // 128 bits; every other type is UNIMPLEMENTED: no per-point path stands in.
+  // Shard `shard` of `num_shards` = 2^k is the x whose top k bits are `shard`
+  // (num_shards <= 2^(n-1)).  Checked before the device is touched, in this
+  // order: requested type, key or batch, shard arguments, record_words,
+  // buffers, value type.
+  //
+  // Packed elements [x - first_x] of one key's shard into `device_out` (16-byte
+  // aligned) on `stream`; returns the number of elements written.
+  StatusOr<int64_t> EvaluateFullDomainToDevice(const DcfKey& key, int64_t shard,
+                                               int64_t num_shards, void* device_out,
+                                               int64_t capacity_bytes, void* stream);
+  // The same for every key of a device batch: [key][x - first_x].
+  StatusOr<int64_t> EvaluateFullDomainBatchToDevice(const DeviceKeyBatch& keys, int64_t shard,
+                                                    int64_t num_shards, void* device_out,
+                                                    int64_t capacity_bytes, void* stream) const;
+  // The whole domain on the host.  `requested_type` (may be null) plays the
+  // role of T.
+  StatusOr<std::vector<uint8_t>> EvaluateFullDomainPacked(
+      const DcfKey& key, const ValueType* requested_type = nullptr);
+  template <typename T>
+  StatusOr<std::vector<T>> EvaluateFullDomain(const DcfKey& key) {
+    ValueType t = ToValueType<T>();
+    StatusOr<std::vector<uint8_t>> packed = EvaluateFullDomainPacked(key, &t);
+    if (!packed.ok()) return packed.status();
+    const auto& f = dpf_->flat_value_type(0);
+    return dpf_internal::UnpackElements<T>(f, packed->data(),
+                                           static_cast<int64_t>(packed->size() / f.packed_size));
+  }
+  bool EvaluatesFullDomainOnDevice() const;
+  // Private range query over a database of uint64 records (uint64_t DCFs
+  // only, the integer type dpf_hip_dot_rows takes): out[w] = sum over the
+  // shard's x of f(x) * db[x - first_x][w] mod 2^64, so the two parties'
+  // results add to beta * (sum of db[x][w] over x < alpha).  `device_db` holds
+  // the shard's records, record_words uint64 each.  A host composition: the
+  // shard's share vector is written slab by slab -- sub-shards of the same
+  // kernel -- into this object's scratch and folded by dpf_hip_dot_rows.
+  // Returns record_words.
+  StatusOr<int64_t> EvaluateRangeDotToDevice(const DcfKey& key, int64_t shard, int64_t num_shards,
+                                             const void* device_db, int64_t db_bytes,
+                                             int64_t record_words, void* device_out,
+                                             int64_t out_bytes, void* stream);
+  // The whole domain's fold on the host: record_words uint64.
+  StatusOr<std::vector<uint64_t>> EvaluateRangeDot(const DcfKey& key, const void* device_db,
+                                                   int64_t db_bytes, int64_t record_words);
   // SoA batch of the DpfKeys inside `keys` (validated like EvaluateAt does).
   StatusOr<KeyBatch> MakeKeyBatch(Span<const DcfKey* const> keys) const;
   // Key generation for many alphas at once, straight into SoA form: row k of
@@ -112,6 +162,26 @@ class DistributedComparisonFunction {
                 const dpf_block* cw_seed, const uint8_t* cw_left, const uint8_t* cw_right,
                 int cw_stride, const std::vector<const dpf_block*>& vcw, void* device_out,
                 void* stream) const;
+
+  // dpf_hip_dcf_expand for a key batch in device memory: shard `shard` of
+  // 2^shard_bits, for every key of the batch.
+  struct DeviceKeys;
+  Status LaunchFullDomain(const DeviceKeys& keys, int shard_bits, int64_t shard, void* device_out,
+                          void* stream) const;
+  // Packs one key's batch into `up` (reset here, committed on `stream`).
+  Status UploadKey(const KeyBatch& batch, dpf_internal::PackedUploads& up, void* stream,
+                   DeviceKeys* keys) const;
+  // UNIMPLEMENTED unless dpf_hip_dcf_expand takes this DCF.
+  Status CheckFullDomainType() const;
+  // The host checks of a range dot call (device_out only where `has_out`) and
+  // what they work out; then the call itself.
+  struct RangeDotCall;
+  Status CheckRangeDot(const DcfKey& key, int64_t shard, int64_t num_shards,
+                       const void* device_db, int64_t db_bytes, int64_t record_words,
+                       bool has_out, const void* device_out, int64_t out_bytes,
+                       RangeDotCall* call) const;
+  Status RunRangeDot(const RangeDotCall& call, int64_t shard, const void* device_db,
+                     int64_t record_words, void* device_out, void* stream);
 
   const DcfParameters parameters_;
   const std::unique_ptr<DistributedPointFunction> dpf_;

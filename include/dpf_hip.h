@@ -628,6 +628,46 @@ int dpf_hip_dcf_eval_batch(int64_t num_keys, int64_t points_per_key, int shared_
                            const dpf_aes_key* key_value, const dpf_value_desc* desc,
                            void* out, void* stream);
 
+/* ---- full-domain DCF evaluation --------------------------------------------
+ * No reference counterpart.  The shares of Evaluate(key_k, x) at every x of
+ * the DCF's domain, or of shard `shard_index` of its 2^shard_bits equal
+ * parts, in one depth-first walk of each key's tree (every node hashed once:
+ * 2^(n+1) - 3 AES for 2^n outputs, against (2n - 1) * 2^n point by point):
+ *   out[k * 2^(n - shard_bits) + (x - first_x)] = Evaluate(key_k, x),
+ *   first_x = shard_index * 2^(n - shard_bits),
+ * packed elements.  The key batch is passed as dpf_hip_dcf_eval_batch takes
+ * it.  Only for the DCFs dpf_hip_dcf_expand_supported reports: one integer or
+ * XorWrapper leaf of 8, 16, 32, 64 or 128 bits and level_depth[i] == i (every
+ * DCF the validator builds for such a type); others: 12 UNIMPLEMENTED -- there
+ * is no per-point fallback behind this call.  Argument errors are reported
+ * before any device call: 3 for negative counts, NULL tables, shard_bits
+ * outside [0, n - 1], shard_index outside [0, 2^shard_bits), n - shard_bits >
+ * 62 and an `out` that is not 16-byte aligned.  num_keys == 0 returns 0
+ * without a launch.  The item loop is dynamic as chunked launches are
+ * (DPF_DCF_EXPAND_DYNAMIC=0, read per launch: a fixed share per thread; A/B
+ * and test hook), and dpf_hip_last_dynamic_chunks reports it. */
+int dpf_hip_dcf_expand_supported(const dpf_value_desc* desc, int num_levels,
+                                 const int32_t* level_depth);
+int dpf_hip_dcf_expand(int64_t num_keys, int num_levels, int shard_bits, int64_t shard_index,
+                       const dpf_block* key_seed, const uint8_t* party,
+                       const dpf_block* cw_seed, const uint8_t* cw_left,
+                       const uint8_t* cw_right, int cw_stride,
+                       const dpf_block* const* value_correction,
+                       const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+                       const dpf_aes_key* key_value, const dpf_value_desc* desc, void* out,
+                       void* stream);
+/* The launch plan of dpf_hip_dcf_expand on a device of num_cus compute units,
+ * a pure function (no device is touched): a work item is (key, subtree), the
+ * subtree's root lies at depth walk = n - 1 - G and the item visits G levels
+ * depth-first and writes 2^(G+1) outputs.  out = {G, walk, items, items per
+ * key, top_G, top_items}: with top_G >= 0 a first launch of top_items items,
+ * each walking from its key's root and visiting top_G levels, leaves every
+ * item its root in the first bytes of the item's own outputs, and the items
+ * walk nothing; with top_G == -1 every item walks from its key's root.  3 for
+ * arguments dpf_hip_dcf_expand rejects, num_keys < 1 or num_cus < 1. */
+int dpf_hip_dcf_expand_plan(int64_t num_keys, int num_levels, int shard_bits, int num_cus,
+                            int64_t out[6]);
+
 /* ---- batched multiple-interval-containment gate (eprint 2020/1392 Fig. 14) -
  * MultipleIntervalContainmentGate::Eval (dcf/fss_gates/
  * multiple_interval_containment.cc:206-275) for num_gates gates over
