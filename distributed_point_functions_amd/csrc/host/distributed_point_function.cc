@@ -1032,6 +1032,99 @@ StatusOr<std::vector<uint8_t>> DistributedPointFunction::EvaluateDotPacked(
   return out;
 }
 
+// Private table lookup over a key batch: one fused launch (dpf_lookup.hip).
+// The host's part is the argument checks, in the order the header gives.
+bool DistributedPointFunction::EvaluatesLookupOnDevice(int hierarchy_level) const {
+  if (!CheckLevel(hierarchy_level, parameters().size()).ok()) return false;
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  return dpf_hip_lookup_supported(&desc, 1) != 0 && n >= 1 && n <= 40;
+}
+
+Status DistributedPointFunction::CheckLookupArgs(int64_t num_keys, bool batch_matches,
+                                                 int hierarchy_level, const void* device_offsets,
+                                                 const void* device_table, int64_t table_bytes,
+                                                 int64_t table_words, const void* device_out,
+                                                 int64_t out_bytes) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  if (!dpf_hip_lookup_supported(&desc, 1))
+    return UnimplementedError(
+        "the table lookup is implemented for uint64_t and XorWrapper<uint64_t> only");
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  if (n < 1 || n > 40)
+    return InvalidArgumentError("the table lookup takes a log_domain_size in [1, 40]");
+  if (table_words < 1 || table_words > DPF_HIP_DOT_MAX_RECORD_WORDS)
+    return InvalidArgumentError("`table_words` must be in [1, 1024]");
+  if (!dpf_hip_lookup_supported(&desc, static_cast<int>(table_words)))
+    return UnimplementedError("the table lookup is implemented for table_words 1, 2 and 4 only");
+  if (table_bytes != (int64_t{1} << n) * table_words * 8)
+    return InvalidArgumentError("`table_bytes` must be 2^log_domain_size * table_words * 8");
+  if (!device_offsets || !device_table || !device_out)
+    return InvalidArgumentError(
+        "`device_offsets`, `device_table` and `device_out` must not be null");
+  if (num_keys < 0 || out_bytes / (table_words * 8) < num_keys)
+    return InvalidArgumentError("device output buffer too small");
+  if (!batch_matches)
+    return InvalidArgumentError("key batch does not match this DistributedPointFunction");
+  if ((reinterpret_cast<uintptr_t>(device_table) & (table_words == 1 ? 7 : 15)) != 0 ||
+      (reinterpret_cast<uintptr_t>(device_out) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(device_offsets) & 7) != 0)
+    return InvalidArgumentError(
+        "`device_table` must be aligned to min(16, 8 * table_words) bytes, `device_offsets` "
+        "and `device_out` to 8");
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateLookupBatchToDevice(
+    const DeviceKeyBatch& keys, int hierarchy_level, const uint64_t* device_offsets,
+    const void* device_table, int64_t table_bytes, int64_t table_words, void* device_out,
+    int64_t out_bytes, void* stream) const {
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  DPF_RETURN_IF_ERROR(CheckLookupArgs(K, matches, hierarchy_level, device_offsets, device_table,
+                                      table_bytes, table_words, device_out, out_bytes));
+  const int W = static_cast<int>(table_words);
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  HIP_RETURN_IF_ERROR(dpf_hip_lookup_batch(
+      K, hierarchy_to_tree()[hierarchy_level], keys.num_levels(),
+      parameters()[hierarchy_level].log_domain_size(), keys.seed(), keys.party(), keys.cw_seed(),
+      keys.cw_left(), keys.cw_right(), &kl, &kr, &kv, &desc,
+      keys.value_correction(hierarchy_level), device_offsets, device_table, W,
+      static_cast<uint64_t*>(device_out), stream));
+  return K * W;
+}
+
+StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateLookupBatch(
+    const DeviceKeyBatch& keys, int hierarchy_level, Span<const uint64_t> offsets,
+    const void* device_table, int64_t table_bytes, int64_t table_words) const {
+  // The device call's checks first, with stand-ins for the two buffers this
+  // call makes itself: host errors touch no device.
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  alignas(8) static const uint64_t stand_in = 0;
+  DPF_RETURN_IF_ERROR(CheckLookupArgs(K, matches, hierarchy_level, &stand_in, device_table,
+                                      table_bytes, table_words, &stand_in,
+                                      std::numeric_limits<int64_t>::max()));
+  if (static_cast<int64_t>(offsets.size()) != K)
+    return InvalidArgumentError("`offsets` must hold one offset per key of the batch");
+  std::vector<uint64_t> out(static_cast<size_t>(K * table_words));
+  if (K == 0) return out;
+  dpf_internal::DeviceBuffer d_off, d_out;
+  DPF_RETURN_IF_ERROR(d_off.Upload(offsets.data(), offsets.size(), nullptr));
+  DPF_RETURN_IF_ERROR(d_out.Reserve(out.size() * sizeof(uint64_t)));
+  DPF_RETURN_IF_ERROR(EvaluateLookupBatchToDevice(keys, hierarchy_level, d_off.as<uint64_t>(),
+                                                  device_table, table_bytes, table_words,
+                                                  d_out.get(),
+                                                  static_cast<int64_t>(out.size() * 8), nullptr)
+                          .status());
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), d_out.get(), out.size() * 8, nullptr));
+  return out;
+}
+
 // Dense PIR: the streamed path of EvaluateDotToDevice with one bit per record
 // and up to 64 keys per pass over the database.  The shard is cut into slabs
 // of whole leaf blocks whose Q bit rows fit the dot call's scratch bound

@@ -497,6 +497,41 @@ class PyDpf {
       throw StatusError(st);
     }
   }
+  int64_t EvaluateLookupBatchToDevice(const PyDeviceKeyBatch& keys, int level, uintptr_t offsets,
+                                      uintptr_t table, int64_t table_bytes, int64_t table_words,
+                                      uintptr_t out, int64_t out_bytes, uintptr_t stream) {
+    return TakeNoGil([&] {
+      return dpf_->EvaluateLookupBatchToDevice(
+          *keys.d, level, reinterpret_cast<const uint64_t*>(offsets),
+          reinterpret_cast<const void*>(table), table_bytes, table_words,
+          reinterpret_cast<void*>(out), out_bytes, reinterpret_cast<void*>(stream));
+    });
+  }
+  py::array_t<uint64_t> EvaluateLookupBatch(const PyDeviceKeyBatch& keys, int level,
+                                            const U64Array& offsets, uintptr_t table,
+                                            int64_t table_bytes, int64_t table_words) {
+    const std::vector<uint64_t> off(offsets.data(), offsets.data() + offsets.size());
+    const std::vector<uint64_t> r = TakeNoGil([&] {
+      return dpf_->EvaluateLookupBatch(*keys.d, level, MakeConstSpan(off),
+                                       reinterpret_cast<const void*>(table), table_bytes,
+                                       table_words);
+    });
+    py::array_t<uint64_t> a(static_cast<py::ssize_t>(r.size()));
+    if (!r.empty()) std::memcpy(a.mutable_data(), r.data(), r.size() * 8);
+    return a;
+  }
+  bool EvaluatesLookupOnDevice(int level) const { return dpf_->EvaluatesLookupOnDevice(level); }
+  // The lookup call's host checks for a batch of `num_keys` keys (no device,
+  // no batch object needed).
+  void CheckLookupArgs(int64_t num_keys, bool batch_matches, int level, uintptr_t offsets,
+                       uintptr_t table, int64_t table_bytes, int64_t table_words, uintptr_t out,
+                       int64_t out_bytes) const {
+    Status st = dpf_->CheckLookupArgs(num_keys, batch_matches, level,
+                                      reinterpret_cast<const void*>(offsets),
+                                      reinterpret_cast<const void*>(table), table_bytes,
+                                      table_words, reinterpret_cast<const void*>(out), out_bytes);
+    if (!st.ok()) throw StatusError(st);
+  }
   PyBatchContext CreateBatchEvaluationContext(const PyDeviceKeyBatch& keys) {
     auto c = Take(dpf_->CreateBatchEvaluationContext(*keys.d));
     return PyBatchContext{keys.d, std::shared_ptr<DeviceBatchContext>(c.release())};
@@ -882,6 +917,10 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("generates_keys_on_device", &PyDpf::GeneratesKeysOnDevice)
       .def("evaluate_at_batch_to_device", &PyDpf::EvaluateAtBatchToDevice)
       .def("evaluate_at_batch_sum_to_device", &PyDpf::EvaluateAtBatchSumToDevice)
+      .def("evaluate_lookup_batch_to_device", &PyDpf::EvaluateLookupBatchToDevice)
+      .def("evaluate_lookup_batch", &PyDpf::EvaluateLookupBatch)
+      .def("evaluates_lookup_on_device", &PyDpf::EvaluatesLookupOnDevice)
+      .def("check_lookup_args", &PyDpf::CheckLookupArgs)
       .def("create_batch_evaluation_context", &PyDpf::CreateBatchEvaluationContext)
       .def("evaluate_until_batch_to_device", &PyDpf::EvaluateUntilBatchToDevice)
       .def("evaluate_until_batch_sketch_to_device", &PyDpf::EvaluateUntilBatchSketchToDevice)

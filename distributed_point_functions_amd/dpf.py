@@ -482,6 +482,51 @@ class DistributedPointFunction:
         _call(self._impl.evaluate_at_batch_sum_to_device, device_batch, int(hierarchy_level),
               points.data_ptr(), int(points.shape[0]), out.data_ptr(), s.cuda_stream)
 
+    def evaluate_lookup_batch_to_device(self, device_batch, hierarchy_level: int, offsets, table,
+                                        table_words: int, out, stream=None) -> int:
+        """Private table lookup for every key of a device batch: the key's
+        full-domain evaluation y_k (uint64 or XorWrapper<uint64>, 2^n elements)
+        folded into the shared public `table` (torch device tensor, 2^n rows
+        of `table_words` uint64, row-major) rotated by the key's public offset
+        s_k = offsets[k] mod 2^n (`offsets`: torch device tensor of K uint64 or
+        int64), without storing y_k:
+        out[k][w] = sum_i y_k[i] * T[(i + s_k) mod 2^n][w] mod 2^64, or
+        XOR_i (y_k[i] & T[...][w]).  Writes K * table_words uint64 into the
+        torch device tensor `out` and returns that count.  The two parties'
+        results add (XOR) to beta_k * T[(alpha_k + s_k) mod 2^n]."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(out.device)
+        return _call(self._impl.evaluate_lookup_batch_to_device, device_batch,
+                     int(hierarchy_level), offsets.data_ptr(), table.data_ptr(),
+                     table.numel() * table.element_size(), int(table_words), out.data_ptr(),
+                     out.numel() * out.element_size(), s.cuda_stream)
+
+    def evaluate_lookup_batch(self, device_batch, hierarchy_level: int, offsets, table,
+                              table_words: int) -> np.ndarray:
+        """evaluate_lookup_batch_to_device with host offsets, returned as a numpy
+        uint64 array of shape (K, table_words)."""
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        out = _call(self._impl.evaluate_lookup_batch, device_batch, int(hierarchy_level), off,
+                    table.data_ptr(), table.numel() * table.element_size(), int(table_words))
+        return out.reshape(-1, int(table_words))
+
+    def evaluates_lookup_on_device(self, hierarchy_level: int) -> bool:
+        """Whether evaluate_lookup_batch_to_device takes this level's value type
+        and domain size (there is no fallback behind it)."""
+        return self._impl.evaluates_lookup_on_device(int(hierarchy_level))
+
+    def check_lookup_args(self, num_keys: int, hierarchy_level: int, offsets, table,
+                          table_words: int, out, batch_matches: bool = True) -> None:
+        """The host checks of evaluate_lookup_batch_to_device for a batch of
+        `num_keys` keys, in its order; raises what it would raise.  Touches no
+        device and needs no batch."""
+        _call(self._impl.check_lookup_args, int(num_keys), bool(batch_matches),
+              int(hierarchy_level), offsets.data_ptr(), table.data_ptr(),
+              table.numel() * table.element_size(), int(table_words), out.data_ptr(),
+              out.numel() * out.element_size())
+
     # -- device-resident incremental evaluation of a key batch (8f.1, cfg 5b) --
     def create_batch_evaluation_context(self, device_batch):
         """EvaluationContext of every key of a device batch, kept on the GPU."""

@@ -152,6 +152,11 @@ def load(require_gpu: bool = False):
                              [I64, I, I, I64, P, P, P, P, P, I, P, P, P, P, P, P, P]),
                             ("dpf_hip_dcf_expand_plan",
                              [I64, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_lookup_supported", [P, I]),
+                            ("dpf_hip_lookup_batch",
+                             [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P]),
+                            ("dpf_hip_lookup_plan",
+                             [I64, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_prefix_batch_max_expand", [P, I]),
                             ("dpf_hip_prefix_batch_level", [ctypes.POINTER(PrefixBatchArgs), P])):
             if hasattr(L, name):
@@ -235,6 +240,21 @@ def dcf_expand_plan(num_keys: int, num_levels: int, shard_bits: int, compute_uni
     check(load().dpf_hip_dcf_expand_plan(num_keys, num_levels, shard_bits, compute_units, out))
     return {"G": out[0], "walk": out[1], "items": out[2], "items_per_key": out[3],
             "top_G": out[4], "top_items": out[5]}
+
+
+def lookup_plan(num_keys: int, tree_depth: int, table_words: int, compute_units: int) -> dict:
+    """The launch plan of dpf_hip_lookup_batch for that shape (no GPU needed):
+    {"S", "walk", "items_per_key", "items"}."""
+    out = (ctypes.c_int64 * 4)()
+    check(load().dpf_hip_lookup_plan(num_keys, tree_depth, table_words, compute_units, out))
+    return {"S": out[0], "walk": out[1], "items_per_key": out[2], "items": out[3]}
+
+
+def lookup_supported(desc, table_words: int) -> bool:
+    """Whether dpf_hip_lookup_batch takes this value type and table width
+    (`desc` None: a NULL descriptor; no GPU needed)."""
+    return bool(load().dpf_hip_lookup_supported(ctypes.byref(desc) if desc is not None else None,
+                                                table_words))
 
 
 def clock_probe(on: bool) -> None:

@@ -375,6 +375,49 @@ class DistributedPointFunction {
   Status EvaluateAtBatchSumToDevice(const DeviceKeyBatch& keys, int hierarchy_level,
                                     const void* device_points, int64_t num_points,
                                     void* device_out, void* stream) const;
+  // Private table lookup, batched over keys: the full-domain expansion of
+  // every key of a device batch folded into one shared public table at a
+  // public rotation per key, without a share vector being stored.  For T =
+  // uint64_t or XorWrapper<uint64_t> at `hierarchy_level` (other value types:
+  // UNIMPLEMENTED; there is no fallback behind this call), n =
+  // log_domain_size in [1, 40], N = 2^n, y_k = EvaluateUntil<T>(
+  // hierarchy_level, {}, fresh ctx of key k), `device_table` a row-major
+  // device array of N rows of `table_words` (W: 1, 2 or 4; others in
+  // [1, 1024] UNIMPLEMENTED) uint64 and s_k = device_offsets[k] mod N:
+  //   uint64_t:             out[k][w] = sum_i y_k[i] * T[(i + s_k) mod N][w]  (mod 2^64)
+  //   XorWrapper<uint64_t>: out[k][w] = XOR_i (y_k[i] & T[(i + s_k) mod N][w]);
+  // the two parties' results for key k combine with T's + to
+  // beta_k * T[(alpha_k + s_k) mod N][w] (beta_k & ...).  Stateless and
+  // key-based.  Writes K * W uint64 to `device_out` on `stream`
+  // (asynchronous), whatever it held before, and returns K * W.  Checked in
+  // this order, before the device is touched, the first failure reported:
+  // the level, the value type and its domain size, table_words, table_bytes
+  // == N * W * 8, null pointers, out_bytes >= K * W * 8, that the batch is
+  // this DPF's, and the buffers' alignment (the table to min(16, 8 W) bytes,
+  // offsets and output to 8).
+  StatusOr<int64_t> EvaluateLookupBatchToDevice(const DeviceKeyBatch& keys, int hierarchy_level,
+                                                const uint64_t* device_offsets,
+                                                const void* device_table, int64_t table_bytes,
+                                                int64_t table_words, void* device_out,
+                                                int64_t out_bytes, void* stream) const;
+  // The same with host offsets (keys.num_keys() of them) and the K * W sums
+  // returned to the host.
+  StatusOr<std::vector<uint64_t>> EvaluateLookupBatch(const DeviceKeyBatch& keys,
+                                                      int hierarchy_level,
+                                                      Span<const uint64_t> offsets,
+                                                      const void* device_table,
+                                                      int64_t table_bytes,
+                                                      int64_t table_words) const;
+  // True when `hierarchy_level` exists and its value type and domain size are
+  // ones EvaluateLookupBatchToDevice takes.
+  bool EvaluatesLookupOnDevice(int hierarchy_level) const;
+  // EvaluateLookupBatchToDevice's argument checks, in its order and with its
+  // messages, for a batch of num_keys keys that is (`batch_matches`) or is not
+  // one of this DistributedPointFunction.  Touches no device.
+  Status CheckLookupArgs(int64_t num_keys, bool batch_matches, int hierarchy_level,
+                         const void* device_offsets, const void* device_table,
+                         int64_t table_bytes, int64_t table_words, const void* device_out,
+                         int64_t out_bytes) const;
   // ---- device-resident incremental evaluation of a key batch (8f.1, cfg 5b)
   // A fresh context for every key of `keys` (previous_hierarchy_level -1), as
   // CreateEvaluationContext would make per key.  `keys` must outlive it.

@@ -668,6 +668,60 @@ int dpf_hip_dcf_expand(int64_t num_keys, int num_levels, int shard_bits, int64_t
 int dpf_hip_dcf_expand_plan(int64_t num_keys, int num_levels, int shard_bits, int num_cus,
                             int64_t out[6]);
 
+/* ---- batched private table lookup ------------------------------------------
+ * No reference counterpart.  The full-domain expansion of every key of a key
+ * batch, folded into one shared public table at a public rotation per key,
+ * without storing a share vector.  With n = log_domain_size, N = 2^n, y_k the
+ * N shares EvaluateUntil gives for key k, W = table_words and
+ * s_k = offsets[k] mod N (only the low n bits of an offset are read):
+ *   uint64_t:              out[k*W + w] = sum_{i<N} y_k[i] * T[(i + s_k) mod N][w]  (mod 2^64)
+ *   XorWrapper<uint64_t>:  out[k*W + w] = XOR_{i<N} (y_k[i] & T[(i + s_k) mod N][w])
+ * `table` is N rows of W uint64, row-major.  The two parties' outputs add
+ * (XOR) to beta_k * T[(alpha_k + s_k) mod N][w] (beta_k & ...).  The key batch
+ * is passed as dpf_hip_eval_points_batch takes it, with num_levels the
+ * hierarchy level's tree depth (n - 1 for these value types), cw_stride the
+ * key's correction-word count and value_correction that level's, two blocks
+ * per key.  The call is asynchronous on `stream`, overwrites out[0, K*W) and
+ * reads nothing of what it held before.
+ * Checks, all before any device call, the first failing one reported:
+ *   1. num_keys outside [0, 2^31 - 1], log_domain_size outside [1, 40],
+ *      num_levels != log_domain_size - 1: 3;
+ *   2. NULL desc or AES keys: 3;
+ *   3. a value type other than uint64_t / XorWrapper<uint64_t>: 12
+ *      UNIMPLEMENTED (there is no fallback behind this call);
+ *   4. table_words outside [1, 1024]: 3;   5. table_words not 1, 2 or 4: 12;
+ *   6. cw_stride < num_levels: 3;          7. num_keys == 0: returns 0, no launch;
+ *   8. NULL key arrays, offsets, table or out (correction words only when
+ *      num_levels > 0): 3;
+ *   9. `table` not aligned to min(16, 8 * table_words) bytes, `offsets` or
+ *      `out` not to 8: 3.
+ * The item loop is dynamic as chunked launches are (DPF_LOOKUP_DYNAMIC=0, read
+ * per launch: a fixed share per thread; A/B and test hook), and
+ * dpf_hip_last_dynamic_chunks reports it. */
+int dpf_hip_lookup_supported(const dpf_value_desc* desc, int table_words);
+int dpf_hip_lookup_batch(int64_t num_keys, int num_levels, int cw_stride, int log_domain_size,
+                         const dpf_block* key_seed, const uint8_t* party,
+                         const dpf_block* cw_seed, const uint8_t* cw_left,
+                         const uint8_t* cw_right, const dpf_aes_key* key_left,
+                         const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                         const dpf_value_desc* desc, const dpf_block* value_correction,
+                         const uint64_t* offsets, const void* table, int table_words,
+                         uint64_t* out, void* stream);
+/* The launch plan of dpf_hip_lookup_batch on a device of num_cus compute
+ * units, a pure function (no device is touched).  A work item is (key,
+ * subtree): it walks `walk` levels from the key's root and visits S levels
+ * depth-first, tree_depth = walk + S.  out = {S, walk, items per key = 2^walk,
+ * items}.  S is the deepest the kernel's register stack allows for the table
+ * width (5 levels for table_words 1 and 2, 4 for 4), lowered while the launch
+ * has fewer than 256 items per compute unit.  A key costs
+ * 2^walk * (walk + 2 (2^S - 1) + 2^S) AES.  Items per key below 64: several
+ * keys per wave, summed by a segmented cross-lane reduction; 64: one wave per
+ * key; above: the waves of a key meet by 64-bit atomics on `out`, which the
+ * call clears first in stream order.  3 for num_keys outside [1, 2^31 - 1],
+ * tree_depth outside [0, 39], table_words not 1, 2 or 4, num_cus < 1. */
+int dpf_hip_lookup_plan(int64_t num_keys, int tree_depth, int table_words, int num_cus,
+                        int64_t out[4]);
+
 /* ---- batched multiple-interval-containment gate (eprint 2020/1392 Fig. 14) -
  * MultipleIntervalContainmentGate::Eval (dcf/fss_gates/
  * multiple_interval_containment.cc:206-275) for num_gates gates over
