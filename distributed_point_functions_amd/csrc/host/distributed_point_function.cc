@@ -1125,6 +1125,86 @@ StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateLookupBatch(
   return out;
 }
 
+// Full-domain sum over a key batch: a table kernel and one fused launch
+// (dpf_expand_sum.hip).  The host's part is the argument checks, in the order
+// the header gives, and the table's room in the device scratch.
+bool DistributedPointFunction::EvaluatesFullDomainSumOnDevice(int hierarchy_level) const {
+  if (!CheckLevel(hierarchy_level, parameters().size()).ok()) return false;
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  return dpf_hip_expand_sum_supported(&desc) != 0 && n >= 1 && n <= 30;
+}
+
+Status DistributedPointFunction::CheckFullDomainSumArgs(int64_t num_keys, bool batch_matches,
+                                                        int hierarchy_level,
+                                                        const void* device_out,
+                                                        int64_t out_bytes) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  if (!dpf_hip_expand_sum_supported(&desc))
+    return UnimplementedError(
+        "the full-domain sum is implemented for uint64_t and XorWrapper<uint64_t> only");
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  if (n < 1 || n > 30)
+    return InvalidArgumentError("the full-domain sum takes a log_domain_size in [1, 30]");
+  if (!device_out) return InvalidArgumentError("`device_out` must not be null");
+  if (num_keys < 0 || out_bytes < (int64_t{1} << n) * 8)
+    return InvalidArgumentError("device output buffer too small");
+  if (!batch_matches)
+    return InvalidArgumentError("key batch does not match this DistributedPointFunction");
+  if ((reinterpret_cast<uintptr_t>(device_out) & 15) != 0)
+    return InvalidArgumentError("`device_out` must be aligned to 16 bytes");
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateFullDomainSumToDevice(
+    const DeviceKeyBatch& keys, int hierarchy_level, void* device_out, int64_t out_bytes,
+    bool accumulate, void* stream) const {
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  DPF_RETURN_IF_ERROR(CheckFullDomainSumArgs(K, matches, hierarchy_level, device_out, out_bytes));
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  const int depth = hierarchy_to_tree()[hierarchy_level];
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  const int64_t workspace_bytes = dpf_hip_expand_sum_workspace_bytes(K, depth);
+  if (workspace_bytes < 0) return InvalidArgumentError("key batch too large for the full-domain sum");
+  if (K > 0)
+    DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace,
+                                                   static_cast<size_t>(workspace_bytes), stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_expand_sum(
+      K, depth, keys.num_levels(), n, keys.seed(), keys.party(), keys.cw_seed(), keys.cw_left(),
+      keys.cw_right(), &kl, &kr, &kv, &desc, keys.value_correction(hierarchy_level),
+      K > 0 ? s->workspace.get() : nullptr, workspace_bytes, static_cast<uint64_t*>(device_out),
+      accumulate ? 1 : 0, stream));
+  if (K > 0) DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  return int64_t{1} << n;
+}
+
+StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateFullDomainSum(
+    const DeviceKeyBatch& keys, int hierarchy_level) const {
+  // The device call's checks first, with a stand-in for the buffer this call
+  // makes itself: host errors touch no device.
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  alignas(16) static const uint64_t stand_in[2] = {0, 0};
+  DPF_RETURN_IF_ERROR(CheckFullDomainSumArgs(keys.num_keys(), matches, hierarchy_level, stand_in,
+                                             std::numeric_limits<int64_t>::max()));
+  const size_t N = size_t{1} << parameters()[hierarchy_level].log_domain_size();
+  std::vector<uint64_t> out(N);
+  if (keys.num_keys() == 0) return out;   // the empty sum
+  dpf_internal::DeviceBuffer d_out;
+  DPF_RETURN_IF_ERROR(d_out.Reserve(N * sizeof(uint64_t)));
+  DPF_RETURN_IF_ERROR(EvaluateFullDomainSumToDevice(keys, hierarchy_level, d_out.get(),
+                                                    static_cast<int64_t>(N * 8), false, nullptr)
+                          .status());
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), d_out.get(), N * 8, nullptr));
+  return out;
+}
+
 // Dense PIR: the streamed path of EvaluateDotToDevice with one bit per record
 // and up to 64 keys per pass over the database.  The shard is cut into slabs
 // of whole leaf blocks whose Q bit rows fit the dot call's scratch bound

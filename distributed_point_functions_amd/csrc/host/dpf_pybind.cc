@@ -532,6 +532,32 @@ class PyDpf {
                                       table_words, reinterpret_cast<const void*>(out), out_bytes);
     if (!st.ok()) throw StatusError(st);
   }
+  int64_t EvaluateFullDomainSumToDevice(const PyDeviceKeyBatch& keys, int level, uintptr_t out,
+                                        int64_t out_bytes, bool accumulate, uintptr_t stream) {
+    return TakeNoGil([&] {
+      return dpf_->EvaluateFullDomainSumToDevice(*keys.d, level, reinterpret_cast<void*>(out),
+                                                 out_bytes, accumulate,
+                                                 reinterpret_cast<void*>(stream));
+    });
+  }
+  py::array_t<uint64_t> EvaluateFullDomainSum(const PyDeviceKeyBatch& keys, int level) {
+    const std::vector<uint64_t> r =
+        TakeNoGil([&] { return dpf_->EvaluateFullDomainSum(*keys.d, level); });
+    py::array_t<uint64_t> a(static_cast<py::ssize_t>(r.size()));
+    if (!r.empty()) std::memcpy(a.mutable_data(), r.data(), r.size() * 8);
+    return a;
+  }
+  bool EvaluatesFullDomainSumOnDevice(int level) const {
+    return dpf_->EvaluatesFullDomainSumOnDevice(level);
+  }
+  // The full-domain sum's host checks for a batch of `num_keys` keys (no
+  // device, no batch object needed).
+  void CheckFullDomainSumArgs(int64_t num_keys, bool batch_matches, int level, uintptr_t out,
+                              int64_t out_bytes) const {
+    Status st = dpf_->CheckFullDomainSumArgs(num_keys, batch_matches, level,
+                                             reinterpret_cast<const void*>(out), out_bytes);
+    if (!st.ok()) throw StatusError(st);
+  }
   PyBatchContext CreateBatchEvaluationContext(const PyDeviceKeyBatch& keys) {
     auto c = Take(dpf_->CreateBatchEvaluationContext(*keys.d));
     return PyBatchContext{keys.d, std::shared_ptr<DeviceBatchContext>(c.release())};
@@ -921,6 +947,10 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_lookup_batch", &PyDpf::EvaluateLookupBatch)
       .def("evaluates_lookup_on_device", &PyDpf::EvaluatesLookupOnDevice)
       .def("check_lookup_args", &PyDpf::CheckLookupArgs)
+      .def("evaluate_full_domain_sum_to_device", &PyDpf::EvaluateFullDomainSumToDevice)
+      .def("evaluate_full_domain_sum", &PyDpf::EvaluateFullDomainSum)
+      .def("evaluates_full_domain_sum_on_device", &PyDpf::EvaluatesFullDomainSumOnDevice)
+      .def("check_full_domain_sum_args", &PyDpf::CheckFullDomainSumArgs)
       .def("create_batch_evaluation_context", &PyDpf::CreateBatchEvaluationContext)
       .def("evaluate_until_batch_to_device", &PyDpf::EvaluateUntilBatchToDevice)
       .def("evaluate_until_batch_sketch_to_device", &PyDpf::EvaluateUntilBatchSketchToDevice)

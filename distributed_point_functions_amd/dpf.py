@@ -527,6 +527,41 @@ class DistributedPointFunction:
               table.numel() * table.element_size(), int(table_words), out.data_ptr(),
               out.numel() * out.element_size())
 
+    def evaluate_full_domain_sum_to_device(self, device_batch, hierarchy_level: int, out,
+                                           accumulate: bool = False, stream=None) -> int:
+        """Private histogram of a device batch: every key's full-domain
+        evaluation y_k (uint64 or XorWrapper<uint64>, N = 2^n elements, n <= 30)
+        summed element by element without storing y_k,
+        out[i] = sum_k y_k[i] mod 2^64, or XOR_k y_k[i].  `out`: a torch device
+        tensor of at least N 64-bit words, 16-byte aligned; overwritten, or with
+        `accumulate` added (XORed) into.  Returns N.  The two parties' vectors
+        add (XOR) to sum_k beta_k * e_{alpha_k}."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(out.device)
+        return _call(self._impl.evaluate_full_domain_sum_to_device, device_batch,
+                     int(hierarchy_level), out.data_ptr(), out.numel() * out.element_size(),
+                     bool(accumulate), s.cuda_stream)
+
+    def evaluate_full_domain_sum(self, device_batch, hierarchy_level: int) -> np.ndarray:
+        """evaluate_full_domain_sum_to_device into a fresh vector, returned as a
+        numpy uint64 array of N sums."""
+        return _call(self._impl.evaluate_full_domain_sum, device_batch, int(hierarchy_level))
+
+    def evaluates_full_domain_sum_on_device(self, hierarchy_level: int) -> bool:
+        """Whether evaluate_full_domain_sum_to_device takes this level's value
+        type and domain size (there is no fallback behind it)."""
+        return self._impl.evaluates_full_domain_sum_on_device(int(hierarchy_level))
+
+    def check_full_domain_sum_args(self, num_keys: int, hierarchy_level: int, out,
+                                   batch_matches: bool = True) -> None:
+        """The host checks of evaluate_full_domain_sum_to_device for a batch of
+        `num_keys` keys, in its order; raises what it would raise.  Touches no
+        device and needs no batch."""
+        _call(self._impl.check_full_domain_sum_args, int(num_keys), bool(batch_matches),
+              int(hierarchy_level), out.data_ptr(), out.numel() * out.element_size())
+
     # -- device-resident incremental evaluation of a key batch (8f.1, cfg 5b) --
     def create_batch_evaluation_context(self, device_batch):
         """EvaluationContext of every key of a device batch, kept on the GPU."""

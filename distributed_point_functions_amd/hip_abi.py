@@ -82,7 +82,7 @@ def prefix_batch_args(**members) -> PrefixBatchArgs:
 def header_functions() -> list:
     """Names of every function the C ABI header declares."""
     txt = open(HEADER).read()
-    return sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(dpf_hip_\w+)\s*\(", txt, re.M)))
+    return sorted(set(re.findall(r"^\s*(?:int|int64_t|const char\*)\s+(dpf_hip_\w+)\s*\(", txt, re.M)))
 
 
 def load(require_gpu: bool = False):
@@ -157,10 +157,18 @@ def load(require_gpu: bool = False):
                              [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P]),
                             ("dpf_hip_lookup_plan",
                              [I64, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_expand_sum_supported", [P]),
+                            ("dpf_hip_expand_sum",
+                             [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I64, P, I, P]),
+                            ("dpf_hip_expand_sum_plan",
+                             [I64, I, I, ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_prefix_batch_max_expand", [P, I]),
                             ("dpf_hip_prefix_batch_level", [ctypes.POINTER(PrefixBatchArgs), P])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = types
+        if hasattr(L, "dpf_hip_expand_sum_workspace_bytes"):
+            L.dpf_hip_expand_sum_workspace_bytes.argtypes = [I64, I]
+            L.dpf_hip_expand_sum_workspace_bytes.restype = ctypes.c_int64
         if hasattr(L, "dpf_hip_last_dot_kernel"):
             L.dpf_hip_last_dot_kernel.restype = ctypes.c_char_p
         _lib = L
@@ -255,6 +263,31 @@ def lookup_supported(desc, table_words: int) -> bool:
     (`desc` None: a NULL descriptor; no GPU needed)."""
     return bool(load().dpf_hip_lookup_supported(ctypes.byref(desc) if desc is not None else None,
                                                 table_words))
+
+
+EXPAND_SUM_WAVE_ITEMS_PER_CU = 64   # DPF_HIP_EXPAND_SUM_WAVE_ITEMS_PER_CU
+
+
+def expand_sum_plan(num_keys: int, tree_depth: int, compute_units: int) -> dict:
+    """The launch plan of dpf_hip_expand_sum for that shape (no GPU needed):
+    {"S", "walk", "subtrees", "wave_items", "group", "threshold"}."""
+    out = (ctypes.c_int64 * 6)()
+    check(load().dpf_hip_expand_sum_plan(num_keys, tree_depth, compute_units, out))
+    return {"S": out[0], "walk": out[1], "subtrees": out[2], "wave_items": out[3],
+            "group": out[4], "threshold": out[5]}
+
+
+def expand_sum_supported(desc) -> bool:
+    """Whether dpf_hip_expand_sum takes this value type (`desc` None: a NULL
+    descriptor; no GPU needed)."""
+    return bool(load().dpf_hip_expand_sum_supported(
+        ctypes.byref(desc) if desc is not None else None))
+
+
+def expand_sum_workspace_bytes(num_keys: int, num_levels: int) -> int:
+    """Bytes of dpf_hip_expand_sum's workspace for that batch (no GPU needed);
+    -1 for arguments out of range."""
+    return int(load().dpf_hip_expand_sum_workspace_bytes(num_keys, num_levels))
 
 
 def clock_probe(on: bool) -> None:

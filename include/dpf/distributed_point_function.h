@@ -418,6 +418,40 @@ class DistributedPointFunction {
                          const void* device_offsets, const void* device_table,
                          int64_t table_bytes, int64_t table_words, const void* device_out,
                          int64_t out_bytes) const;
+  // Fused full-domain sum over a key batch -- private histograms, private
+  // writes: every key of a device batch expanded over its whole domain and
+  // summed element by element, without a share vector being stored.  For T =
+  // uint64_t or XorWrapper<uint64_t> at `hierarchy_level` (other value types:
+  // UNIMPLEMENTED; there is no fallback behind this call), n =
+  // log_domain_size in [1, 30], N = 2^n and y_k = EvaluateUntil<T>(
+  // hierarchy_level, {}, fresh ctx of key k):
+  //   uint64_t:             out[i] = sum_k y_k[i]  (mod 2^64)
+  //   XorWrapper<uint64_t>: out[i] = XOR_k y_k[i]           for i in [0, N);
+  // the two parties' vectors combine to sum_k beta_k * e_{alpha_k}.  Stateless
+  // and key-based.  With `accumulate` false, out[0, N) is overwritten and
+  // nothing of what it held is read; with true, the sums are added (XORed)
+  // into what it holds, so that several batches stream into one accumulator.
+  // An empty batch launches nothing: it writes N zeros, or with `accumulate`
+  // leaves the output untouched.  Works on `stream` (asynchronous) and returns
+  // N.  The call's table of correction words lives in this object's device
+  // scratch (ReleaseScratch frees it).  Checked in this order, before the
+  // device is touched, the first failure reported: the level, the value type
+  // and its domain size, a null pointer, out_bytes >= N * 8, that the batch
+  // is this DPF's, and the output's alignment to 16 bytes.
+  StatusOr<int64_t> EvaluateFullDomainSumToDevice(const DeviceKeyBatch& keys, int hierarchy_level,
+                                                  void* device_out, int64_t out_bytes,
+                                                  bool accumulate, void* stream) const;
+  // The same into a fresh vector of N sums returned to the host.
+  StatusOr<std::vector<uint64_t>> EvaluateFullDomainSum(const DeviceKeyBatch& keys,
+                                                        int hierarchy_level) const;
+  // True when `hierarchy_level` exists and its value type and domain size are
+  // ones EvaluateFullDomainSumToDevice takes.
+  bool EvaluatesFullDomainSumOnDevice(int hierarchy_level) const;
+  // EvaluateFullDomainSumToDevice's argument checks, in its order and with its
+  // messages, for a batch of num_keys keys that is (`batch_matches`) or is not
+  // one of this DistributedPointFunction.  Touches no device.
+  Status CheckFullDomainSumArgs(int64_t num_keys, bool batch_matches, int hierarchy_level,
+                                const void* device_out, int64_t out_bytes) const;
   // ---- device-resident incremental evaluation of a key batch (8f.1, cfg 5b)
   // A fresh context for every key of `keys` (previous_hierarchy_level -1), as
   // CreateEvaluationContext would make per key.  `keys` must outlive it.

@@ -722,6 +722,67 @@ int dpf_hip_lookup_batch(int64_t num_keys, int num_levels, int cw_stride, int lo
 int dpf_hip_lookup_plan(int64_t num_keys, int tree_depth, int table_words, int num_cus,
                         int64_t out[4]);
 
+/* ---- fused full-domain sum over a key batch: private histograms -------------
+ * No reference counterpart.  The full-domain expansion of every key of a key
+ * batch summed element by element, without storing a share vector.  With n =
+ * log_domain_size, N = 2^n and y_k the N shares EvaluateUntil gives for key k:
+ *   uint64_t:              out[i] = sum_{k<K} y_k[i]  (mod 2^64)
+ *   XorWrapper<uint64_t>:  out[i] = XOR_{k<K} y_k[i]          for i in [0, N)
+ * The two parties' vectors combine to the histogram sum_k beta_k * e_{alpha_k}.
+ * The key batch is passed as dpf_hip_lookup_batch takes it (num_levels the
+ * hierarchy level's tree depth n - 1, cw_stride the key's correction-word
+ * count, value_correction that level's, two blocks per key).  `workspace` is
+ * device memory of at least dpf_hip_expand_sum_workspace_bytes(num_keys,
+ * num_levels) bytes that the call fills with its [level][key] table of
+ * correction words; it must stay untouched until the call's work on `stream`
+ * is done.  accumulate == 0: out[0, N) is overwritten and nothing of what it
+ * held is read; otherwise the sums are added (XORed) into what it holds.  The
+ * call is asynchronous on `stream`.
+ * Checks, all before any device call, the first failing one reported:
+ *   1. num_keys outside [0, 2^31 - 1], log_domain_size outside [1, 30],
+ *      num_levels != log_domain_size - 1: 3;
+ *   2. NULL desc or AES keys: 3;
+ *   3. a value type other than uint64_t / XorWrapper<uint64_t>: 12
+ *      UNIMPLEMENTED (there is no fallback behind this call);
+ *   4. cw_stride < num_levels: 3;          5. NULL out: 3;
+ *   6. num_keys == 0: clears out[0, N) unless accumulating, returns 0, no
+ *      kernel is launched;
+ *   7. NULL key arrays (correction words only when num_levels > 0): 3;
+ *   8. NULL workspace or workspace_bytes too small: 8, the message names the
+ *      size needed;
+ *   9. `out` or `workspace` not aligned to 16 bytes: 3.
+ * The item loop is dynamic as chunked launches are (DPF_EXPAND_SUM_DYNAMIC=0,
+ * read per launch: a fixed share per wave; A/B and test hook), and
+ * dpf_hip_last_dynamic_chunks reports it. */
+#define DPF_HIP_EXPAND_SUM_WAVE_ITEMS_PER_CU 64
+int dpf_hip_expand_sum_supported(const dpf_value_desc* desc);
+/* Bytes of the call's table: 20 * (num_levels + 1) per key, the keys rounded
+ * up to a multiple of 64.  Monotone in both arguments; -1 for num_keys outside
+ * [0, 2^31 - 1] or num_levels outside [0, 29].  No device is touched. */
+int64_t dpf_hip_expand_sum_workspace_bytes(int64_t num_keys, int num_levels);
+int dpf_hip_expand_sum(int64_t num_keys, int num_levels, int cw_stride, int log_domain_size,
+                       const dpf_block* key_seed, const uint8_t* party,
+                       const dpf_block* cw_seed, const uint8_t* cw_left,
+                       const uint8_t* cw_right, const dpf_aes_key* key_left,
+                       const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                       const dpf_value_desc* desc, const dpf_block* value_correction,
+                       void* workspace, int64_t workspace_bytes, uint64_t* out, int accumulate,
+                       void* stream);
+/* The launch plan of dpf_hip_expand_sum on a device of num_cus compute units,
+ * a pure function (no device is touched).  A wave item is (key chunk of 64
+ * consecutive keys, subtree): the wave walks `walk` levels from its keys'
+ * roots and visits S levels depth-first, tree_depth = walk + S, finishing the
+ * subtree as leaf groups of `group` levels (pairs: 1).  out = {S, walk,
+ * subtrees per chunk = 2^walk, wave items = ceil(K / 64) * 2^walk, group,
+ * threshold}.  walk is the smallest value with wave items >= threshold =
+ * DPF_HIP_EXPAND_SUM_WAVE_ITEMS_PER_CU * num_cus (what the dynamic item loop
+ * needs), but at most tree_depth - group.  Small case: tree_depth 0 (n = 1:
+ * the root is value-hashed, below a leaf group's depth) is group = S = walk =
+ * 0, one wave item per chunk.  A key costs 2^walk * (walk + 2 (2^S - 1)
+ * + 2^S) AES.  3 for num_keys outside [1, 2^31 - 1], tree_depth outside
+ * [0, 29], num_cus outside [1, 65536]. */
+int dpf_hip_expand_sum_plan(int64_t num_keys, int tree_depth, int num_cus, int64_t out[6]);
+
 /* ---- batched multiple-interval-containment gate (eprint 2020/1392 Fig. 14) -
  * MultipleIntervalContainmentGate::Eval (dcf/fss_gates/
  * multiple_interval_containment.cc:206-275) for num_gates gates over
