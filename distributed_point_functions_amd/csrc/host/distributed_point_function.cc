@@ -1205,6 +1205,124 @@ StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateFullDomainSum(
   return out;
 }
 
+// Checked private histograms: the field sum of a key batch's full domain with
+// every key's sketches, one fused launch between a table and a finish kernel
+// (dpf_expand_sketch.hip).  The host's part is the argument checks, in the
+// order the header gives, and the workspace's room in the device scratch.
+bool DistributedPointFunction::EvaluatesFullDomainSumSketchOnDevice(int hierarchy_level) const {
+  if (!CheckLevel(hierarchy_level, parameters().size()).ok()) return false;
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  return dpf_hip_expand_sketch_supported(&desc) != 0 && n >= 1 &&
+         n <= DPF_HIP_EXPAND_SKETCH_MAX_LOG_DOMAIN;
+}
+
+Status DistributedPointFunction::CheckFullDomainSumSketchArgs(
+    int64_t num_keys, bool batch_matches, int hierarchy_level, const void* device_weights,
+    int num_weight_rows, const void* device_sum, int64_t sum_bytes, const void* device_sketch,
+    int64_t sketch_bytes) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  if (!dpf_hip_expand_sketch_supported(&desc))
+    return UnimplementedError(
+        "the checked full-domain sum is implemented for IntModN<uint32_t, N> and 2-tuples of "
+        "it only");
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  if (n < 1 || n > DPF_HIP_EXPAND_SKETCH_MAX_LOG_DOMAIN)
+    return InvalidArgumentError("the checked full-domain sum takes a log_domain_size in [1, 28]");
+  const int64_t J = num_weight_rows, nl = desc.num_leaves;
+  if (J < 0 || J > 2) return InvalidArgumentError("`num_weight_rows` must be in [0, 2]");
+  if (!device_sum) return InvalidArgumentError("`device_sum` must not be null");
+  if (J > 0 && (!device_weights || (!device_sketch && num_keys > 0)))
+    return InvalidArgumentError(
+        "`device_weights` and `device_sketch` must not be null when num_weight_rows > 0");
+  if (sum_bytes < (int64_t{1} << n) * nl * 4)
+    return InvalidArgumentError("device sum buffer too small");
+  if (num_keys < 0 || (J > 0 && sketch_bytes / (J * nl * 4) < num_keys))
+    return InvalidArgumentError("device sketch buffer too small");
+  if (!batch_matches)
+    return InvalidArgumentError("key batch does not match this DistributedPointFunction");
+  if ((reinterpret_cast<uintptr_t>(device_sum) & 15) != 0 ||
+      (J > 0 && ((reinterpret_cast<uintptr_t>(device_weights) & 3) != 0 ||
+                 (reinterpret_cast<uintptr_t>(device_sketch) & 3) != 0)))
+    return InvalidArgumentError(
+        "`device_sum` must be aligned to 16 bytes, `device_weights` and `device_sketch` to 4");
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateFullDomainSumSketchToDevice(
+    int hierarchy_level, const DeviceKeyBatch& keys, const uint32_t* device_weights,
+    int num_weight_rows, void* device_sum, int64_t sum_bytes, void* device_sketch,
+    int64_t sketch_bytes, bool accumulate, void* stream) const {
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  DPF_RETURN_IF_ERROR(CheckFullDomainSumSketchArgs(K, matches, hierarchy_level, device_weights,
+                                                   num_weight_rows, device_sum, sum_bytes,
+                                                   device_sketch, sketch_bytes));
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  const int depth = hierarchy_to_tree()[hierarchy_level];
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  const int64_t workspace_bytes =
+      dpf_hip_expand_sketch_workspace_bytes(K, depth, n, desc.num_leaves, num_weight_rows);
+  if (workspace_bytes < 0)
+    return InvalidArgumentError("key batch too large for the checked full-domain sum");
+  if (K > 0)
+    DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace,
+                                                   static_cast<size_t>(workspace_bytes), stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_expand_sketch(
+      K, depth, keys.num_levels(), n, keys.seed(), keys.party(), keys.cw_seed(), keys.cw_left(),
+      keys.cw_right(), &kl, &kr, &kv, &desc, keys.value_correction(hierarchy_level),
+      num_weight_rows, device_weights, K > 0 ? s->workspace.get() : nullptr, workspace_bytes,
+      static_cast<uint32_t*>(device_sum), static_cast<uint32_t*>(device_sketch),
+      accumulate ? 1 : 0, stream));
+  if (K > 0) DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  return int64_t{1} << n;
+}
+
+StatusOr<DistributedPointFunction::SumSketch> DistributedPointFunction::EvaluateFullDomainSumSketch(
+    int hierarchy_level, const DeviceKeyBatch& keys, Span<const uint32_t> weights,
+    int num_weight_rows) const {
+  // The device call's checks first, with stand-ins for the buffers this call
+  // makes itself: host errors touch no device.
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  alignas(16) static const uint32_t stand_in[4] = {0, 0, 0, 0};
+  DPF_RETURN_IF_ERROR(CheckFullDomainSumSketchArgs(
+      K, matches, hierarchy_level, stand_in, num_weight_rows, stand_in,
+      std::numeric_limits<int64_t>::max(), stand_in, std::numeric_limits<int64_t>::max()));
+  const size_t N = size_t{1} << parameters()[hierarchy_level].log_domain_size();
+  const size_t J = static_cast<size_t>(num_weight_rows);
+  const size_t nl = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]).num_leaves;
+  if (weights.size() != J * N)
+    return InvalidArgumentError("`weights` must hold num_weight_rows rows of 2^log_domain_size");
+  SumSketch out;
+  out.sum.assign(N * nl, 0);
+  out.sketch.assign(static_cast<size_t>(K) * J * nl, 0);
+  if (K == 0) return out;   // the empty sum
+  dpf_internal::DeviceBuffer d_w, d_sum, d_sk;
+  if (J > 0) {
+    DPF_RETURN_IF_ERROR(d_w.Upload(weights.data(), weights.size(), nullptr));
+    DPF_RETURN_IF_ERROR(d_sk.Reserve(out.sketch.size() * 4));
+  }
+  DPF_RETURN_IF_ERROR(d_sum.Reserve(out.sum.size() * 4));
+  DPF_RETURN_IF_ERROR(EvaluateFullDomainSumSketchToDevice(
+                          hierarchy_level, keys, J > 0 ? d_w.as<uint32_t>() : nullptr,
+                          num_weight_rows, d_sum.get(), static_cast<int64_t>(out.sum.size() * 4),
+                          J > 0 ? d_sk.get() : nullptr,
+                          static_cast<int64_t>(out.sketch.size() * 4), false, nullptr)
+                          .status());
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.sum.data(), d_sum.get(), out.sum.size() * 4, nullptr));
+  if (J > 0)
+    HIP_RETURN_IF_ERROR(
+        dpf_hip_memcpy_d2h(out.sketch.data(), d_sk.get(), out.sketch.size() * 4, nullptr));
+  return out;
+}
+
 // Dense PIR: the streamed path of EvaluateDotToDevice with one bit per record
 // and up to 64 keys per pass over the database.  The shard is cut into slabs
 // of whole leaf blocks whose Q bit rows fit the dot call's scratch bound

@@ -558,6 +558,47 @@ class PyDpf {
                                              reinterpret_cast<const void*>(out), out_bytes);
     if (!st.ok()) throw StatusError(st);
   }
+  int64_t EvaluateFullDomainSumSketchToDevice(int level, const PyDeviceKeyBatch& keys,
+                                              uintptr_t weights, int num_weight_rows,
+                                              uintptr_t sum, int64_t sum_bytes, uintptr_t sketch,
+                                              int64_t sketch_bytes, bool accumulate,
+                                              uintptr_t stream) {
+    return TakeNoGil([&] {
+      return dpf_->EvaluateFullDomainSumSketchToDevice(
+          level, *keys.d, reinterpret_cast<const uint32_t*>(weights), num_weight_rows,
+          reinterpret_cast<void*>(sum), sum_bytes, reinterpret_cast<void*>(sketch), sketch_bytes,
+          accumulate, reinterpret_cast<void*>(stream));
+    });
+  }
+  // (sums uint32 [N * nl], sketches uint32 [K * J * nl]); weights: J rows of N.
+  py::tuple EvaluateFullDomainSumSketch(
+      int level, const PyDeviceKeyBatch& keys,
+      py::array_t<uint32_t, py::array::c_style | py::array::forcecast> weights,
+      int num_weight_rows) {
+    const Span<const uint32_t> w(weights.data(), static_cast<size_t>(weights.size()));
+    const DistributedPointFunction::SumSketch r = TakeNoGil(
+        [&] { return dpf_->EvaluateFullDomainSumSketch(level, *keys.d, w, num_weight_rows); });
+    py::array_t<uint32_t> a(static_cast<py::ssize_t>(r.sum.size()));
+    py::array_t<uint32_t> b(static_cast<py::ssize_t>(r.sketch.size()));
+    if (!r.sum.empty()) std::memcpy(a.mutable_data(), r.sum.data(), r.sum.size() * 4);
+    if (!r.sketch.empty()) std::memcpy(b.mutable_data(), r.sketch.data(), r.sketch.size() * 4);
+    return py::make_tuple(a, b);
+  }
+  bool EvaluatesFullDomainSumSketchOnDevice(int level) const {
+    return dpf_->EvaluatesFullDomainSumSketchOnDevice(level);
+  }
+  // The checked full-domain sum's host checks for a batch of `num_keys` keys
+  // (no device, no batch object needed).
+  void CheckFullDomainSumSketchArgs(int64_t num_keys, bool batch_matches, int level,
+                                    uintptr_t weights, int num_weight_rows, uintptr_t sum,
+                                    int64_t sum_bytes, uintptr_t sketch,
+                                    int64_t sketch_bytes) const {
+    Status st = dpf_->CheckFullDomainSumSketchArgs(
+        num_keys, batch_matches, level, reinterpret_cast<const void*>(weights), num_weight_rows,
+        reinterpret_cast<const void*>(sum), sum_bytes, reinterpret_cast<const void*>(sketch),
+        sketch_bytes);
+    if (!st.ok()) throw StatusError(st);
+  }
   PyBatchContext CreateBatchEvaluationContext(const PyDeviceKeyBatch& keys) {
     auto c = Take(dpf_->CreateBatchEvaluationContext(*keys.d));
     return PyBatchContext{keys.d, std::shared_ptr<DeviceBatchContext>(c.release())};
@@ -951,6 +992,12 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_full_domain_sum", &PyDpf::EvaluateFullDomainSum)
       .def("evaluates_full_domain_sum_on_device", &PyDpf::EvaluatesFullDomainSumOnDevice)
       .def("check_full_domain_sum_args", &PyDpf::CheckFullDomainSumArgs)
+      .def("evaluate_full_domain_sum_sketch_to_device",
+           &PyDpf::EvaluateFullDomainSumSketchToDevice)
+      .def("evaluate_full_domain_sum_sketch", &PyDpf::EvaluateFullDomainSumSketch)
+      .def("evaluates_full_domain_sum_sketch_on_device",
+           &PyDpf::EvaluatesFullDomainSumSketchOnDevice)
+      .def("check_full_domain_sum_sketch_args", &PyDpf::CheckFullDomainSumSketchArgs)
       .def("create_batch_evaluation_context", &PyDpf::CreateBatchEvaluationContext)
       .def("evaluate_until_batch_to_device", &PyDpf::EvaluateUntilBatchToDevice)
       .def("evaluate_until_batch_sketch_to_device", &PyDpf::EvaluateUntilBatchSketchToDevice)

@@ -562,6 +562,59 @@ class DistributedPointFunction:
         _call(self._impl.check_full_domain_sum_args, int(num_keys), bool(batch_matches),
               int(hierarchy_level), out.data_ptr(), out.numel() * out.element_size())
 
+    def evaluate_full_domain_sum_sketch_to_device(self, hierarchy_level: int, device_batch,
+                                                  weights, sum_out, sketch_out=None,
+                                                  accumulate: bool = False, stream=None) -> int:
+        """Checked private histogram of a device batch over a field
+        (IntModN<uint32, N_0> or a 2-tuple of such, nl leaves, N = 2^n elements,
+        n <= 28): sum_out[i][e] = sum_k y_k[i][e] mod N_e and, for the J <= 2 rows
+        of `weights` (torch device tensor, J x N 32-bit words, or None for J = 0),
+        sketch_out[k][j][e] = sum_i (w[j][i] mod N_e) * y_k[i][e] mod N_e, in
+        one launch that stores no y_k.  `sum_out`: at least N * nl 32-bit words,
+        16-byte aligned; overwritten, or with `accumulate` added into mod N_e
+        (its entries must be below N_e).  `sketch_out`: at least K * J * nl
+        words, always overwritten.  Returns N."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(sum_out.device)
+        J = 0 if weights is None else int(weights.shape[0]) if weights.dim() > 1 else 1
+        nbytes = lambda t: 0 if t is None else t.numel() * t.element_size()
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        return _call(self._impl.evaluate_full_domain_sum_sketch_to_device, int(hierarchy_level),
+                     device_batch, ptr(weights), J, ptr(sum_out), nbytes(sum_out),
+                     ptr(sketch_out), nbytes(sketch_out), bool(accumulate), s.cuda_stream)
+
+    def evaluate_full_domain_sum_sketch(self, hierarchy_level: int, device_batch, weights=None):
+        """evaluate_full_domain_sum_sketch_to_device with host weights (J x N,
+        None: J = 0) into fresh arrays: numpy uint32 (sums [N, nl], sketches
+        [K, J, nl])."""
+        w = (np.zeros((0, 0), dtype=np.uint32) if weights is None
+             else np.ascontiguousarray(weights, dtype=np.uint32))
+        J = int(w.shape[0]) if w.ndim > 1 else 1
+        sums, sk = _call(self._impl.evaluate_full_domain_sum_sketch, int(hierarchy_level),
+                         device_batch, w.reshape(-1), J)
+        n = int(self.parameters()[hierarchy_level].log_domain_size)
+        nl = sums.size >> n
+        return sums.reshape(1 << n, nl), sk.reshape(int(device_batch.num_keys), J, nl)
+
+    def evaluates_full_domain_sum_sketch_on_device(self, hierarchy_level: int) -> bool:
+        """Whether evaluate_full_domain_sum_sketch_to_device takes this level's
+        value type and domain size (there is no fallback behind it)."""
+        return self._impl.evaluates_full_domain_sum_sketch_on_device(int(hierarchy_level))
+
+    def check_full_domain_sum_sketch_args(self, num_keys: int, hierarchy_level: int, weights,
+                                          num_weight_rows: int, sum_out, sketch_out,
+                                          batch_matches: bool = True) -> None:
+        """The host checks of evaluate_full_domain_sum_sketch_to_device for a
+        batch of `num_keys` keys, in its order; raises what it would raise.
+        Touches no device and needs no batch.  Each buffer is None or a
+        (address, bytes) pair."""
+        w, s, k = (b if b is not None else (0, 0) for b in (weights, sum_out, sketch_out))
+        _call(self._impl.check_full_domain_sum_sketch_args, int(num_keys), bool(batch_matches),
+              int(hierarchy_level), int(w[0]), int(num_weight_rows), int(s[0]), int(s[1]),
+              int(k[0]), int(k[1]))
+
     # -- device-resident incremental evaluation of a key batch (8f.1, cfg 5b) --
     def create_batch_evaluation_context(self, device_batch):
         """EvaluationContext of every key of a device batch, kept on the GPU."""

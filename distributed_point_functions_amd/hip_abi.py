@@ -162,10 +162,19 @@ def load(require_gpu: bool = False):
                              [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I64, P, I, P]),
                             ("dpf_hip_expand_sum_plan",
                              [I64, I, I, ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_expand_sketch_supported", [P]),
+                            ("dpf_hip_expand_sketch",
+                             [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, I, P, P, I64, P, P, I,
+                              P]),
+                            ("dpf_hip_expand_sketch_plan",
+                             [I64, I, I, ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_prefix_batch_max_expand", [P, I]),
                             ("dpf_hip_prefix_batch_level", [ctypes.POINTER(PrefixBatchArgs), P])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = types
+        if hasattr(L, "dpf_hip_expand_sketch_workspace_bytes"):
+            L.dpf_hip_expand_sketch_workspace_bytes.argtypes = [I64, I, I, I, I]
+            L.dpf_hip_expand_sketch_workspace_bytes.restype = ctypes.c_int64
         if hasattr(L, "dpf_hip_expand_sum_workspace_bytes"):
             L.dpf_hip_expand_sum_workspace_bytes.argtypes = [I64, I]
             L.dpf_hip_expand_sum_workspace_bytes.restype = ctypes.c_int64
@@ -288,6 +297,35 @@ def expand_sum_workspace_bytes(num_keys: int, num_levels: int) -> int:
     """Bytes of dpf_hip_expand_sum's workspace for that batch (no GPU needed);
     -1 for arguments out of range."""
     return int(load().dpf_hip_expand_sum_workspace_bytes(num_keys, num_levels))
+
+
+EXPAND_SKETCH_WAVE_ITEMS_PER_CU = 64   # DPF_HIP_EXPAND_SKETCH_WAVE_ITEMS_PER_CU
+EXPAND_SKETCH_MAX_LOG_DOMAIN = 28      # DPF_HIP_EXPAND_SKETCH_MAX_LOG_DOMAIN
+
+
+def expand_sketch_plan(num_keys: int, tree_depth: int, compute_units: int) -> dict:
+    """The launch plan of dpf_hip_expand_sketch for that shape (no GPU needed;
+    DPF_EXPAND_SKETCH_WAVE_ITEMS in the environment replaces the threshold):
+    {"S", "walk", "subtrees", "wave_items", "group", "threshold"}."""
+    out = (ctypes.c_int64 * 6)()
+    check(load().dpf_hip_expand_sketch_plan(num_keys, tree_depth, compute_units, out))
+    return {"S": out[0], "walk": out[1], "subtrees": out[2], "wave_items": out[3],
+            "group": out[4], "threshold": out[5]}
+
+
+def expand_sketch_supported(desc) -> bool:
+    """Whether dpf_hip_expand_sketch takes this value type (`desc` None: a NULL
+    descriptor; no GPU needed)."""
+    return bool(load().dpf_hip_expand_sketch_supported(
+        ctypes.byref(desc) if desc is not None else None))
+
+
+def expand_sketch_workspace_bytes(num_keys: int, num_levels: int, log_domain_size: int,
+                                  num_leaves: int, num_weights: int) -> int:
+    """Bytes of dpf_hip_expand_sketch's workspace for that call (no GPU needed);
+    -1 for arguments out of range."""
+    return int(load().dpf_hip_expand_sketch_workspace_bytes(
+        num_keys, num_levels, log_domain_size, num_leaves, num_weights))
 
 
 def clock_probe(on: bool) -> None:
@@ -515,6 +553,35 @@ def sketch_rows(num_keys: int, row_len: int, desc: ValueDesc, rows, weights, out
     check(L.dpf_hip_sketch_rows(num_keys, row_len, ctypes.byref(desc), _p(rows), J, weight_bits,
                                 _p(weights), _p(out), _stream(stream)))
     return out
+
+
+def expand_sketch(log_domain_size: int, key_seed, party, cw_seed, cw_left, cw_right, keys,
+                  desc: ValueDesc, value_correction, weights=None, sum_out=None,
+                  accumulate: bool = False, workspace=None, stream=None):
+    """dpf_hip_expand_sketch on torch device tensors: key_seed (K, 2) int64,
+    party (K,) uint8, cw_seed (K, n, 2) int64, cw_left / cw_right (K, n) uint8,
+    value_correction (K * nl, 2) int64, weights (J, 2^n) int32 or None, keys =
+    (left, right, value) AES keys as integers.  Returns (sums int32 [2^n, nl],
+    sketches int32 [K, J, nl]); the workspace is a fresh tensor unless given."""
+    import torch
+    L = load(require_gpu=True)
+    K, n, nl = int(key_seed.shape[0]), int(log_domain_size), int(desc.num_leaves)
+    J = 0 if weights is None else int(weights.shape[0])
+    need = expand_sketch_workspace_bytes(K, n, n, nl, J)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=key_seed.device)
+    if sum_out is None:
+        make = torch.zeros if accumulate else torch.empty
+        sum_out = make((1 << n, nl), dtype=torch.int32, device=key_seed.device)
+    sketch = torch.empty((K, J, nl), dtype=torch.int32, device=key_seed.device)
+    kl, kr, kv = (aes_key(k) for k in keys)
+    check(L.dpf_hip_expand_sketch(K, n, n, n, _p(key_seed), _p(party), _p(cw_seed), _p(cw_left),
+                                  _p(cw_right), ctypes.byref(kl), ctypes.byref(kr),
+                                  ctypes.byref(kv), ctypes.byref(desc), _p(value_correction), J,
+                                  _p(weights), _p(workspace), workspace.numel(), _p(sum_out),
+                                  _p(sketch) if J else None, 1 if accumulate else 0,
+                                  _stream(stream)))
+    return sum_out, sketch
 
 
 def eval_points(n, points_per_key, levels, key_seed, party, tree_index, block_index, cw_seed,

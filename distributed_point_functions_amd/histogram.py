@@ -9,6 +9,11 @@ a server's side is one fused launch per batch,
 evaluate_full_domain_sum_to_device, which stores no share vector and can
 stream batch after batch into one accumulator.
 
+Over a field (IntModN<uint32, N>, or the heavy-hitters 2-tuple) the servers can
+check every client before counting it: fold_checked gives the field sum and, in
+the same launch, each client's linear sketches, which `check` tests for a unit
+vector; reconstruct_mod adds the two servers' sums mod N.
+
 Where the clients of one server are spread over several ranks, each rank folds
 its own clients into a vector of its own, and those per-rank vectors are what
 sharding.aggregate_shares reduces across the ranks: nothing here adds a
@@ -53,6 +58,57 @@ def reconstruct(share0, share1, xor: bool) -> np.ndarray:
     a = _host_u64(share0)
     b = _host_u64(share1)
     return a ^ b if xor else a + b
+
+
+def fold_checked(dpf: D.DistributedPointFunction, device_batch, weights, hierarchy_level: int = 0,
+                 out=None, accumulate: bool = False, stream=None):
+    """One server's share of a checked histogram over a field (DESIGN.md
+    section 6h): (sum, sketches), the torch int32 device tensors [2^n, nl] of
+    its batch's sums mod N_e and [K, J, nl] of every client's sketches under
+    `weights` (uint32 (J, 2^n), J <= 2: heavy_hitters.sketch_weights; None for
+    the plain field sum, J = 0), from one launch.  `out`: the sum tensor to
+    write (or, with `accumulate`, to add into mod N_e); None makes a fresh one,
+    zeroed when accumulating.  The sketches are per batch: always fresh."""
+    import torch
+    n = int(dpf.parameters()[hierarchy_level].log_domain_size)
+    nl = dpf.packed_size(hierarchy_level) // 4
+    w = None
+    if weights is not None:
+        w = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.uint32).view(np.int32))
+        w = w.reshape(-1, 1 << n).to("cuda")
+    J = 0 if w is None else int(w.shape[0])
+    if out is None:
+        make = torch.zeros if accumulate else torch.empty
+        out = make((1 << n, nl), dtype=torch.int32, device="cuda")
+    sketches = torch.empty((device_batch.num_keys, J, nl), dtype=torch.int32, device="cuda")
+    dpf.evaluate_full_domain_sum_sketch_to_device(hierarchy_level, device_batch, w, out,
+                                                  sketches if J else None,
+                                                  accumulate=accumulate, stream=stream)
+    return out, sketches
+
+
+def check(s0, s1) -> np.ndarray:
+    """bool[K]: which clients' vectors pass the unit-vector test, from the two
+    servers' sketches under heavy_hitters.sketch_weights of the heavy-hitters
+    value type (heavy_hitters.check_sketches: Z is opened in one process, which
+    stands in for the servers' multiplication protocol)."""
+    from . import heavy_hitters as HH
+    return HH.check_sketches(_host_u32(s0), _host_u32(s1))
+
+
+def reconstruct_mod(share0, share1, moduli: Sequence[int]) -> np.ndarray:
+    """The two servers' field shares combined: uint32 [..., nl], element e
+    added mod moduli[e]."""
+    m = np.asarray(moduli, dtype=np.uint64)
+    a = _host_u32(share0).astype(np.uint64).reshape(-1, len(m))
+    b = _host_u32(share1).astype(np.uint64).reshape(-1, len(m))
+    return ((a + b) % m).astype(np.uint32)
+
+
+def _host_u32(x) -> np.ndarray:
+    if hasattr(x, "cpu"):
+        x = x.cpu().numpy()
+    return np.ascontiguousarray(x).view(np.uint32)
 
 
 def _host_u64(x) -> np.ndarray:

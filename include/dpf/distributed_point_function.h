@@ -452,6 +452,53 @@ class DistributedPointFunction {
   // one of this DistributedPointFunction.  Touches no device.
   Status CheckFullDomainSumArgs(int64_t num_keys, bool batch_matches, int hierarchy_level,
                                 const void* device_out, int64_t out_bytes) const;
+  // Checked private histograms: the full-domain sum of a key batch over a
+  // field, with every key's linear sketches taken in the same launch (the
+  // per-key vectors exist nowhere else).  For T = IntModN<uint32_t, N_0> or
+  // Tuple<IntModN<uint32_t, N_0>, IntModN<uint32_t, N_1>> at `hierarchy_level`
+  // (nl leaves; other value types: UNIMPLEMENTED, there is no fallback behind
+  // this call), n = log_domain_size in [1, 28], N = 2^n, y_k =
+  // EvaluateUntil<T>(hierarchy_level, {}, fresh ctx of key k) and J =
+  // num_weight_rows in {0, 1, 2} rows of N public 32-bit weights
+  // (`device_weights`, [j][i]):
+  //   sum[i][e]       = ( sum_k y_k[i][e] ) mod N_e               uint32 at  i*nl + e
+  //   sketch[k][j][e] = ( sum_i (w[j][i] mod N_e) * y_k[i][e] ) mod N_e
+  //                                                               uint32 at (k*J + j)*nl + e
+  // -- EvaluateUntilBatchSketchToDevice's sketches, in its layout.  J == 0 is
+  // the plain field sum; `device_weights` and `device_sketch` are then not
+  // read and may be null.  With `accumulate` false sum[0, N*nl) is overwritten
+  // and nothing of what it held is read; with true the sums are added mod N_e
+  // into what it holds, whose entries must be below N_e.  The sketches are
+  // per batch and always overwritten.  An empty batch launches nothing: it
+  // writes N*nl zeros, or with `accumulate` leaves the sums untouched.  Works
+  // on `stream` (asynchronous) and returns N.  The call's table, accumulators
+  // and reduced weights live in this object's device scratch (ReleaseScratch
+  // frees it).  Checked in this order, before the device is touched, the first
+  // failure reported: the level, the value type and n <= 28, J, null pointers
+  // (the sketches' only when there is a key to sketch), sum_bytes >= N*nl*4, sketch_bytes >= K*J*nl*4, that the batch is this
+  // DPF's, and alignment (sums to 16 bytes, weights and sketches to 4).
+  StatusOr<int64_t> EvaluateFullDomainSumSketchToDevice(
+      int hierarchy_level, const DeviceKeyBatch& keys, const uint32_t* device_weights,
+      int num_weight_rows, void* device_sum, int64_t sum_bytes, void* device_sketch,
+      int64_t sketch_bytes, bool accumulate, void* stream) const;
+  // The same with host weights (J rows of N) into fresh vectors returned to
+  // the host: N*nl sums and K*J*nl sketches.
+  struct SumSketch {
+    std::vector<uint32_t> sum, sketch;
+  };
+  StatusOr<SumSketch> EvaluateFullDomainSumSketch(int hierarchy_level, const DeviceKeyBatch& keys,
+                                                  Span<const uint32_t> weights,
+                                                  int num_weight_rows) const;
+  // True when `hierarchy_level` exists and its value type and domain size are
+  // ones EvaluateFullDomainSumSketchToDevice takes.
+  bool EvaluatesFullDomainSumSketchOnDevice(int hierarchy_level) const;
+  // EvaluateFullDomainSumSketchToDevice's argument checks, in its order and
+  // with its messages, for a batch of num_keys keys that is (`batch_matches`)
+  // or is not one of this DistributedPointFunction.  Touches no device.
+  Status CheckFullDomainSumSketchArgs(int64_t num_keys, bool batch_matches, int hierarchy_level,
+                                      const void* device_weights, int num_weight_rows,
+                                      const void* device_sum, int64_t sum_bytes,
+                                      const void* device_sketch, int64_t sketch_bytes) const;
   // ---- device-resident incremental evaluation of a key batch (8f.1, cfg 5b)
   // A fresh context for every key of `keys` (previous_hierarchy_level -1), as
   // CreateEvaluationContext would make per key.  `keys` must outlive it.

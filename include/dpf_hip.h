@@ -783,6 +783,88 @@ int dpf_hip_expand_sum(int64_t num_keys, int num_levels, int cw_stride, int log_
  * [0, 29], num_cus outside [1, 65536]. */
 int dpf_hip_expand_sum_plan(int64_t num_keys, int tree_depth, int num_cus, int64_t out[6]);
 
+/* ---- checked private histograms: fused field sum and per-key sketches -------
+ * No reference counterpart.  dpf_hip_expand_sum over a field, with the linear
+ * sketches of every key's own vector (dpf_hip_sketch_rows' definition) taken
+ * in the same pass, where alone the per-key vectors exist.  Value types:
+ * IntModN<uint32_t, N_0> and Tuple<IntModN<uint32_t, N_0>, IntModN<uint32_t,
+ * N_1>> (nl = num_leaves <= 2, one element per block, tree depth = n).  With
+ * n = log_domain_size in [1, 28], N = 2^n, y_k the N shares EvaluateUntil
+ * gives for key k and J = num_weights in {0, 1, 2} rows of N 32-bit weights
+ * (`weights`, device, [j][i]):
+ *   sum_out[i*nl + e]          = ( sum_{k<K} y_k[i][e] ) mod N_e
+ *   sketch_out[(k*J + j)*nl+e] = ( sum_{i<N} (w[j][i] mod N_e) * y_k[i][e] ) mod N_e
+ * Exact for any K < 2^31.  The key batch is passed as dpf_hip_expand_sum takes
+ * it, with num_levels = the hierarchy level's tree depth = log_domain_size,
+ * cw_stride the key's correction-word count and value_correction that level's,
+ * nl blocks per key.  `workspace` is device memory of at least
+ * dpf_hip_expand_sketch_workspace_bytes(...) bytes holding the call's
+ * [level][key] table, its 64-bit accumulators and the reduced weights; it must
+ * stay untouched until the call's work on `stream` is done.  accumulate == 0:
+ * sum_out[0, N*nl) is overwritten and nothing of what it held is read;
+ * otherwise the sums are added mod N_e into what it holds, whose entries must
+ * be below N_e.  sketch_out[0, K*J*nl) is always overwritten.  With J == 0
+ * `weights` and `sketch_out` are not read and may be NULL.  The call is
+ * asynchronous on `stream` and allocates nothing.
+ * Checks, all before any device call, the first failing one reported:
+ *   1. num_keys outside [0, 2^31 - 1], log_domain_size outside [1, 28],
+ *      num_levels != log_domain_size: 3;
+ *   2. NULL desc or AES keys: 3;
+ *   3. a value type dpf_hip_expand_sketch_supported refuses: 12 UNIMPLEMENTED
+ *      (there is no fallback behind this call);
+ *   4. num_weights outside [0, 2]: 3;      5. cw_stride < num_levels: 3;
+ *   6. NULL sum_out; with num_weights > 0, NULL weights, or NULL sketch_out
+ *      unless num_keys == 0 (no sketch is written): 3;
+ *   7. num_keys == 0: clears sum_out[0, N*nl) unless accumulating, returns 0,
+ *      no kernel is launched, sketch_out is untouched;
+ *   8. NULL key arrays: 3;
+ *   9. NULL workspace or workspace_bytes too small: 8, the message names the
+ *      size needed;
+ *  10. sum_out or workspace not aligned to 16 bytes, weights or sketch_out
+ *      not to 4: 3.
+ * The item loop is dynamic as chunked launches are (DPF_EXPAND_SKETCH_DYNAMIC=0,
+ * read per launch: a fixed share per wave; A/B and test hook), and
+ * dpf_hip_last_dynamic_chunks reports it. */
+#define DPF_HIP_EXPAND_SKETCH_WAVE_ITEMS_PER_CU 64
+#define DPF_HIP_EXPAND_SKETCH_MAX_LOG_DOMAIN 28
+int dpf_hip_expand_sketch_supported(const dpf_value_desc* desc);
+/* Bytes of the call's workspace, the keys rounded up to a multiple of 64 (kp):
+ * kp * (20 * num_levels + 12) for the table, 8 * N * num_leaves and
+ * 8 * kp * num_weights * num_leaves for the accumulators, 4 * N * num_weights
+ * * num_leaves for the reduced weights.  Monotone in every argument; -1 for
+ * num_keys outside [0, 2^31 - 1], log_domain_size outside [1, 28], num_levels
+ * != log_domain_size, num_leaves outside [1, 2] or num_weights outside [0, 2].
+ * No device is touched. */
+int64_t dpf_hip_expand_sketch_workspace_bytes(int64_t num_keys, int num_levels,
+                                              int log_domain_size, int num_leaves,
+                                              int num_weights);
+int dpf_hip_expand_sketch(int64_t num_keys, int num_levels, int cw_stride, int log_domain_size,
+                          const dpf_block* key_seed, const uint8_t* party,
+                          const dpf_block* cw_seed, const uint8_t* cw_left,
+                          const uint8_t* cw_right, const dpf_aes_key* key_left,
+                          const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                          const dpf_value_desc* desc, const dpf_block* value_correction,
+                          int num_weights, const uint32_t* weights, void* workspace,
+                          int64_t workspace_bytes, uint32_t* sum_out, uint32_t* sketch_out,
+                          int accumulate, void* stream);
+/* The launch plan of dpf_hip_expand_sketch on a device of num_cus compute
+ * units (no device is touched), dpf_hip_expand_sum_plan's analogue: a wave
+ * item is (key chunk of 64 consecutive keys, subtree), the wave walks `walk`
+ * levels from its keys' roots and visits S levels depth-first, tree_depth =
+ * walk + S, finishing the subtree in leaf pairs (`group` = 1 level).  out =
+ * {S, walk, subtrees per chunk = 2^walk, wave items = ceil(K / 64) * 2^walk,
+ * group, threshold}.  walk is the smallest value with wave items >= threshold,
+ * but at most tree_depth - group.  threshold is
+ * DPF_HIP_EXPAND_SKETCH_WAVE_ITEMS_PER_CU * num_cus, or, when the environment
+ * holds DPF_EXPAND_SKETCH_WAVE_ITEMS=<t> with t >= 1 (read per call; test and
+ * A/B hook), min(t, 2^24) for the whole launch.  Small case: tree_depth 0 has
+ * no level for a leaf pair and is group = S = walk = 0; the value types of
+ * dpf_hip_expand_sketch have tree_depth = n >= 1 (n = 1 is exactly one leaf
+ * pair), so this case is planned but never launched.  A key costs 2^walk *
+ * (walk + 2 (2^S - 1) + nl 2^S) AES.  3 for num_keys outside [1, 2^31 - 1],
+ * tree_depth outside [0, 28], num_cus outside [1, 65536]. */
+int dpf_hip_expand_sketch_plan(int64_t num_keys, int tree_depth, int num_cus, int64_t out[6]);
+
 /* ---- batched multiple-interval-containment gate (eprint 2020/1392 Fig. 14) -
  * MultipleIntervalContainmentGate::Eval (dcf/fss_gates/
  * multiple_interval_containment.cc:206-275) for num_gates gates over
