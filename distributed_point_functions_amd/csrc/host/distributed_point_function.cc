@@ -412,11 +412,23 @@ Status CheckRecordWords(int64_t record_words) {
   return OkStatus();
 }
 
-// A slab hook (DPF_DOT_SLAB_LOG, DPF_SELECT_SLAB_LOG; read per call; test
-// hooks): the log2 of a slab's rows, in place of the scratch bound.
+// A slab hook (DPF_DOT_SLAB_LOG, DPF_SELECT_SLAB_LOG, DPF_DOT_BATCH_SLAB_LOG;
+// read per call; test hooks): the log2 of a slab's rows, in place of the
+// scratch bound.
 std::optional<int> SlabLogHook(const char* name) {
   const char* v = std::getenv(name);
   return v && *v ? std::optional<int>(std::atoi(v)) : std::nullopt;
+}
+
+// Keys of EvaluateDotBatchToDevice whose share rows lie in the scratch
+// together, or the A/B hook's value, at least 1.  Measured at 4 and 32 words
+// only: 8 keys for wide records, 4 for narrow ones, where the
+// shares outweigh the records and larger slabs count for more than fewer
+// passes over the database.
+int DotBatchHostTile(int64_t record_words) { return record_words >= 16 ? 8 : 4; }
+int64_t TileHook(const char* name, int dflt) {
+  const char* v = std::getenv(name);
+  return v && *v ? std::max(std::atoi(v), 1) : dflt;
 }
 
 // Phase split of the prefix walk (ComputePartialEvaluations), printed at exit
@@ -1436,6 +1448,133 @@ StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateSelect(
   DPF_RETURN_IF_ERROR(EvaluateSelectToDevice(keys, hierarchy_level, 0, 1, device_db, db_bytes,
                                              record_words, s->gathered.get(),
                                              static_cast<int64_t>(words * 8), nullptr)
+                          .status());
+  std::vector<uint64_t> out(words);
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), s->gathered.get(), words * 8, nullptr));
+  return out;
+}
+
+// Additive-share PIR batched over queries: the streamed path of
+// EvaluateSelectToDevice with 64 bits per record and query instead of one.
+// The keys are taken a tile at a time, and the shard is cut into slabs of
+// whole leaf blocks of which a tile's share rows fit the scratch bound
+// together; every key's slab is expanded by the unchanged dpf_hip_expand into
+// its row of the scratch, and dpf_hip_dot_rows_batch folds the slab of the
+// database into the tile's answers at once.  DPF_DOT_BATCH_SLAB_LOG (read per
+// call; test hook) sets the log2 of a slab's records instead.
+Status DistributedPointFunction::CheckDotBatchArgs(
+    Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard, int64_t num_shards,
+    const void* device_db, int64_t db_bytes, int64_t record_words, const void* device_out,
+    int64_t out_bytes, SelectShape* shape) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
+  const dpf_internal::FlatValueType& f = flat_[hierarchy_level];
+  const dpf_value_desc desc = MakeDesc(f, blocks_needed_[hierarchy_level]);
+  if (dpf_hip_dot_rows_batch_workspace_bytes(&desc, 1, 1) < 0)
+    return UnimplementedError(
+        "the batched database fold is implemented for uint64_t and XorWrapper<uint64_t> only");
+  // The cap of EvaluateDotToDevice: one record per element.
+  const int stop_level = hierarchy_to_tree()[hierarchy_level];
+  DPF_ASSIGN_OR_RETURN(const int k, dpf_internal::ShardLevels(
+                                        shard, num_shards, stop_level,
+                                        parameters()[hierarchy_level].log_domain_size(), 0));
+  DPF_RETURN_IF_ERROR(CheckRecordWords(record_words));
+  const int64_t Q = static_cast<int64_t>(keys.size());
+  if (Q < 1 || Q > DPF_HIP_DOT_BATCH_MAX_QUERIES)
+    return InvalidArgumentError("`keys` must hold between 1 and 64 keys");
+  const int64_t rows =
+      (int64_t{1} << (stop_level - k)) * corrected_elements_per_block(hierarchy_level);
+  if (shape) *shape = SelectShape{k, stop_level, rows};
+  if (rows > (std::numeric_limits<int64_t>::max() / (8 * record_words)) ||
+      db_bytes < rows * 8 * record_words)
+    return InvalidArgumentError("database buffer too small");
+  if (out_bytes < Q * record_words * 8)
+    return InvalidArgumentError("device output buffer too small");
+  if (!device_db || !device_out)
+    return InvalidArgumentError("`device_db` and `device_out` must not be null");
+  for (int64_t q = 0; q < Q; ++q) {
+    if (!keys[q])
+      return InvalidArgumentError("`keys[" + std::to_string(q) + "]` must not be null");
+    if (Status st = validator_->ValidateDpfKey(*keys[q]); !st.ok())
+      return Status(st.code(), "DpfKey " + std::to_string(q) + ": " + st.message());
+  }
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateDotBatchToDevice(
+    Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard, int64_t num_shards,
+    const void* device_db, int64_t db_bytes, int64_t record_words, void* device_out,
+    int64_t out_bytes, void* stream) const {
+  SelectShape shape;
+  DPF_RETURN_IF_ERROR(CheckDotBatchArgs(keys, hierarchy_level, shard, num_shards, device_db,
+                                        db_bytes, record_words, device_out, out_bytes, &shape));
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const int cepb = corrected_elements_per_block(hierarchy_level);
+  const int W = static_cast<int>(record_words);
+  const int64_t Q = static_cast<int64_t>(keys.size());
+  // The keys go through the scratch a tile at a time: the database is read
+  // once per tile whatever the scratch holds, and the fewer share rows lie in
+  // it together, the larger the slabs and the fewer, larger expansions a call
+  // takes.  DPF_DOT_BATCH_TILE=<t> (read per call; A/B hook) sets the tile.
+  const int64_t T = std::min<int64_t>(
+      std::min<int64_t>(Q, TileHook("DPF_DOT_BATCH_TILE", DotBatchHostTile(record_words))),
+      DPF_HIP_DOT_BATCH_MAX_QUERIES);
+  const int workspace_bytes =
+      dpf_hip_dot_rows_batch_workspace_bytes(&desc, W, static_cast<int>(T));
+  if (workspace_bytes < 0) return InvalidArgumentError(dpf_hip_last_error());
+
+  // Slabs of whole leaf blocks whose T rows of 64-bit shares fit the scratch bound.
+  DPF_ASSIGN_OR_RETURN(const dpf_internal::SlabPlan slab,
+                       dpf_internal::PlanSlabs(shape.rows, cepb, 64 * T,
+                                               SlabLogHook("DPF_DOT_BATCH_SLAB_LOG")));
+  const int64_t stride = (slab.slab_rows * 8 + 15) & ~int64_t{15};   // bytes of a key's share row
+
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  // One image for all keys: the slabs' paths once, then each key's parts.
+  PackedUploads& up = NextShardImage(*s);
+  DPF_RETURN_IF_ERROR(up.Reset());
+  const size_t o_path = AddSubtreePaths(shard, slab.j, up);
+  std::vector<SubtreeParts> sub(Q);
+  for (int64_t q = 0; q < Q; ++q) {
+    DPF_ASSIGN_OR_RETURN(std::vector<uint128> vcw, ValueCorrectionLeaves(*keys[q], hierarchy_level));
+    sub[q] = AddSubtreeParts(*keys[q], slab.slabs, shape.k + slab.j, shape.stop_level, vcw, up);
+  }
+  DPF_RETURN_IF_ERROR(up.Commit(stream));
+  for (int64_t q = 0; q < Q; ++q) DPF_RETURN_IF_ERROR(WalkSubtreeRoots(sub[q], o_path, up, stream));
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace, workspace_bytes, stream));
+  DPF_RETURN_IF_ERROR(s->out.Reserve(static_cast<size_t>(T * stride)));
+  char* y = static_cast<char*>(s->out.get());
+  for (int64_t i = 0; i < slab.slabs; ++i) {
+    for (int64_t q0 = 0; q0 < Q; q0 += T) {
+      const int64_t nq = std::min(T, Q - q0);
+      for (int64_t q = 0; q < nq; ++q)
+        DPF_RETURN_IF_ERROR(
+            ExpandSubtree(sub[q0 + q], i, desc, cepb, up, y + q * stride, stream));
+      HIP_RETURN_IF_ERROR(dpf_hip_dot_rows_batch(
+          slab.slab_rows, W, static_cast<int>(nq), &desc, y, stride,
+          static_cast<const char*>(device_db) + i * slab.slab_rows * 8 * W, i > 0,
+          s->workspace.get(), static_cast<uint64_t*>(device_out) + q0 * W, stream));
+    }
+  }
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  DPF_RETURN_IF_ERROR(up.MarkUsed(stream));
+  return Q * record_words;
+}
+
+StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateDotBatch(
+    Span<const DpfKey* const> keys, int hierarchy_level, const void* device_db, int64_t db_bytes,
+    int64_t record_words) const {
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);
+  // Checked before the result buffer is allocated: host errors touch no device.
+  DPF_RETURN_IF_ERROR(CheckDotBatchArgs(keys, hierarchy_level, 0, 1, device_db, db_bytes,
+                                        record_words, /*device_out=*/this,
+                                        std::numeric_limits<int64_t>::max(), /*shape=*/nullptr));
+  const size_t words = keys.size() * static_cast<size_t>(record_words);
+  DPF_RETURN_IF_ERROR(s->gathered.Reserve(words * 8));
+  DPF_RETURN_IF_ERROR(EvaluateDotBatchToDevice(keys, hierarchy_level, 0, 1, device_db, db_bytes,
+                                               record_words, s->gathered.get(),
+                                               static_cast<int64_t>(words * 8), nullptr)
                           .status());
   std::vector<uint64_t> out(words);
   HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), s->gathered.get(), words * 8, nullptr));

@@ -367,6 +367,49 @@ class PyDpf {
     if (!out.empty()) std::memcpy(a.mutable_data(), out.data(), out.size() * 8);
     return a;
   }
+  int64_t EvaluateDotBatchToDevice(const std::vector<py::bytes>& key_bytes, int level,
+                                   int64_t shard, int64_t num_shards, uintptr_t db_ptr,
+                                   int64_t db_bytes, int64_t record_words, uintptr_t out_ptr,
+                                   int64_t out_bytes, uintptr_t stream) {
+    std::vector<DpfKey> keys;
+    for (const auto& b : key_bytes) keys.push_back(Parse<DpfKey>(b));
+    std::vector<const DpfKey*> ptrs;
+    for (const auto& k : keys) ptrs.push_back(&k);
+    py::gil_scoped_release nogil;
+    auto r = dpf_->EvaluateDotBatchToDevice(MakeConstSpan(ptrs), level, shard, num_shards,
+                                            reinterpret_cast<const void*>(db_ptr), db_bytes,
+                                            record_words, reinterpret_cast<void*>(out_ptr),
+                                            out_bytes, reinterpret_cast<void*>(stream));
+    if (!r.ok()) {
+      py::gil_scoped_acquire g;
+      throw StatusError(r.status());
+    }
+    return *r;
+  }
+  py::array_t<uint64_t> EvaluateDotBatch(const std::vector<py::bytes>& key_bytes, int level,
+                                         uintptr_t db_ptr, int64_t db_bytes,
+                                         int64_t record_words) {
+    std::vector<DpfKey> keys;
+    for (const auto& b : key_bytes) keys.push_back(Parse<DpfKey>(b));
+    std::vector<const DpfKey*> ptrs;
+    for (const auto& k : keys) ptrs.push_back(&k);
+    std::vector<uint64_t> out;
+    {
+      py::gil_scoped_release nogil;
+      auto r = dpf_->EvaluateDotBatch(MakeConstSpan(ptrs), level,
+                                      reinterpret_cast<const void*>(db_ptr), db_bytes,
+                                      record_words);
+      if (!r.ok()) {
+        py::gil_scoped_acquire g;
+        throw StatusError(r.status());
+      }
+      out = std::move(*r);
+    }
+    py::array_t<uint64_t> a({static_cast<py::ssize_t>(keys.size()),
+                             static_cast<py::ssize_t>(record_words)});
+    if (!out.empty()) std::memcpy(a.mutable_data(), out.data(), out.size() * 8);
+    return a;
+  }
   py::array_t<uint8_t> EvaluateAt(const py::bytes& key_bytes, int level,
                                   const py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& points,
                                   const py::object& vt) {
@@ -971,6 +1014,8 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_dot", &PyDpf::EvaluateDot)
       .def("evaluate_select_to_device", &PyDpf::EvaluateSelectToDevice)
       .def("evaluate_select", &PyDpf::EvaluateSelect)
+      .def("evaluate_dot_batch_to_device", &PyDpf::EvaluateDotBatchToDevice)
+      .def("evaluate_dot_batch", &PyDpf::EvaluateDotBatch)
       .def("evaluate_at", &PyDpf::EvaluateAt)
       .def("evaluate_at_ctx", &PyDpf::EvaluateAtCtx)
       .def("evaluate_at_batch", &PyDpf::EvaluateAtBatch)

@@ -1,8 +1,9 @@
 // shard_plan.h -- the host-side plan of a full-domain call that expands one
 // key's tree as several independent subtree launches (EvaluateShardToDevice,
-// EvaluateDotToDevice, EvaluateSelectToDevice and the split first call of
-// EvaluateUntil), as pure functions: which subtree a shard is, how many slabs
-// a database fold cuts it into, and the tree paths of the subtrees' roots.
+// EvaluateDotToDevice, EvaluateSelectToDevice, EvaluateDotBatchToDevice and
+// the split first call of EvaluateUntil), as pure functions: which subtree a
+// shard is, how many slabs a database fold cuts it into, and the tree paths
+// of the subtrees' roots.
 // Nothing here calls a dpf_hip_* entry point or touches a context, so a
 // stand-alone program tests it (tests/cpp/shard_plan_test.cc).
 #ifndef DPF_HOST_SHARD_PLAN_H_

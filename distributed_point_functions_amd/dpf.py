@@ -387,6 +387,43 @@ class DistributedPointFunction:
         torch.cuda.synchronize(out.device)
         return out[:n].cpu().numpy().view(np.uint64).reshape(len(keys), int(record_words))
 
+    def evaluate_dot_batch_to_device(self, keys: Sequence[pb.DpfKey], hierarchy_level: int, db,
+                                     record_words: int, out, shard: int = 0, num_shards: int = 1,
+                                     stream=None) -> int:
+        """Additive-share two-server PIR answers of up to 64 keys against one
+        pass over the database: evaluate_dot_to_device for every key at once,
+        for uint64 (out[q][w] = sum_i y_q[i] * db[i][w] mod 2^64) and
+        XorWrapper<uint64> (XOR_i (y_q[i] & db[i][w])).  `db` (torch device
+        tensor) holds this shard's records, row-major, `record_words` uint64
+        words each; writes len(keys) * record_words uint64 into the torch
+        device tensor `out` and returns that count.  The two parties' (and all
+        shards') answers combine with the type's +."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(out.device)
+        return _call(self._impl.evaluate_dot_batch_to_device,
+                     [k.SerializeToString() for k in keys], int(hierarchy_level), int(shard),
+                     int(num_shards), db.data_ptr(), db.numel() * db.element_size(),
+                     int(record_words), out.data_ptr(), out.numel() * out.element_size(),
+                     s.cuda_stream)
+
+    def evaluate_dot_batch(self, keys: Sequence[pb.DpfKey], hierarchy_level: int, db,
+                           record_words: int, shard: int = 0, num_shards: int = 1):
+        """evaluate_dot_batch_to_device returned as a numpy uint64 array of
+        shape (len(keys), record_words)."""
+        if int(num_shards) == 1 and int(shard) == 0:
+            return _call(self._impl.evaluate_dot_batch, [k.SerializeToString() for k in keys],
+                         int(hierarchy_level), db.data_ptr(), db.numel() * db.element_size(),
+                         int(record_words))
+        import torch
+        n = max(len(keys) * int(record_words), 0)
+        out = torch.empty(max(n, 1), dtype=torch.int64, device=db.device)
+        self.evaluate_dot_batch_to_device(keys, hierarchy_level, db, record_words, out,
+                                          shard=shard, num_shards=num_shards)
+        torch.cuda.synchronize(out.device)
+        return out[:n].cpu().numpy().view(np.uint64).reshape(len(keys), int(record_words))
+
     def evaluate_at_batch(self, keys: Sequence[pb.DpfKey], hierarchy_level: int,
                           points: Sequence[int], points_per_key: int, packed: bool = False):
         pts = points if isinstance(points, np.ndarray) else u128_array(points)

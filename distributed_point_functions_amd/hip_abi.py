@@ -140,6 +140,9 @@ def load(require_gpu: bool = False):
                             ("dpf_hip_select_rows", [I64, I, I, P, I64, P, I, P, P, P]),
                             ("dpf_hip_select_workspace_bytes", [I, I]),
                             ("dpf_hip_last_select_shape", [ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_dot_rows_batch", [I64, I, I, P, P, I64, P, I, P, P, P]),
+                            ("dpf_hip_dot_rows_batch_workspace_bytes", [P, I, I]),
+                            ("dpf_hip_last_dot_batch_shape", [ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_sketch_rows", [I64, I64, P, P, I, I, P, P, P]),
                             ("dpf_hip_sketch_supported", [P]),
                             ("dpf_hip_gen_keys_supported", [P]),
@@ -210,8 +213,8 @@ def last_points_kernel() -> str:
 
 def last_dot_kernel() -> str:
     """Path of this thread's last dot call: "small", "pair" or "octet" (the
-    fused expand kernel), "rows" (dot_rows) or "select" (select_rows) --
-    dispatch diagnostics for the tests."""
+    fused expand kernel), "rows" (dot_rows), "select" (select_rows) or
+    "rows_batch" (dot_rows_batch) -- dispatch diagnostics for the tests."""
     return load().dpf_hip_last_dot_kernel().decode()
 
 
@@ -237,6 +240,24 @@ def last_select_shape():
     this thread's last select_rows -- dispatch diagnostics for the tests."""
     a = (ctypes.c_int64 * 3)()
     check(load().dpf_hip_last_select_shape(a))
+    return tuple(a)
+
+
+def dot_batch_workspace_bytes(desc: ValueDesc, record_words: int, num_queries: int) -> int:
+    """Bytes of workspace dot_rows_batch needs (no GPU needed)."""
+    n = load().dpf_hip_dot_rows_batch_workspace_bytes(ctypes.byref(desc), record_words,
+                                                      num_queries)
+    if n < 0:
+        raise DpfHipError(12 if 1 <= record_words <= 1024 and 1 <= num_queries <= 64 else 3,
+                          load().dpf_hip_last_error().decode())
+    return n
+
+
+def last_dot_batch_shape():
+    """(queries per tile, passes over the database, workgroups per pass) of
+    this thread's last dot_rows_batch -- dispatch diagnostics for the tests."""
+    a = (ctypes.c_int64 * 3)()
+    check(load().dpf_hip_last_dot_batch_shape(a))
     return tuple(a)
 
 
@@ -536,6 +557,26 @@ def select_rows(num_rows: int, record_words: int, num_queries: int, sel, sel_str
     check(L.dpf_hip_select_rows(num_rows, record_words, num_queries, _p(sel), sel_stride_bytes,
                                 _p(db), 1 if accumulate else 0, _p(workspace), _p(out),
                                 _stream(stream)))
+    return out
+
+
+def dot_rows_batch(num_rows: int, record_words: int, num_queries: int, desc: ValueDesc, y,
+                   y_stride_bytes: int, db, accumulate: bool = False, workspace=None, out=None,
+                   stream=None):
+    """out[q][w] (+)= fold of row q of `y` (device, packed 8-byte shares, rows
+    y_stride_bytes apart) into `db`'s first num_rows records: sums mod 2^64 for
+    uint64, XOR of ANDs for XorWrapper<uint64>; returns (num_queries,
+    record_words) as an int64 tensor (the bits of uint64)."""
+    import torch
+    L = load(require_gpu=True)
+    if workspace is None:
+        workspace = torch.empty(dot_batch_workspace_bytes(desc, record_words, num_queries),
+                                dtype=torch.uint8, device=db.device)
+    if out is None:
+        out = torch.empty((num_queries, record_words), dtype=torch.int64, device=db.device)
+    check(L.dpf_hip_dot_rows_batch(num_rows, record_words, num_queries, ctypes.byref(desc), _p(y),
+                                   y_stride_bytes, _p(db), 1 if accumulate else 0, _p(workspace),
+                                   _p(out), _stream(stream)))
     return out
 
 

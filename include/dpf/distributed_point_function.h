@@ -275,6 +275,31 @@ class DistributedPointFunction {
   StatusOr<std::vector<uint64_t>> EvaluateSelect(Span<const DpfKey* const> keys,
                                                  int hierarchy_level, const void* device_db,
                                                  int64_t db_bytes, int64_t record_words) const;
+  // Additive-share two-server PIR, batched over queries: EvaluateDotToDevice
+  // for up to 64 keys against one pass over the database.  For T = uint64_t
+  // or XorWrapper<uint64_t> (other value types: UNIMPLEMENTED) let y_q =
+  // EvaluateUntil<T>(hierarchy_level, {}, fresh ctx of keys[q]) (n elements)
+  // and `device_db` a row-major device array of n records of `record_words`
+  // uint64 words.  Then
+  //   uint64_t:             out[q][w] = sum_i y_q[i] * db[i][w]  (mod 2^64)
+  //   XorWrapper<uint64_t>: out[q][w] = XOR_i (y_q[i] & db[i][w]);
+  // row q is what EvaluateDotToDevice(keys[q], ...) writes, bit for bit, and
+  // the two parties' rows combine with T's + to beta_q * db[alpha_q] (beta_q &
+  // db[alpha_q]).  The database is read once per tile of queries, not once per
+  // key; keys.size() is in [1, 64].  With num_shards > 1 (a power of two),
+  // `device_db` holds only shard `shard`'s n / num_shards records and the
+  // shards' answers combine with T's +.  Stateless and key-based like
+  // EvaluateDotToDevice.  Writes keys.size() * record_words uint64 to
+  // `device_out` on `stream` (asynchronous) and returns that count.
+  StatusOr<int64_t> EvaluateDotBatchToDevice(Span<const DpfKey* const> keys, int hierarchy_level,
+                                             int64_t shard, int64_t num_shards,
+                                             const void* device_db, int64_t db_bytes,
+                                             int64_t record_words, void* device_out,
+                                             int64_t out_bytes, void* stream) const;
+  // The unsharded answers returned to the host, [keys.size()][record_words].
+  StatusOr<std::vector<uint64_t>> EvaluateDotBatch(Span<const DpfKey* const> keys,
+                                                   int hierarchy_level, const void* device_db,
+                                                   int64_t db_bytes, int64_t record_words) const;
   StatusOr<std::vector<uint8_t>> EvaluateAtPacked(const DpfKey& key, int hierarchy_level,
                                                   Span<const uint128> evaluation_points,
                                                   EvaluationContext* ctx,
@@ -631,6 +656,12 @@ class DistributedPointFunction {
                          int64_t num_shards, const void* device_db, int64_t db_bytes,
                          int64_t record_words, const void* device_out, int64_t out_bytes,
                          SelectShape* shape) const;
+  // Every argument check of EvaluateDotBatchToDevice, in CheckSelectArgs'
+  // order, and the shard's shape (`shape` may be null); touches no device.
+  Status CheckDotBatchArgs(Span<const DpfKey* const> keys, int hierarchy_level, int64_t shard,
+                           int64_t num_shards, const void* device_db, int64_t db_bytes,
+                           int64_t record_words, const void* device_out, int64_t out_bytes,
+                           SelectShape* shape) const;
   // Sizes `b` for n keys, and fills row k from `key` (validated).
   void ResizeKeyBatch(int64_t n, KeyBatch* b) const;
   Status FillKeyBatchRow(const DpfKey& key, int64_t k, KeyBatch* b) const;

@@ -231,8 +231,8 @@ int dpf_hip_expand_dot_workspace_bytes(const dpf_value_desc* desc, int record_wo
 int dpf_hip_expand_dot_fused(const dpf_value_desc* desc, int record_words);
 /* Diagnostic: the path the calling thread's last dot call took: "small",
  * "pair" or "octet" (dpf_hip_expand_dot, the expand kernel it ran), "rows"
- * (dpf_hip_dot_rows) or "select" (dpf_hip_select_rows); "" before the first
- * call. */
+ * (dpf_hip_dot_rows), "select" (dpf_hip_select_rows) or "rows_batch"
+ * (dpf_hip_dot_rows_batch); "" before the first call. */
 const char* dpf_hip_last_dot_kernel(void);
 
 /* ---- dense PIR: a bit-selected database fold batched over queries ----------
@@ -264,6 +264,49 @@ int dpf_hip_select_workspace_bytes(int record_words, int num_queries);
  * {queries per tile, passes over the database = ceil(num_queries / tile),
  * workgroups of one pass}. */
 int dpf_hip_last_select_shape(int64_t* out3);
+
+/* ---- additive-share PIR: a word-weighted database fold batched over queries -
+ * No reference counterpart.  The word-valued sibling of dpf_hip_select_rows:
+ * `db` is a row-major device array of num_rows records of record_words uint64
+ * words; row q of `y` (device, at y + q * y_stride_bytes) is query q's share
+ * vector, num_rows packed 8-byte elements -- the packed output of
+ * dpf_hip_expand for uint64_t or XorWrapper<uint64_t>.  For q < num_queries,
+ * w < W:
+ *   uint64_t:              out[q*W + w] (+)= sum_i y_q[i] * db[i*W + w] (mod 2^64)
+ *   XorWrapper<uint64_t>:  out[q*W + w] (^)= XOR_i (y_q[i] & db[i*W + w])
+ * (accumulate != 0 combines with out's old value -- the next slab of a
+ * streamed fold --, else out is overwritten; num_rows == 0 is an empty sum).
+ * Row q is what dpf_hip_dot_rows writes for y_q, bit for bit: both maps are
+ * exact in any order.  The database is read once per tile of queries
+ * (dpf_hip_last_dot_batch_shape), not once per query.  num_rows is arbitrary
+ * and record_words need not be a power of two.  Checked in this order, before
+ * any device call:
+ *   record_words in [1, DPF_HIP_DOT_MAX_RECORD_WORDS], num_queries in [1,
+ *   DPF_HIP_DOT_BATCH_MAX_QUERIES], num_rows in range; desc, out and (for
+ *   num_rows > 0) y and db not NULL; y_stride_bytes a multiple of 16 and at
+ *   least 8 * num_rows: else 3 INVALID_ARGUMENT;
+ *   a value type other than uint64_t or XorWrapper<uint64_t>: 12
+ *   UNIMPLEMENTED (no fallback);
+ *   no workspace: 8 RESOURCE_EXHAUSTED, naming the bytes it needs.
+ * `workspace` (device, dpf_hip_dot_rows_batch_workspace_bytes) holds one
+ * partial [tile][record_words] per workgroup, written with plain stores (no
+ * atomics) and folded by a second small kernel; the call does not depend on
+ * what it held before.  Asynchronous on `stream`; allocates nothing.
+ * dpf_hip_last_dot_kernel reports "rows_batch" after this call. */
+#define DPF_HIP_DOT_BATCH_MAX_QUERIES 64
+int dpf_hip_dot_rows_batch(int64_t num_rows, int record_words, int num_queries,
+                           const dpf_value_desc* desc, const void* y, int64_t y_stride_bytes,
+                           const void* db, int accumulate, void* workspace, void* out,
+                           void* stream);
+/* Bytes of workspace the call needs; never less for a larger record_words or
+ * num_queries (-1 and a last error for counts out of range or an unsupported
+ * type).  No device is touched. */
+int dpf_hip_dot_rows_batch_workspace_bytes(const dpf_value_desc* desc, int record_words,
+                                           int num_queries);
+/* Diagnostic: the shape of the calling thread's last dpf_hip_dot_rows_batch:
+ * {queries per tile, passes over the database = ceil(num_queries / tile),
+ * workgroups of one pass}. */
+int dpf_hip_last_dot_batch_shape(int64_t* out3);
 
 /* Diagnostic: which kernel the calling thread's last successful dpf_hip_expand
  * launched ("octet/<leaf>" or "pair/<leaf>", leaf = fast, swar, mod32,
