@@ -205,8 +205,9 @@ def build_tools(force=False):
     (tests/cpp/dcf_expand_api_test.cc), the batched table lookup's
     (tests/cpp/lookup_api_test.cc), the full-domain sum's
     (tests/cpp/full_domain_sum_api_test.cc), the checked full-domain sum's
-    (tests/cpp/full_domain_sketch_api_test.cc) and the batched database
-    fold's (tests/cpp/dot_batch_api_test.cc)."""
+    (tests/cpp/full_domain_sketch_api_test.cc), the batched database
+    fold's (tests/cpp/dot_batch_api_test.cc) and the bucketed database
+    fold's (tests/cpp/dot_buckets_api_test.cc)."""
     hdrs = _files(os.path.join(INCLUDE), (".h",))
     cxx = os.environ.get("CXX", "g++")
     for src, name in ((os.path.join(ROOT, "tools", "dpf_benchmark.cc"), "dpf_benchmark"),
@@ -228,7 +229,9 @@ def build_tools(force=False):
                       (os.path.join(ROOT, "tests", "cpp", "full_domain_sketch_api_test.cc"),
                        "full_domain_sketch_api_test"),
                       (os.path.join(ROOT, "tests", "cpp", "dot_batch_api_test.cc"),
-                       "dot_batch_api_test")):
+                       "dot_batch_api_test"),
+                      (os.path.join(ROOT, "tests", "cpp", "dot_buckets_api_test.cc"),
+                       "dot_buckets_api_test")):
         out = os.path.join(LIBDIR, name)
         if force or _stale(out, [src, os.path.join(LIBDIR, "libdpf.so")] + hdrs):
             _run([cxx, "-O2", "-std=c++20", "-Wall", f"-I{INCLUDE}", src, "-o", out,

@@ -1137,6 +1137,135 @@ StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateLookupBatch(
   return out;
 }
 
+// Multi-query PIR over a bucketed database: the key batch expanded into share
+// rows in one launch (dpf_expand_rows.hip) and the rows folded into every
+// key's own bucket's slice (dpf_dot_buckets.hip).  The host's part is the
+// argument checks, in the order the header gives, the rows' and the fold's
+// room in the device scratch, and the cut into chunks of keys.
+bool DistributedPointFunction::EvaluatesDotBucketsOnDevice(int hierarchy_level) const {
+  if (!CheckLevel(hierarchy_level, parameters().size()).ok()) return false;
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  return dpf_hip_expand_rows_supported(&desc) != 0 && n >= 1 && n <= 24;
+}
+
+Status DistributedPointFunction::CheckDotBucketsArgs(
+    int64_t num_keys, bool batch_matches, int hierarchy_level, Span<const int64_t> bucket_begin,
+    const void* device_db, int64_t db_bytes, int64_t record_words, const void* device_out,
+    int64_t out_bytes) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  if (!dpf_hip_expand_rows_supported(&desc))
+    return UnimplementedError(
+        "the bucketed database fold is implemented for uint64_t and XorWrapper<uint64_t> only");
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  if (n < 1 || n > 24)
+    return InvalidArgumentError("the bucketed database fold takes a log_domain_size in [1, 24]");
+  DPF_RETURN_IF_ERROR(CheckRecordWords(record_words));
+  const int64_t B = static_cast<int64_t>(bucket_begin.size()) - 1;
+  if (B < 1 || B > (int64_t{1} << 20))
+    return InvalidArgumentError("`bucket_begin` must hold between 2 and 2^20 + 1 entries");
+  if (bucket_begin[0] != 0) return InvalidArgumentError("`bucket_begin` must start at 0");
+  for (int64_t b = 0; b < B; ++b)
+    if (bucket_begin[b + 1] < bucket_begin[b])
+      return InvalidArgumentError("`bucket_begin` must be nondecreasing");
+  if (num_keys < 0 || bucket_begin[B] != num_keys)
+    return InvalidArgumentError("`bucket_begin` must end at the number of keys of the batch");
+  if (db_bytes != B * (int64_t{1} << n) * record_words * 8)
+    return InvalidArgumentError(
+        "`db_bytes` must be num_buckets * 2^log_domain_size * record_words * 8");
+  if (!device_db || !device_out)
+    return InvalidArgumentError("`device_db` and `device_out` must not be null");
+  if (out_bytes / (record_words * 8) < num_keys)
+    return InvalidArgumentError("device output buffer too small");
+  if (!batch_matches)
+    return InvalidArgumentError("key batch does not match this DistributedPointFunction");
+  if ((reinterpret_cast<uintptr_t>(device_db) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(device_out) & 7) != 0)
+    return InvalidArgumentError("`device_db` and `device_out` must be aligned to 8 bytes");
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateDotBucketsToDevice(
+    const DeviceKeyBatch& keys, int hierarchy_level, Span<const int64_t> bucket_begin,
+    const void* device_db, int64_t db_bytes, int64_t record_words, void* device_out,
+    int64_t out_bytes, void* stream) const {
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  DPF_RETURN_IF_ERROR(CheckDotBucketsArgs(K, matches, hierarchy_level, bucket_begin, device_db,
+                                          db_bytes, record_words, device_out, out_bytes));
+  if (K == 0) return int64_t{0};
+  const int W = static_cast<int>(record_words);
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  const int depth = hierarchy_to_tree()[hierarchy_level];
+  const int64_t B = static_cast<int64_t>(bucket_begin.size()) - 1;
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  // Chunks of consecutive keys whose share rows fit the dot calls' scratch
+  // bound (n <= 24: at least two keys).
+  const int64_t stride = int64_t{8} << n;   // bytes of a key's share row (n >= 1: 16 | stride)
+  const int64_t chunk =
+      std::min(K, TileHook("DPF_DOT_BUCKETS_CHUNK_KEYS",
+                           static_cast<int>(std::min<int64_t>(
+                               std::max<int64_t>(dpf_internal::kSlabScratchBits / 8 / stride, 1),
+                               std::numeric_limits<int>::max()))));
+  const int64_t fold_bytes = dpf_hip_dot_buckets_workspace_bytes(&desc, W, B, chunk, n);
+  if (fold_bytes < 0) return InvalidArgumentError(dpf_hip_last_error());
+  const int64_t rows_at = (fold_bytes + 255) & ~int64_t{255};
+
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  // The fold's table and the share rows, one after the other in the fenced
+  // workspace: a call on another stream waits for this one's last kernel, and
+  // a chunk follows the one before it in stream order.
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(
+      s->workspace, static_cast<size_t>(rows_at + chunk * stride), stream));
+  char* const ws = static_cast<char*>(s->workspace.get());
+  uint64_t* const rows = reinterpret_cast<uint64_t*>(ws + rows_at);
+  const int64_t cws = keys.num_levels();
+  std::vector<int64_t> begin(static_cast<size_t>(B) + 1);
+  for (int64_t k0 = 0; k0 < K; k0 += chunk) {
+    const int64_t nk = std::min(chunk, K - k0);
+    for (int64_t b = 0; b <= B; ++b)
+      begin[b] = std::min(std::max(bucket_begin[b], k0), k0 + nk) - k0;
+    HIP_RETURN_IF_ERROR(dpf_hip_expand_rows(
+        nk, depth, static_cast<int>(cws), n, keys.seed() + k0, keys.party() + k0,
+        keys.cw_seed() + k0 * cws, keys.cw_left() + k0 * cws, keys.cw_right() + k0 * cws, &kl, &kr,
+        &kv, &desc, keys.value_correction(hierarchy_level) + 2 * k0, rows, stride, stream));
+    HIP_RETURN_IF_ERROR(dpf_hip_dot_buckets(B, n, W, begin.data(), nk, &desc, rows, stride,
+                                            device_db,
+                                            static_cast<uint64_t*>(device_out) + k0 * W, ws,
+                                            fold_bytes, stream));
+  }
+  DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  return K * W;
+}
+
+StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateDotBuckets(
+    const DeviceKeyBatch& keys, int hierarchy_level, Span<const int64_t> bucket_begin,
+    const void* device_db, int64_t db_bytes, int64_t record_words) const {
+  // The device call's checks first, with a stand-in for the buffer this call
+  // makes itself: host errors touch no device.
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  alignas(8) static const uint64_t stand_in = 0;
+  DPF_RETURN_IF_ERROR(CheckDotBucketsArgs(K, matches, hierarchy_level, bucket_begin, device_db,
+                                          db_bytes, record_words, &stand_in,
+                                          std::numeric_limits<int64_t>::max()));
+  std::vector<uint64_t> out(static_cast<size_t>(K * record_words));
+  if (K == 0) return out;
+  dpf_internal::DeviceBuffer d_out;
+  DPF_RETURN_IF_ERROR(d_out.Reserve(out.size() * sizeof(uint64_t)));
+  DPF_RETURN_IF_ERROR(EvaluateDotBucketsToDevice(keys, hierarchy_level, bucket_begin, device_db,
+                                                 db_bytes, record_words, d_out.get(),
+                                                 static_cast<int64_t>(out.size() * 8), nullptr)
+                          .status());
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), d_out.get(), out.size() * 8, nullptr));
+  return out;
+}
+
 // Full-domain sum over a key batch: a table kernel and one fused launch
 // (dpf_expand_sum.hip).  The host's part is the argument checks, in the order
 // the header gives, and the table's room in the device scratch.

@@ -575,6 +575,43 @@ class PyDpf {
                                       table_words, reinterpret_cast<const void*>(out), out_bytes);
     if (!st.ok()) throw StatusError(st);
   }
+  int64_t EvaluateDotBucketsToDevice(const PyDeviceKeyBatch& keys, int level,
+                                     const std::vector<int64_t>& bucket_begin, uintptr_t db,
+                                     int64_t db_bytes, int64_t record_words, uintptr_t out,
+                                     int64_t out_bytes, uintptr_t stream) {
+    return TakeNoGil([&] {
+      return dpf_->EvaluateDotBucketsToDevice(
+          *keys.d, level, MakeConstSpan(bucket_begin), reinterpret_cast<const void*>(db), db_bytes,
+          record_words, reinterpret_cast<void*>(out), out_bytes, reinterpret_cast<void*>(stream));
+    });
+  }
+  py::array_t<uint64_t> EvaluateDotBuckets(const PyDeviceKeyBatch& keys, int level,
+                                           const std::vector<int64_t>& bucket_begin, uintptr_t db,
+                                           int64_t db_bytes, int64_t record_words) {
+    const std::vector<uint64_t> r = TakeNoGil([&] {
+      return dpf_->EvaluateDotBuckets(*keys.d, level, MakeConstSpan(bucket_begin),
+                                      reinterpret_cast<const void*>(db), db_bytes, record_words);
+    });
+    py::array_t<uint64_t> a(static_cast<py::ssize_t>(r.size()));
+    if (!r.empty()) std::memcpy(a.mutable_data(), r.data(), r.size() * 8);
+    return a;
+  }
+  bool EvaluatesDotBucketsOnDevice(int level) const {
+    return dpf_->EvaluatesDotBucketsOnDevice(level);
+  }
+  // The bucketed fold's host checks for a batch of `num_keys` keys (no device,
+  // no batch object needed).
+  void CheckDotBucketsArgs(int64_t num_keys, bool batch_matches, int level,
+                           const std::vector<int64_t>& bucket_begin, uintptr_t db,
+                           int64_t db_bytes, int64_t record_words, uintptr_t out,
+                           int64_t out_bytes) const {
+    Status st = dpf_->CheckDotBucketsArgs(num_keys, batch_matches, level,
+                                          MakeConstSpan(bucket_begin),
+                                          reinterpret_cast<const void*>(db), db_bytes,
+                                          record_words, reinterpret_cast<const void*>(out),
+                                          out_bytes);
+    if (!st.ok()) throw StatusError(st);
+  }
   int64_t EvaluateFullDomainSumToDevice(const PyDeviceKeyBatch& keys, int level, uintptr_t out,
                                         int64_t out_bytes, bool accumulate, uintptr_t stream) {
     return TakeNoGil([&] {
@@ -1033,6 +1070,10 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_lookup_batch", &PyDpf::EvaluateLookupBatch)
       .def("evaluates_lookup_on_device", &PyDpf::EvaluatesLookupOnDevice)
       .def("check_lookup_args", &PyDpf::CheckLookupArgs)
+      .def("evaluate_dot_buckets_to_device", &PyDpf::EvaluateDotBucketsToDevice)
+      .def("evaluate_dot_buckets", &PyDpf::EvaluateDotBuckets)
+      .def("evaluates_dot_buckets_on_device", &PyDpf::EvaluatesDotBucketsOnDevice)
+      .def("check_dot_buckets_args", &PyDpf::CheckDotBucketsArgs)
       .def("evaluate_full_domain_sum_to_device", &PyDpf::EvaluateFullDomainSumToDevice)
       .def("evaluate_full_domain_sum", &PyDpf::EvaluateFullDomainSum)
       .def("evaluates_full_domain_sum_on_device", &PyDpf::EvaluatesFullDomainSumOnDevice)

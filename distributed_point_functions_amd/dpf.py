@@ -564,6 +564,51 @@ class DistributedPointFunction:
               table.numel() * table.element_size(), int(table_words), out.data_ptr(),
               out.numel() * out.element_size())
 
+    def evaluate_dot_buckets_to_device(self, device_batch, hierarchy_level: int, bucket_begin, db,
+                                       record_words: int, out, stream=None) -> int:
+        """Multi-query PIR over a bucketed database: every key of a device batch
+        expanded over its domain (uint64 or XorWrapper<uint64>, N = 2^n
+        elements, n <= 24) and folded into its own bucket's slice of `db` (torch
+        device tensor [B][N][record_words] of uint64, row-major).  Keys
+        bucket_begin[b] .. bucket_begin[b + 1] - 1 belong to bucket b
+        (`bucket_begin`: B + 1 host integers from 0 to K, nondecreasing):
+        out[k][w] = sum_i y_k[i] * db[b(k)][i][w] mod 2^64, or
+        XOR_i (y_k[i] & db[b(k)][i][w]).  Writes K * record_words uint64 into
+        the torch device tensor `out` and returns that count.  The two
+        parties' rows add (XOR) to beta_k * db[b(k)][alpha_k]."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(out.device)
+        return _call(self._impl.evaluate_dot_buckets_to_device, device_batch,
+                     int(hierarchy_level), [int(x) for x in bucket_begin], db.data_ptr(),
+                     db.numel() * db.element_size(), int(record_words), out.data_ptr(),
+                     out.numel() * out.element_size(), s.cuda_stream)
+
+    def evaluate_dot_buckets(self, device_batch, hierarchy_level: int, bucket_begin, db,
+                             record_words: int) -> np.ndarray:
+        """evaluate_dot_buckets_to_device returned as a numpy uint64 array of
+        shape (K, record_words)."""
+        out = _call(self._impl.evaluate_dot_buckets, device_batch, int(hierarchy_level),
+                    [int(x) for x in bucket_begin], db.data_ptr(),
+                    db.numel() * db.element_size(), int(record_words))
+        return out.reshape(-1, int(record_words))
+
+    def evaluates_dot_buckets_on_device(self, hierarchy_level: int) -> bool:
+        """Whether evaluate_dot_buckets_to_device takes this level's value type
+        and domain size (there is no fallback behind it)."""
+        return self._impl.evaluates_dot_buckets_on_device(int(hierarchy_level))
+
+    def check_dot_buckets_args(self, num_keys: int, hierarchy_level: int, bucket_begin, db,
+                               record_words: int, out, batch_matches: bool = True) -> None:
+        """The host checks of evaluate_dot_buckets_to_device for a batch of
+        `num_keys` keys, in its order; raises what it would raise.  Touches no
+        device and needs no batch."""
+        _call(self._impl.check_dot_buckets_args, int(num_keys), bool(batch_matches),
+              int(hierarchy_level), [int(x) for x in bucket_begin], db.data_ptr(),
+              db.numel() * db.element_size(), int(record_words), out.data_ptr(),
+              out.numel() * out.element_size())
+
     def evaluate_full_domain_sum_to_device(self, device_batch, hierarchy_level: int, out,
                                            accumulate: bool = False, stream=None) -> int:
         """Private histogram of a device batch: every key's full-domain

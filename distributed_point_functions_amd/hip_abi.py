@@ -160,6 +160,15 @@ def load(require_gpu: bool = False):
                              [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P]),
                             ("dpf_hip_lookup_plan",
                              [I64, I, I, I, ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_expand_rows_supported", [P]),
+                            ("dpf_hip_expand_rows",
+                             [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I64, P]),
+                            ("dpf_hip_expand_rows_plan",
+                             [I64, I, I, ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_dot_buckets",
+                             [I64, I, I, ctypes.POINTER(ctypes.c_int64), I64, P, P, I64, P, P, P,
+                              I64, P]),
+                            ("dpf_hip_last_dot_buckets_shape", [ctypes.POINTER(ctypes.c_int64)]),
                             ("dpf_hip_expand_sum_supported", [P]),
                             ("dpf_hip_expand_sum",
                              [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I64, P, I, P]),
@@ -181,6 +190,9 @@ def load(require_gpu: bool = False):
         if hasattr(L, "dpf_hip_expand_sum_workspace_bytes"):
             L.dpf_hip_expand_sum_workspace_bytes.argtypes = [I64, I]
             L.dpf_hip_expand_sum_workspace_bytes.restype = ctypes.c_int64
+        if hasattr(L, "dpf_hip_dot_buckets_workspace_bytes"):
+            L.dpf_hip_dot_buckets_workspace_bytes.argtypes = [P, I, I64, I64, I]
+            L.dpf_hip_dot_buckets_workspace_bytes.restype = ctypes.c_int64
         if hasattr(L, "dpf_hip_last_dot_kernel"):
             L.dpf_hip_last_dot_kernel.restype = ctypes.c_char_p
         _lib = L
@@ -213,8 +225,9 @@ def last_points_kernel() -> str:
 
 def last_dot_kernel() -> str:
     """Path of this thread's last dot call: "small", "pair" or "octet" (the
-    fused expand kernel), "rows" (dot_rows), "select" (select_rows) or
-    "rows_batch" (dot_rows_batch) -- dispatch diagnostics for the tests."""
+    fused expand kernel), "rows" (dot_rows), "select" (select_rows),
+    "rows_batch" (dot_rows_batch) or "buckets" (dot_buckets) -- dispatch
+    diagnostics for the tests."""
     return load().dpf_hip_last_dot_kernel().decode()
 
 
@@ -293,6 +306,41 @@ def lookup_supported(desc, table_words: int) -> bool:
     (`desc` None: a NULL descriptor; no GPU needed)."""
     return bool(load().dpf_hip_lookup_supported(ctypes.byref(desc) if desc is not None else None,
                                                 table_words))
+
+
+EXPAND_ROWS_MAX_SUBTREE = 6   # DPF_HIP_EXPAND_ROWS_MAX_SUBTREE
+
+
+def expand_rows_plan(num_keys: int, tree_depth: int, compute_units: int) -> dict:
+    """The launch plan of dpf_hip_expand_rows for that shape (no GPU needed):
+    {"S", "walk", "items_per_key", "items"}."""
+    out = (ctypes.c_int64 * 4)()
+    check(load().dpf_hip_expand_rows_plan(num_keys, tree_depth, compute_units, out))
+    return {"S": out[0], "walk": out[1], "items_per_key": out[2], "items": out[3]}
+
+
+def expand_rows_supported(desc) -> bool:
+    """Whether dpf_hip_expand_rows and dpf_hip_dot_buckets take this value type
+    (`desc` None: a NULL descriptor; no GPU needed)."""
+    return bool(load().dpf_hip_expand_rows_supported(
+        ctypes.byref(desc) if desc is not None else None))
+
+
+def dot_buckets_workspace_bytes(desc, record_words: int, num_buckets: int, num_keys: int,
+                                log_domain_size: int) -> int:
+    """Bytes of dpf_hip_dot_buckets' workspace for those counts (no GPU
+    needed); -1 for arguments out of range or a value type it does not take."""
+    return int(load().dpf_hip_dot_buckets_workspace_bytes(
+        ctypes.byref(desc) if desc is not None else None, record_words, num_buckets, num_keys,
+        log_domain_size))
+
+
+def last_dot_buckets_shape():
+    """(work items, tiles, largest tile, column chunks) of this thread's last
+    dot_buckets that launched -- dispatch diagnostics for the tests."""
+    a = (ctypes.c_int64 * 4)()
+    check(load().dpf_hip_last_dot_buckets_shape(a))
+    return tuple(a)
 
 
 EXPAND_SUM_WAVE_ITEMS_PER_CU = 64   # DPF_HIP_EXPAND_SUM_WAVE_ITEMS_PER_CU
@@ -577,6 +625,54 @@ def dot_rows_batch(num_rows: int, record_words: int, num_queries: int, desc: Val
     check(L.dpf_hip_dot_rows_batch(num_rows, record_words, num_queries, ctypes.byref(desc), _p(y),
                                    y_stride_bytes, _p(db), 1 if accumulate else 0, _p(workspace),
                                    _p(out), _stream(stream)))
+    return out
+
+
+def expand_rows(log_domain_size: int, key_seed, party, cw_seed, cw_left, cw_right, keys,
+                desc: ValueDesc, value_correction, rows=None, row_stride_bytes=None,
+                cw_stride=None, stream=None):
+    """dpf_hip_expand_rows on torch device tensors: key_seed (K, 2) int64, party
+    (K,) uint8, cw_seed (K, cw_stride, 2) int64, cw_left / cw_right (K,
+    cw_stride) uint8, value_correction (2 K, 2) int64, keys = (left, right,
+    value) AES keys as integers.  Returns `rows`: K rows of row_stride_bytes /
+    8 int64 (the bits of uint64; default stride 8 * 2^n), of which the first
+    2^n of every row are written."""
+    import torch
+    L = load(require_gpu=True)
+    K, n = int(key_seed.shape[0]), int(log_domain_size)
+    stride = (8 << n) if row_stride_bytes is None else int(row_stride_bytes)
+    if cw_stride is None:
+        cw_stride = n - 1
+    if rows is None:
+        rows = torch.empty((max(K, 1), stride // 8), dtype=torch.int64, device=key_seed.device)
+    kl, kr, kv = (aes_key(k) for k in keys)
+    check(L.dpf_hip_expand_rows(K, n - 1, int(cw_stride), n, _p(key_seed), _p(party), _p(cw_seed),
+                                _p(cw_left), _p(cw_right), ctypes.byref(kl), ctypes.byref(kr),
+                                ctypes.byref(kv), ctypes.byref(desc), _p(value_correction),
+                                _p(rows), stride, _stream(stream)))
+    return rows
+
+
+def dot_buckets(log_domain_size: int, record_words: int, bucket_begin, desc: ValueDesc, y,
+                y_stride_bytes: int, db, out=None, workspace=None, stream=None):
+    """out[k][w] = fold of row k of `y` (device, 8-byte shares, rows
+    y_stride_bytes apart) into the slice db[b(k)] of `db` (device, [B][2^n]
+    [record_words] uint64), b(k) given by the B + 1 host integers
+    `bucket_begin`: sums mod 2^64 for uint64, XOR of ANDs for
+    XorWrapper<uint64>; returns (K, record_words) as an int64 tensor (the bits
+    of uint64).  The workspace is a fresh tensor unless given."""
+    import torch
+    L = load(require_gpu=True)
+    bb = (ctypes.c_int64 * len(bucket_begin))(*[int(x) for x in bucket_begin])
+    B, K = len(bucket_begin) - 1, int(bucket_begin[-1])
+    if workspace is None:
+        need = dot_buckets_workspace_bytes(desc, record_words, B, K, log_domain_size)
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=db.device)
+    if out is None:
+        out = torch.empty((K, record_words), dtype=torch.int64, device=db.device)
+    check(L.dpf_hip_dot_buckets(B, log_domain_size, record_words, bb, K, ctypes.byref(desc),
+                                _p(y), y_stride_bytes, _p(db), _p(out), _p(workspace),
+                                workspace.numel(), _stream(stream)))
     return out
 
 

@@ -443,6 +443,53 @@ class DistributedPointFunction {
                          const void* device_offsets, const void* device_table,
                          int64_t table_bytes, int64_t table_words, const void* device_out,
                          int64_t out_bytes) const;
+  // Multi-query PIR over a bucketed database (a batch code): every key of a
+  // device batch expanded over its small domain and folded into its own
+  // bucket's slice of the database.  For T = uint64_t or XorWrapper<uint64_t>
+  // at `hierarchy_level` (other value types: UNIMPLEMENTED; there is no
+  // fallback behind this call), n = log_domain_size in [1, 24], N = 2^n,
+  // y_k = EvaluateUntil<T>(hierarchy_level, {}, fresh ctx of key k),
+  // `bucket_begin` a host array of B + 1 entries (bucket_begin[0] = 0,
+  // nondecreasing, bucket_begin[B] = K; keys bucket_begin[b] ..
+  // bucket_begin[b + 1] - 1 belong to bucket b: none, one or many) and
+  // `device_db` a row-major device array [B][N][W] of uint64, W =
+  // record_words in [1, 1024], with b(k) the bucket of key k:
+  //   uint64_t:             out[k][w] = sum_i y_k[i] * db[b(k)][i][w]  (mod 2^64)
+  //   XorWrapper<uint64_t>: out[k][w] = XOR_i (y_k[i] & db[b(k)][i][w]);
+  // row k is what EvaluateDotToDevice gives for key k on slice b(k), and the
+  // two parties' rows combine with T's + to beta_k * db[b(k)][alpha_k]
+  // (beta_k & ...).  Stateless and key-based.  Writes K * W uint64 to
+  // `device_out` on `stream` (asynchronous), whatever it held before, and
+  // returns K * W; K == 0 launches nothing.  The share rows and the fold's
+  // workspace live in this object's device scratch (ReleaseScratch() frees
+  // them); the keys are taken in chunks of consecutive keys whose rows fit
+  // 256 MiB (DPF_DOT_BUCKETS_CHUNK_KEYS=<c>, read per call, sets the chunk:
+  // test hook).  Checked in this order, before the device is touched, the
+  // first failure reported: the level, the value type and its domain size,
+  // record_words, bucket_begin, db_bytes == B * N * W * 8, null pointers,
+  // out_bytes >= K * W * 8, that the batch is this DPF's, and the buffers'
+  // alignment (8 bytes).
+  StatusOr<int64_t> EvaluateDotBucketsToDevice(const DeviceKeyBatch& keys, int hierarchy_level,
+                                               Span<const int64_t> bucket_begin,
+                                               const void* device_db, int64_t db_bytes,
+                                               int64_t record_words, void* device_out,
+                                               int64_t out_bytes, void* stream) const;
+  // The same with the K * W sums returned to the host.
+  StatusOr<std::vector<uint64_t>> EvaluateDotBuckets(const DeviceKeyBatch& keys,
+                                                     int hierarchy_level,
+                                                     Span<const int64_t> bucket_begin,
+                                                     const void* device_db, int64_t db_bytes,
+                                                     int64_t record_words) const;
+  // True when `hierarchy_level` exists and its value type and domain size are
+  // ones EvaluateDotBucketsToDevice takes.
+  bool EvaluatesDotBucketsOnDevice(int hierarchy_level) const;
+  // EvaluateDotBucketsToDevice's argument checks, in its order and with its
+  // messages, for a batch of num_keys keys that is (`batch_matches`) or is not
+  // one of this DistributedPointFunction.  Touches no device.
+  Status CheckDotBucketsArgs(int64_t num_keys, bool batch_matches, int hierarchy_level,
+                             Span<const int64_t> bucket_begin, const void* device_db,
+                             int64_t db_bytes, int64_t record_words, const void* device_out,
+                             int64_t out_bytes) const;
   // Fused full-domain sum over a key batch -- private histograms, private
   // writes: every key of a device batch expanded over its whole domain and
   // summed element by element, without a share vector being stored.  For T =

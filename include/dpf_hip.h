@@ -231,8 +231,9 @@ int dpf_hip_expand_dot_workspace_bytes(const dpf_value_desc* desc, int record_wo
 int dpf_hip_expand_dot_fused(const dpf_value_desc* desc, int record_words);
 /* Diagnostic: the path the calling thread's last dot call took: "small",
  * "pair" or "octet" (dpf_hip_expand_dot, the expand kernel it ran), "rows"
- * (dpf_hip_dot_rows), "select" (dpf_hip_select_rows) or "rows_batch"
- * (dpf_hip_dot_rows_batch); "" before the first call. */
+ * (dpf_hip_dot_rows), "select" (dpf_hip_select_rows), "rows_batch"
+ * (dpf_hip_dot_rows_batch) or "buckets" (dpf_hip_dot_buckets); "" before the
+ * first call. */
 const char* dpf_hip_last_dot_kernel(void);
 
 /* ---- dense PIR: a bit-selected database fold batched over queries ----------
@@ -907,6 +908,103 @@ int dpf_hip_expand_sketch(int64_t num_keys, int num_levels, int cw_stride, int l
  * (walk + 2 (2^S - 1) + nl 2^S) AES.  3 for num_keys outside [1, 2^31 - 1],
  * tree_depth outside [0, 28], num_cus outside [1, 65536]. */
 int dpf_hip_expand_sketch_plan(int64_t num_keys, int tree_depth, int num_cus, int64_t out[6]);
+
+/* ---- multi-query PIR over a bucketed database --------------------------------
+ * No reference counterpart.  Two calls: the stateless full-domain expansion of
+ * every key of a key batch into [key][element] share rows in one launch, and
+ * the fold of those rows in which every key meets its own bucket's slice of a
+ * database [bucket][row][word].
+ *
+ * dpf_hip_expand_rows: with n = log_domain_size in [1, 24], N = 2^n and y_k
+ * the N shares EvaluateUntil gives for key k (uint64_t or
+ * XorWrapper<uint64_t>),
+ *   rows[k * row_stride_bytes / 8 + i] = y_k[i]      for k < num_keys, i < N.
+ * The key batch is passed as dpf_hip_lookup_batch takes it (num_levels the
+ * hierarchy level's tree depth n - 1, cw_stride the key's correction-word
+ * count, value_correction that level's, two blocks per key).  row_stride_bytes
+ * is a multiple of 16 and at least 8 N; the bytes of a row past 8 N are not
+ * written.  The call is asynchronous on `stream`, overwrites the N elements
+ * of every row and reads nothing of what they held before.
+ * Checks, all before any device call, the first failing one reported:
+ *   1. num_keys outside [0, 2^31 - 1], log_domain_size outside [1, 24],
+ *      num_levels != log_domain_size - 1: 3;
+ *   2. NULL desc or AES keys: 3;
+ *   3. a value type other than uint64_t / XorWrapper<uint64_t>: 12
+ *      UNIMPLEMENTED (there is no fallback behind this call);
+ *   4. cw_stride < num_levels: 3;
+ *   5. row_stride_bytes not a multiple of 16 or below 8 N: 3;
+ *   6. num_keys == 0: returns 0, no launch;
+ *   7. NULL key arrays or rows (correction words only when num_levels > 0): 3;
+ *   8. `rows` not aligned to 16 bytes: 3.
+ * The item loop is dynamic as chunked launches are (DPF_EXPAND_ROWS_DYNAMIC=0,
+ * read per launch: a fixed share per thread; A/B and test hook), and
+ * dpf_hip_last_dynamic_chunks reports it. */
+int dpf_hip_expand_rows_supported(const dpf_value_desc* desc);
+int dpf_hip_expand_rows(int64_t num_keys, int num_levels, int cw_stride, int log_domain_size,
+                        const dpf_block* key_seed, const uint8_t* party,
+                        const dpf_block* cw_seed, const uint8_t* cw_left,
+                        const uint8_t* cw_right, const dpf_aes_key* key_left,
+                        const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+                        const dpf_value_desc* desc, const dpf_block* value_correction,
+                        uint64_t* rows, int64_t row_stride_bytes, void* stream);
+/* The launch plan of dpf_hip_expand_rows on a device of num_cus compute units,
+ * a pure function (no device is touched), by dpf_hip_lookup_plan's rule.  A
+ * work item is (key, subtree): it walks `walk` levels from the key's root,
+ * visits S levels depth-first and stores 2^(S+1) elements, tree_depth = walk
+ * + S.  out = {S, walk, items per key = 2^walk, items}.  S is the deepest the
+ * kernel's register stack allows (DPF_HIP_EXPAND_ROWS_MAX_SUBTREE levels),
+ * lowered while the launch has fewer than 256 items per compute unit.  A key
+ * costs 2^walk * (walk + 2 (2^S - 1) + 2^S) AES.  3 for num_keys outside
+ * [1, 2^31 - 1], tree_depth outside [0, 23], num_cus < 1. */
+#define DPF_HIP_EXPAND_ROWS_MAX_SUBTREE 6
+int dpf_hip_expand_rows_plan(int64_t num_keys, int tree_depth, int num_cus, int64_t out[4]);
+
+/* dpf_hip_dot_buckets: the segmented fold.  The num_keys rows of `y` (device,
+ * row k at y + k * y_stride_bytes, N = 2^log_domain_size uint64 shares each)
+ * are grouped by bucket: bucket_begin is a HOST array of num_buckets + 1
+ * entries, read before the call returns, with bucket_begin[0] == 0,
+ * nondecreasing, bucket_begin[num_buckets] == num_keys; keys bucket_begin[b]
+ * .. bucket_begin[b + 1] - 1 belong to bucket b (none, one or many).  `db` is
+ * the device array [num_buckets][N][W] of uint64, W = record_words.  With
+ * b(k) the bucket of key k:
+ *   uint64_t:              out[k*W + w] = sum_{i<N} y_k[i] * db[b(k)][i][w]  (mod 2^64)
+ *   XorWrapper<uint64_t>:  out[k*W + w] = XOR_{i<N} (y_k[i] & db[b(k)][i][w])
+ * Both are exact in any order.  A workgroup takes (bucket, tile of at most 16
+ * of its keys, block of its rows, chunk of 64 columns); an empty bucket's
+ * slice is not read.  The work-item table is built on the host and copied
+ * into `workspace` (device, at least dpf_hip_dot_buckets_workspace_bytes(...)
+ * bytes, untouched until the call's work on `stream` is done) with one
+ * asynchronous copy.  The call is asynchronous on `stream`, overwrites
+ * out[0, K*W) and reads nothing of what `out` or the workspace held before.
+ * Checks, all before any device call, the first failing one reported:
+ *   1. num_buckets outside [1, 2^20], log_domain_size outside [1, 24],
+ *      record_words outside [1, 1024], num_keys outside [0, 2^31 - 1]: 3;
+ *   2. NULL desc: 3;
+ *   3. a value type other than uint64_t / XorWrapper<uint64_t>: 12
+ *      UNIMPLEMENTED (there is no fallback behind this call);
+ *   4. bucket_begin NULL, not starting at 0, decreasing or not ending at
+ *      num_keys: 3;
+ *   5. y_stride_bytes not a multiple of 16 or below 8 N: 3;
+ *   6. num_keys == 0: returns 0, no launch;
+ *   7. NULL y, db or out: 3;
+ *   8. NULL workspace or workspace_bytes too small: 8, the message names the
+ *      size needed;
+ *   9. `y` or `workspace` not aligned to 16 bytes, `db` or `out` not to 8: 3. */
+/* Bytes of the work-item table: 16 per work item, for the most work items a
+ * call of these counts can have.  Monotone in every count; -1 for counts
+ * dpf_hip_dot_buckets rejects or a value type it does not take.  No device is
+ * touched. */
+int64_t dpf_hip_dot_buckets_workspace_bytes(const dpf_value_desc* desc, int record_words,
+                                            int64_t num_buckets, int64_t num_keys,
+                                            int log_domain_size);
+int dpf_hip_dot_buckets(int64_t num_buckets, int log_domain_size, int record_words,
+                        const int64_t* bucket_begin, int64_t num_keys,
+                        const dpf_value_desc* desc, const void* y, int64_t y_stride_bytes,
+                        const void* db, uint64_t* out, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+/* {work items, tiles, largest tile, column chunks} of the calling thread's
+ * last dpf_hip_dot_buckets call that launched (test hook). */
+int dpf_hip_last_dot_buckets_shape(int64_t out[4]);
 
 /* ---- batched multiple-interval-containment gate (eprint 2020/1392 Fig. 14) -
  * MultipleIntervalContainmentGate::Eval (dcf/fss_gates/
