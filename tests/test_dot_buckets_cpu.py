@@ -59,6 +59,18 @@ def _ptr(obj):
 
 
 # ---- dpf_hip_expand_rows ------------------------------------------------------------
+def _stable_id(over):
+    """str(over), with ctypes pointers and arrays named by what they hold, not
+    by their address: the same test id in every process."""
+    def show(v):
+        if isinstance(v, ctypes.c_void_p):
+            return f"base+{v.value - _BASE}"
+        if isinstance(v, ctypes.Array):
+            return f"begin{list(v)}"
+        return repr(v)
+    return "{" + ", ".join(f"{k!r}: {show(v)}" for k, v in over.items()) + "}"
+
+
 def _rows(desc=None, null_desc=False, **over):
     """A call of dpf_hip_expand_rows whose pointers are non-null, 16-byte
     aligned dummies: it must be rejected before anything dereferences them."""
@@ -83,7 +95,7 @@ def _rows(desc=None, null_desc=False, **over):
     dict(key_seed=None), dict(party=None), dict(cw_seed=None), dict(cw_left=None),
     dict(cw_right=None), dict(vcw=None), dict(rows=None),
     dict(rows=ctypes.c_void_p(_BASE + 8)),
-], ids=str)
+], ids=_stable_id)
 def test_expand_rows_argument_errors_are_invalid_argument(over):
     st, msg = _rows(**over)
     assert st == INVALID_ARGUMENT and msg
@@ -220,7 +232,7 @@ def _fold(desc=None, null_desc=False, **over):
     dict(y_stride=(8 << 8) - 16), dict(y_stride=(8 << 8) + 8), dict(y=None), dict(db=None),
     dict(out=None), dict(y=ctypes.c_void_p(_BASE + 8)), dict(workspace=ctypes.c_void_p(_BASE + 8)),
     dict(db=ctypes.c_void_p(_BASE + 4)), dict(out=ctypes.c_void_p(_BASE + 4)),
-], ids=str)
+], ids=_stable_id)
 def test_dot_buckets_argument_errors_are_invalid_argument(over):
     st, msg = _fold(**over)
     assert st == INVALID_ARGUMENT and msg

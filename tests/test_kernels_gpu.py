@@ -162,16 +162,24 @@ GENERIC_TYPES = [
 ]
 
 
-def _expand_case(hip, rng, vt, n0, levels, party, sec=48.0, cepb=None):
+def _expand_case(hip, rng, vt, n0, levels, party, sec=48.0, cepb=None, inputs=None):
+    """`inputs`: the tree ("seeds", "ctrl", "cws", "cl", "cr") and the value
+    corrections ("vcw") of the caller's choosing instead of draws from `rng`."""
     b = (O.bits_needed(vt, sec) + 127) // 128
     E = O.elements_per_block(vt)
     cepb = cepb or E
-    seeds = _rand_blocks(rng, n0)
-    ctrl = rng.integers(0, 2, size=n0, dtype=np.uint8)
-    cws = _rand_blocks(rng, max(levels, 1))
-    cl = rng.integers(0, 2, size=max(levels, 1), dtype=np.uint8)
-    cr = rng.integers(0, 2, size=max(levels, 1), dtype=np.uint8)
-    vcw = [_rand_value(rng, vt) for _ in range(E)]
+    if inputs is not None:
+        seeds, ctrl, cws, cl, cr, vcw = (inputs[k] for k in ("seeds", "ctrl", "cws", "cl", "cr",
+                                                             "vcw"))
+        assert len(seeds) == n0 and len(cws) == len(cl) == len(cr) == max(levels, 1)
+        assert len(vcw) == E
+    else:
+        seeds = _rand_blocks(rng, n0)
+        ctrl = rng.integers(0, 2, size=n0, dtype=np.uint8)
+        cws = _rand_blocks(rng, max(levels, 1))
+        cl = rng.integers(0, 2, size=max(levels, 1), dtype=np.uint8)
+        cr = rng.integers(0, 2, size=max(levels, 1), dtype=np.uint8)
+        vcw = [_rand_value(rng, vt) for _ in range(E)]
     es, ec = O.expand_seeds(seeds, ctrl, cws[:levels], cl[:levels], cr[:levels])
     want = O.hash_correct(vt, es, ec, b, cepb, vcw, party)
     import torch
