@@ -204,7 +204,8 @@ def build_tools(force=False):
     (tests/cpp/keygen_api_test.cc), the full-domain DCF's
     (tests/cpp/dcf_expand_api_test.cc), the batched table lookup's
     (tests/cpp/lookup_api_test.cc), the full-domain sum's
-    (tests/cpp/full_domain_sum_api_test.cc), the checked full-domain sum's
+    (tests/cpp/full_domain_sum_api_test.cc), the packed full-domain sum's
+    (tests/cpp/full_domain_sum_packed_api_test.cc), the checked full-domain sum's
     (tests/cpp/full_domain_sketch_api_test.cc), the batched database
     fold's (tests/cpp/dot_batch_api_test.cc) and the bucketed database
     fold's (tests/cpp/dot_buckets_api_test.cc)."""
@@ -226,6 +227,8 @@ def build_tools(force=False):
                        "lookup_api_test"),
                       (os.path.join(ROOT, "tests", "cpp", "full_domain_sum_api_test.cc"),
                        "full_domain_sum_api_test"),
+                      (os.path.join(ROOT, "tests", "cpp", "full_domain_sum_packed_api_test.cc"),
+                       "full_domain_sum_packed_api_test"),
                       (os.path.join(ROOT, "tests", "cpp", "full_domain_sketch_api_test.cc"),
                        "full_domain_sketch_api_test"),
                       (os.path.join(ROOT, "tests", "cpp", "dot_batch_api_test.cc"),

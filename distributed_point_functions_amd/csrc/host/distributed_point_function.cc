@@ -1346,6 +1346,103 @@ StatusOr<std::vector<uint64_t>> DistributedPointFunction::EvaluateFullDomainSum(
   return out;
 }
 
+// The full-domain sum over packed elements of every width that fills a leaf
+// block (dpf_hip_expand_sum_packed): the checks in EvaluateFullDomainSumToDevice's
+// order, the shape refusals with the type's, and the same scratch and fence.
+namespace {
+constexpr char kPackedSumTypeMessage[] =
+    "the packed full-domain sum is implemented for uint8_t, uint16_t, uint32_t, uint64_t and "
+    "XorWrapper of these and of absl::uint128, at a tree level that gives a domain of at least "
+    "one full leaf block (log_domain_size <= 30, at most 29 tree levels)";
+}  // namespace
+
+bool DistributedPointFunction::EvaluatesFullDomainSumPackedOnDevice(int hierarchy_level) const {
+  if (!CheckLevel(hierarchy_level, parameters().size()).ok()) return false;
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  if (!dpf_hip_expand_sum_packed_supported(&desc)) return false;
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  const int depth = hierarchy_to_tree()[hierarchy_level];
+  // Full leaf blocks: 2^depth blocks of E elements are the 2^n outputs.
+  return n <= 30 && depth >= 0 && depth <= 29 &&
+         (int64_t{desc.elements_per_block} << depth) == (int64_t{1} << n);
+}
+
+Status DistributedPointFunction::CheckFullDomainSumPackedArgs(int64_t num_keys,
+                                                              bool batch_matches,
+                                                              int hierarchy_level,
+                                                              const void* device_out,
+                                                              int64_t out_bytes) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
+  if (!EvaluatesFullDomainSumPackedOnDevice(hierarchy_level))
+    return UnimplementedError(kPackedSumTypeMessage);
+  if (!device_out) return InvalidArgumentError("`device_out` must not be null");
+  const int depth = hierarchy_to_tree()[hierarchy_level];
+  if (num_keys < 0 || out_bytes < (int64_t{16} << depth))
+    return InvalidArgumentError("device output buffer too small");
+  if (!batch_matches)
+    return InvalidArgumentError("key batch does not match this DistributedPointFunction");
+  if ((reinterpret_cast<uintptr_t>(device_out) & 15) != 0)
+    return InvalidArgumentError("`device_out` must be aligned to 16 bytes");
+  return OkStatus();
+}
+
+StatusOr<int64_t> DistributedPointFunction::EvaluateFullDomainSumPackedToDevice(
+    const DeviceKeyBatch& keys, int hierarchy_level, void* device_out, int64_t out_bytes,
+    bool accumulate, void* stream) const {
+  const int64_t K = keys.num_keys();
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  DPF_RETURN_IF_ERROR(
+      CheckFullDomainSumPackedArgs(K, matches, hierarchy_level, device_out, out_bytes));
+  const int n = parameters()[hierarchy_level].log_domain_size();
+  const int depth = hierarchy_to_tree()[hierarchy_level];
+  const dpf_value_desc desc = MakeDesc(flat_[hierarchy_level], blocks_needed_[hierarchy_level]);
+  const dpf_aes_key kl = AesKey(kPrgKeyLeft), kr = AesKey(kPrgKeyRight), kv = AesKey(kPrgKeyValue);
+  auto* s = scratch_.get();
+  std::lock_guard<std::recursive_mutex> scratch_lock(s->mu);  // one call at a time per object
+  const int64_t workspace_bytes = dpf_hip_expand_sum_workspace_bytes(K, depth);
+  if (workspace_bytes < 0) return InvalidArgumentError("key batch too large for the full-domain sum");
+  if (K > 0)
+    DPF_RETURN_IF_ERROR(s->workspace_fence.Acquire(s->workspace,
+                                                   static_cast<size_t>(workspace_bytes), stream));
+  HIP_RETURN_IF_ERROR(dpf_hip_expand_sum_packed(
+      K, depth, keys.num_levels(), n, keys.seed(), keys.party(), keys.cw_seed(), keys.cw_left(),
+      keys.cw_right(), &kl, &kr, &kv, &desc, keys.value_correction(hierarchy_level),
+      K > 0 ? s->workspace.get() : nullptr, workspace_bytes, device_out, out_bytes,
+      accumulate ? 1 : 0, stream));
+  if (K > 0) DPF_RETURN_IF_ERROR(s->workspace_fence.Mark(stream));
+  return int64_t{1} << n;
+}
+
+StatusOr<std::vector<uint8_t>> DistributedPointFunction::EvaluateFullDomainSumPackedBytes(
+    const DeviceKeyBatch& keys, int hierarchy_level, const ValueType* requested_type) const {
+  DPF_RETURN_IF_ERROR(CheckLevel(hierarchy_level, parameters().size()));
+  if (requested_type) {
+    DPF_ASSIGN_OR_RETURN(bool eq, dpf_internal::ValueTypesAreEqual(
+                                      *requested_type, parameters()[hierarchy_level].value_type()));
+    if (!eq) return InvalidArgumentError("Value type T doesn't match parameters at `hierarchy_level`");
+  }
+  // The device call's checks first, with a stand-in for the buffer this call
+  // makes itself: host errors touch no device.
+  const bool matches = keys.num_levels() == tree_levels_needed() - 1 &&
+                       keys.num_hierarchy_levels() == static_cast<int>(parameters().size());
+  alignas(16) static const uint64_t stand_in[2] = {0, 0};
+  DPF_RETURN_IF_ERROR(CheckFullDomainSumPackedArgs(keys.num_keys(), matches, hierarchy_level,
+                                                   stand_in,
+                                                   std::numeric_limits<int64_t>::max()));
+  const size_t bytes = size_t{16} << hierarchy_to_tree()[hierarchy_level];
+  std::vector<uint8_t> out(bytes);
+  if (keys.num_keys() == 0) return out;   // the empty sum
+  dpf_internal::DeviceBuffer d_out;
+  DPF_RETURN_IF_ERROR(d_out.Reserve(bytes));
+  DPF_RETURN_IF_ERROR(EvaluateFullDomainSumPackedToDevice(keys, hierarchy_level, d_out.get(),
+                                                          static_cast<int64_t>(bytes), false,
+                                                          nullptr)
+                          .status());
+  HIP_RETURN_IF_ERROR(dpf_hip_memcpy_d2h(out.data(), d_out.get(), bytes, nullptr));
+  return out;
+}
+
 // Checked private histograms: the field sum of a key batch's full domain with
 // every key's sketches, one fused launch between a table and a finish kernel
 // (dpf_expand_sketch.hip).  The host's part is the argument checks, in the

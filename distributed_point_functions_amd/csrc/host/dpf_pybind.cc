@@ -638,6 +638,34 @@ class PyDpf {
                                              reinterpret_cast<const void*>(out), out_bytes);
     if (!st.ok()) throw StatusError(st);
   }
+  int64_t EvaluateFullDomainSumPackedToDevice(const PyDeviceKeyBatch& keys, int level,
+                                              uintptr_t out, int64_t out_bytes, bool accumulate,
+                                              uintptr_t stream) {
+    return TakeNoGil([&] {
+      return dpf_->EvaluateFullDomainSumPackedToDevice(*keys.d, level,
+                                                       reinterpret_cast<void*>(out), out_bytes,
+                                                       accumulate, reinterpret_cast<void*>(stream));
+    });
+  }
+  // The N packed elements as bytes; dpf.py views them by the level's width.
+  py::array_t<uint8_t> EvaluateFullDomainSumPacked(const PyDeviceKeyBatch& keys, int level) {
+    const std::vector<uint8_t> r = TakeNoGil(
+        [&] { return dpf_->EvaluateFullDomainSumPackedBytes(*keys.d, level, nullptr); });
+    py::array_t<uint8_t> a(static_cast<py::ssize_t>(r.size()));
+    if (!r.empty()) std::memcpy(a.mutable_data(), r.data(), r.size());
+    return a;
+  }
+  bool EvaluatesFullDomainSumPackedOnDevice(int level) const {
+    return dpf_->EvaluatesFullDomainSumPackedOnDevice(level);
+  }
+  // The packed full-domain sum's host checks for a batch of `num_keys` keys
+  // (no device, no batch object needed).
+  void CheckFullDomainSumPackedArgs(int64_t num_keys, bool batch_matches, int level,
+                                    uintptr_t out, int64_t out_bytes) const {
+    Status st = dpf_->CheckFullDomainSumPackedArgs(num_keys, batch_matches, level,
+                                                   reinterpret_cast<const void*>(out), out_bytes);
+    if (!st.ok()) throw StatusError(st);
+  }
   int64_t EvaluateFullDomainSumSketchToDevice(int level, const PyDeviceKeyBatch& keys,
                                               uintptr_t weights, int num_weight_rows,
                                               uintptr_t sum, int64_t sum_bytes, uintptr_t sketch,
@@ -1078,6 +1106,12 @@ PYBIND11_MODULE(_dpf_host, m) {
       .def("evaluate_full_domain_sum", &PyDpf::EvaluateFullDomainSum)
       .def("evaluates_full_domain_sum_on_device", &PyDpf::EvaluatesFullDomainSumOnDevice)
       .def("check_full_domain_sum_args", &PyDpf::CheckFullDomainSumArgs)
+      .def("evaluate_full_domain_sum_packed_to_device",
+           &PyDpf::EvaluateFullDomainSumPackedToDevice)
+      .def("evaluate_full_domain_sum_packed", &PyDpf::EvaluateFullDomainSumPacked)
+      .def("evaluates_full_domain_sum_packed_on_device",
+           &PyDpf::EvaluatesFullDomainSumPackedOnDevice)
+      .def("check_full_domain_sum_packed_args", &PyDpf::CheckFullDomainSumPackedArgs)
       .def("evaluate_full_domain_sum_sketch_to_device",
            &PyDpf::EvaluateFullDomainSumSketchToDevice)
       .def("evaluate_full_domain_sum_sketch", &PyDpf::EvaluateFullDomainSumSketch)

@@ -1,9 +1,14 @@
 // dpf_expand_sum.hip -- fused full-domain sum over a key batch on gfx950: the
 // private histogram,
-//   out[i] = sum_{k<K} y_k[i]  (uint64_t, mod 2^64)
-//   out[i] = XOR_{k<K} y_k[i]  (XorWrapper<uint64_t>)          for i in [0, 2^n)
+//   out[i] = sum_{k<K} y_k[i]  (uintB_t, mod 2^B, B in {8, 16, 32, 64})
+//   out[i] = XOR_{k<K} y_k[i]  (XorWrapper<uintB_t>, B up to 128)  for i in [0, 2^n)
 // with y_k the 2^n shares EvaluateUntil gives for key k.  Every key's tree is
-// expanded once and no share vector is stored.
+// expanded once and no share vector is stored.  A leaf block is E = 128 / B
+// packed elements and, whatever B, two 64-bit words of `out`: the walk, the
+// stack and the plan see only the tree (depth n - log2 E), and the width
+// enters in the correction (FastIntLeaf<B>), in the element-wise word sum of
+// the reduction (word_add) and in the atomics (add_into).  XOR of words is XOR
+// of their packed elements: every XOR width runs the 64-bit instance.
 //
 // Lanes are keys.  A wave is 64 consecutive keys (a key chunk) at one
 // wave-uniform tree position; a work item is (key chunk, subtree): the wave
@@ -15,8 +20,9 @@
 // finished as leaf groups of kSumGroup levels kept in registers (pairs: 2
 // leaf blocks, 4 outputs -- octets and quads spill, see kSumGroup); the 64
 // keys' outputs of a group are reduced by a halving butterfly across the lanes
-// (reduce_lanes) and 4 lanes issue one 64-bit atomic each into one 32-byte
-// sector of `out`.
+// (reduce_lanes) and 4 lanes issue one 64-bit atomic each (two 32-bit ones,
+// or a compare-exchange loop below 32 bits: add_into) into one 32-byte sector
+// of `out`.
 //
 // The correction words come from a [level][key] table that
 // expand_sum_table_kernel transposes out of the batch's [key][level] rows for
@@ -91,17 +97,19 @@ struct SumParams {
   int walk, S;
   const dpf_block* key_seed;
   const uint4* cs;          // [D][kp]
-  const uint4* vcw;         // [kp]: the value correction's two elements
+  const uint4* vcw;         // [kp]: the value correction's E packed elements
   const uint32_t* cc;       // [D][kp]: cw_ctrl2
   const uint32_t* party;    // [kp]
-  uint64_t* out;            // [2^n]
+  uint64_t* out;            // [2^(D + 1)] words: 2^n packed elements
   RoundKeys rkl, rkr, rkv, rkd;
   int64_t dyn_per_wg;  // ItemLoop's per_wg (0: grid stride)
 };
 
 // Column kk of the table is key min(kk, K - 1): the lanes past the last key of
-// a partly filled chunk read a valid key.
-__global__ void expand_sum_table_kernel(int64_t K, int64_t kp, int D, int cw_stride,
+// a partly filled chunk read a valid key.  A key's E = 128 / bits value
+// correction elements (one dpf_block each, key-major) are packed into one
+// block, element e at bit e * bits: FastIntLeaf::init's layout.
+__global__ void expand_sum_table_kernel(int64_t K, int64_t kp, int D, int cw_stride, int bits,
                                         const dpf_block* cw_seed, const uint8_t* cw_left,
                                         const uint8_t* cw_right, const dpf_block* vcw_in,
                                         const uint8_t* party_in, uint4* cs, uint4* vcw,
@@ -116,7 +124,20 @@ __global__ void expand_sum_table_kernel(int64_t K, int64_t kp, int D, int cw_str
       cs[i] = cw_u4(cw_seed[r]);
       cc[i] = cw_ctrl2(cw_left, cw_right, r);
     } else {
-      const uint64_t c0 = vcw_in[2 * k].low, c1 = vcw_in[2 * k + 1].low;
+      uint64_t c0, c1;
+      if (bits == 128) {
+        c0 = vcw_in[k].low;
+        c1 = vcw_in[k].high;
+      } else {
+        const int per = 64 / bits;   // elements of a word
+        const uint64_t mask = bits == 64 ? ~(uint64_t)0 : ((uint64_t)1 << bits) - 1;
+        const dpf_block* in = vcw_in + k * (2 * per);
+        c0 = c1 = 0;
+        for (int e = 0; e < per; ++e) {
+          c0 |= (in[e].low & mask) << (e * bits);
+          c1 |= (in[per + e].low & mask) << (e * bits);
+        }
+      }
       vcw[kk] = make_uint4((uint32_t)c0, (uint32_t)(c0 >> 32), (uint32_t)c1, (uint32_t)(c1 >> 32));
       party[kk] = party_in[k] & 1u;
     }
@@ -137,8 +158,8 @@ struct SumCws {
 
 // The leaf group under `node` (L levels, at tree level `level`), depth-first in
 // registers: its 2^L leaf blocks' corrected elements into v[BASE, BASE + 2^(L+1)).
-template <bool XOR, int L, int BASE, int NV>
-__device__ __forceinline__ void sum_group(const LdsLookup& lk, const FastIntLeaf<64, XOR>& leaf,
+template <int BITS, bool XOR, int L, int BASE, int NV>
+__device__ __forceinline__ void sum_group(const LdsLookup& lk, const FastIntLeaf<BITS, XOR>& leaf,
                                           const SumCws& cws, Block4 node, uint32_t nt, int level,
                                           uint64_t (&v)[NV]) {
   if constexpr (L == 0) {
@@ -160,9 +181,25 @@ __device__ __forceinline__ void sum_group(const LdsLookup& lk, const FastIntLeaf
       v[BASE + 2] = ((uint64_t)b.w1 << 32) | b.w0;
       v[BASE + 3] = ((uint64_t)b.w3 << 32) | b.w2;
     } else {
-      sum_group<XOR, L - 1, BASE, NV>(lk, leaf, cws, c0, t0, level + 1, v);
-      sum_group<XOR, L - 1, BASE + (1 << L), NV>(lk, leaf, cws, c1, t1, level + 1, v);
+      sum_group<BITS, XOR, L - 1, BASE, NV>(lk, leaf, cws, c0, t0, level + 1, v);
+      sum_group<BITS, XOR, L - 1, BASE + (1 << L), NV>(lk, leaf, cws, c1, t1, level + 1, v);
     }
+  }
+}
+
+// Element-wise sum mod 2^BITS of two words of 64 / BITS packed elements.  Below
+// 32 bits the elements' top bits H are added apart from the rest, so that no
+// carry crosses an element's top (lanes_add's form, on a word).
+template <int BITS>
+__device__ __forceinline__ uint64_t word_add(uint64_t a, uint64_t b) {
+  if constexpr (BITS == 64) {
+    return a + b;
+  } else if constexpr (BITS == 32) {
+    const uint32_t lo = (uint32_t)a + (uint32_t)b, hi = (uint32_t)(a >> 32) + (uint32_t)(b >> 32);
+    return ((uint64_t)hi << 32) | lo;
+  } else {
+    constexpr uint64_t H = BITS == 16 ? 0x8000800080008000ull : 0x8080808080808080ull;
+    return ((a & ~H) + (b & ~H)) ^ ((a ^ b) & H);
   }
 }
 
@@ -174,7 +211,7 @@ __device__ __forceinline__ void sum_group(const LdsLookup& lk, const FastIntLeaf
 // 64-key total of output lane >> (6 - H): 2^H - 1 + 6 - H sums (7 for a
 // pair's 4 values, whose output o sits in lanes 16 o .. 16 o + 15; 17 for an
 // octet's 16, output o in lanes 4 o .. 4 o + 3).
-template <bool XOR, int NV>
+template <int BITS, bool XOR, int NV>
 __device__ __forceinline__ uint64_t reduce_lanes(uint64_t (&v)[NV], int lane) {
   constexpr int H = NV == 16 ? 4 : (NV == 8 ? 3 : (NV == 4 ? 2 : 1));
 #pragma unroll
@@ -187,21 +224,61 @@ __device__ __forceinline__ uint64_t reduce_lanes(uint64_t (&v)[NV], int lane) {
         const uint64_t send = up ? v[i] : v[i + half];
         const uint64_t keep = up ? v[i + half] : v[i];
         const uint64_t got = __shfl_xor(send, off, 64);
-        v[i] = XOR ? keep ^ got : keep + got;
+        v[i] = XOR ? keep ^ got : word_add<BITS>(keep, got);
       }
     }
   }
 #pragma unroll
   for (int off = 32 >> H; off > 0; off >>= 1) {
     const uint64_t got = __shfl_xor(v[0], off, 64);
-    v[0] = XOR ? v[0] ^ got : v[0] + got;
+    v[0] = XOR ? v[0] ^ got : word_add<BITS>(v[0], got);
   }
   return v[0];
 }
 
-// LG: the levels of a leaf group, kSumGroup or the whole of a shallower tree.
-template <bool XOR, int LG>
+// A word's total into `out`.  Both groups are exact in any order.  64 bits and
+// XOR: one atomic; 32 bits: one native add per element.  Below that there is
+// no packed atomic add and a plain add would carry into the neighbour: a
+// compare-exchange loop on the word.  It waits on no other wave (an exchange
+// fails only because another one succeeded), so it ends under any schedule.
+template <int BITS, bool XOR>
+__device__ __forceinline__ void add_into(uint64_t* out, uint64_t total) {
+  unsigned long long* q = reinterpret_cast<unsigned long long*>(out);
+  if constexpr (XOR) {
+    __hip_atomic_fetch_xor(q, (unsigned long long)total, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+  } else if constexpr (BITS == 64) {
+    __hip_atomic_fetch_add(q, (unsigned long long)total, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+  } else if constexpr (BITS == 32) {
+    uint32_t* q32 = reinterpret_cast<uint32_t*>(out);
+    __hip_atomic_fetch_add(q32, (uint32_t)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(q32 + 1, (uint32_t)(total >> 32), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    unsigned long long seen = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (!__hip_atomic_compare_exchange_weak(q, &seen,
+                                               (unsigned long long)word_add<BITS>(seen, total),
+                                               __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT)) {
+    }
+  }
+}
+
+// The kernel of every width.  SHAPE is sum_shape(bits, LG): the levels LG of a
+// leaf group (kSumGroup, or the whole of a shallower tree) with the additive
+// element's bits 8, 16 or 32 above them, and nothing there for 64 bits and for
+// XOR (which is blind to the element width: one instance runs every XOR
+// type).  So the 64-bit instances have the template arguments, the symbols and
+// the code they had when the kernel took 64 bits alone
+// (profiles/r35/kernel_digest_compare.txt).
+constexpr int sum_shape(int bits, int lg) { return lg | ((bits == 64 ? 0 : bits) << 8); }
+
+template <bool XOR, int SHAPE>
 __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_sum_kernel(SumParams p) {
+  constexpr int LG = SHAPE & 255;
+  constexpr int BITS = (SHAPE >> 8) == 0 ? 64 : (SHAPE >> 8);
+  static_assert(BITS == 64 || (!XOR && (BITS == 8 || BITS == 16 || BITS == 32)), "element width");
   __shared__ LdsImage lds;
   __shared__ int next_chunk;   // ItemLoop (dpf_device.h)
   fill_tables(lds.tab);
@@ -230,7 +307,7 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_sum_kernel(SumPa
     const int64_t kk = (int64_t)chunk * 64 + lane;
     const bool live = kk < p.num_keys;
     const SumCws cws{p.cs, p.cc, p.kp, kk};
-    FastIntLeaf<64, XOR> leaf;
+    FastIntLeaf<BITS, XOR> leaf;
     const uint32_t party = p.party[kk];
     leaf.party = (int)party;
     {
@@ -278,21 +355,15 @@ __global__ __launch_bounds__(kBlock) DPF_WAVES_ATTR void expand_sum_kernel(SumPa
       }
       // 3. the leaf group, its reduction over the 64 keys, and the atomics.
       uint64_t v[NV];
-      sum_group<XOR, LG, 0, NV>(lk, leaf, cws, node, nt, walk + G, v);
+      sum_group<BITS, XOR, LG, 0, NV>(lk, leaf, cws, node, nt, walk + G, v);
       if (!live) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) v[i] = 0;
       }
-      const uint64_t total = reduce_lanes<XOR, NV>(v, lane);
+      const uint64_t total = reduce_lanes<BITS, XOR, NV>(v, lane);
       if ((lane & ((1 << OSHIFT) - 1)) == 0) {
         const int64_t group = ((int64_t)j << G) | (int64_t)((uint32_t)g ^ rot);
-        unsigned long long* q = reinterpret_cast<unsigned long long*>(
-            p.out + (group << (LG + 1)) + (lane >> OSHIFT));
-        // Both groups are exact in any order.
-        if (XOR) __hip_atomic_fetch_xor(q, (unsigned long long)total, __ATOMIC_RELAXED,
-                                        __HIP_MEMORY_SCOPE_AGENT);
-        else __hip_atomic_fetch_add(q, (unsigned long long)total, __ATOMIC_RELAXED,
-                                    __HIP_MEMORY_SCOPE_AGENT);
+        add_into<BITS, XOR>(p.out + (group << (LG + 1)) + (lane >> OSHIFT), total);
       }
     }
   }
@@ -304,11 +375,100 @@ bool sum_type_ok(const dpf_value_desc* d) {
   return d->kind[0] == DPF_LEAF_INT || d->kind[0] == DPF_LEAF_XOR;
 }
 
-template <bool XOR>
+// The packed call's types: one unsigned integer leaf of 8 to 64 bits, or
+// XorWrapper of one of 8 to 128 bits, E = 128 / bits elements to a block.
+bool packed_type_ok(const dpf_value_desc* d) {
+  if (!d || d->num_leaves != 1 || !fast_int(d)) return false;
+  const int bits = d->bits[0];
+  if (bits != 8 && bits != 16 && bits != 32 && bits != 64 && bits != 128) return false;
+  if (d->elements_per_block != 128 / bits) return false;
+  if (d->kind[0] == DPF_LEAF_XOR) return true;
+  return d->kind[0] == DPF_LEAF_INT && bits != 128;
+}
+
+int log2_elements(int bits) {
+  int l = 0;
+  while ((128 / bits) >> (l + 1)) ++l;
+  return l;
+}
+
+template <bool XOR, int BITS>
 void launch_sum(const SumParams& p, int group, dim3 grid, dim3 block, hipStream_t s) {
   static_assert(kSumGroup == 1, "one instance per leaf-group depth up to kSumGroup");
-  if (group == 0) hipLaunchKernelGGL((expand_sum_kernel<XOR, 0>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((expand_sum_kernel<XOR, 1>), grid, block, 0, s, p);
+  if (group == 0)
+    hipLaunchKernelGGL((expand_sum_kernel<XOR, sum_shape(BITS, 0)>), grid, block, 0, s, p);
+  else
+    hipLaunchKernelGGL((expand_sum_kernel<XOR, sum_shape(BITS, 1)>), grid, block, 0, s, p);
+}
+
+// Both entry points from the empty batch on (their checks 6 to 9 and the two
+// launches): a tree of D levels over blocks of 128 / bits elements, `out` of
+// 16 * 2^D bytes.
+int run_sum(int64_t num_keys, int D, int cw_stride, int bits, bool is_xor,
+            const dpf_block* key_seed, const uint8_t* party, const dpf_block* cw_seed,
+            const uint8_t* cw_left, const uint8_t* cw_right, const dpf_aes_key* key_left,
+            const dpf_aes_key* key_right, const dpf_aes_key* key_value,
+            const dpf_block* value_correction, void* workspace, int64_t workspace_bytes,
+            void* out, int accumulate, hipStream_t s) {
+  const size_t out_bytes = (size_t)16 << D;
+  if (num_keys == 0) {
+    // The empty sum.
+    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s));
+    return kOk;
+  }
+  if (!key_seed || !party || !value_correction || (D > 0 && (!cw_seed || !cw_left || !cw_right)))
+    return fail(kInvalidArgument, "NULL pointer");
+  const int64_t need = table_bytes(num_keys, D);
+  if (!workspace || workspace_bytes < need)
+    return fail(kResourceExhausted, "the full-domain sum needs a workspace of " +
+                                        std::to_string((long long)need) + " bytes");
+  if (((uintptr_t)out & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
+    return fail(kInvalidArgument, "`out` and `workspace` must be aligned to 16 bytes");
+  const SumPlan pl = plan_sum(num_keys, D, num_cus());
+  SumParams p;
+  memset(&p, 0, sizeof(p));
+  p.num_keys = num_keys;
+  p.kp = padded_keys(num_keys);
+  p.wave_items = pl.wave_items;
+  p.walk = pl.walk;
+  p.S = pl.S;
+  p.key_seed = key_seed;
+  char* ws = static_cast<char*>(workspace);
+  uint4* cs = reinterpret_cast<uint4*>(ws);
+  uint4* vcw = cs + (int64_t)D * p.kp;
+  uint32_t* cc = reinterpret_cast<uint32_t*>(vcw + p.kp);
+  uint32_t* pty = cc + (int64_t)D * p.kp;
+  p.cs = cs;
+  p.vcw = vcw;
+  p.cc = cc;
+  p.party = pty;
+  p.out = static_cast<uint64_t*>(out);
+  const RoundKeys rkr = expand_key(key_right);
+  p.rkl = expand_key(key_left);
+  p.rkr = rkr;
+  p.rkv = expand_key(key_value);
+  p.rkd = xor_keys(p.rkl, rkr);
+  {
+    const int64_t n = p.kp * (D + 1);
+    int64_t g = (n + 255) / 256;
+    const int64_t cap = (int64_t)num_cus() * 8;
+    if (g > cap) g = cap;
+    hipLaunchKernelGGL(expand_sum_table_kernel, dim3((unsigned)g), dim3(256), 0, s, num_keys, p.kp,
+                       D, cw_stride, bits, cw_seed, cw_left, cw_right, value_correction, party, cs,
+                       vcw, cc, pty);
+    HIP_TRY(hipGetLastError());
+  }
+  if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s));
+  const LaunchShape sh = chunked_shape(pl.wave_items * 64, "DPF_EXPAND_SUM_DYNAMIC");
+  p.dyn_per_wg = sh.dyn_per_wg;
+  const dim3 grid(sh.grid), block(sh.block);
+  if (is_xor) launch_sum<true, 64>(p, pl.group, grid, block, s);
+  else if (bits == 64) launch_sum<false, 64>(p, pl.group, grid, block, s);
+  else if (bits == 32) launch_sum<false, 32>(p, pl.group, grid, block, s);
+  else if (bits == 16) launch_sum<false, 16>(p, pl.group, grid, block, s);
+  else launch_sum<false, 8>(p, pl.group, grid, block, s);
+  HIP_TRY(hipGetLastError());
+  return kOk;
 }
 
 }  // namespace
@@ -362,62 +522,49 @@ extern "C" int dpf_hip_expand_sum(int64_t num_keys, int num_levels, int cw_strid
                 "the full-domain sum is implemented for uint64_t and XorWrapper<uint64_t> only");
   if (cw_stride < num_levels) return fail(kInvalidArgument, "cw_stride < num_levels");
   if (!out) return fail(kInvalidArgument, "`out` is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t out_bytes = ((size_t)1 << log_domain_size) * sizeof(uint64_t);
-  if (num_keys == 0) {
-    // The empty sum.
-    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s));
-    return kOk;
-  }
-  if (!key_seed || !party || !value_correction ||
-      (num_levels > 0 && (!cw_seed || !cw_left || !cw_right)))
-    return fail(kInvalidArgument, "NULL pointer");
-  const int64_t need = table_bytes(num_keys, num_levels);
-  if (!workspace || workspace_bytes < need)
-    return fail(kResourceExhausted, "the full-domain sum needs a workspace of " +
-                                        std::to_string((long long)need) + " bytes");
-  if (((uintptr_t)out & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
-    return fail(kInvalidArgument, "`out` and `workspace` must be aligned to 16 bytes");
-  const int D = num_levels;
-  const SumPlan pl = plan_sum(num_keys, D, num_cus());
-  SumParams p;
-  memset(&p, 0, sizeof(p));
-  p.num_keys = num_keys;
-  p.kp = padded_keys(num_keys);
-  p.wave_items = pl.wave_items;
-  p.walk = pl.walk;
-  p.S = pl.S;
-  p.key_seed = key_seed;
-  char* ws = static_cast<char*>(workspace);
-  uint4* cs = reinterpret_cast<uint4*>(ws);
-  uint4* vcw = cs + (int64_t)D * p.kp;
-  uint32_t* cc = reinterpret_cast<uint32_t*>(vcw + p.kp);
-  uint32_t* pty = cc + (int64_t)D * p.kp;
-  p.cs = cs;
-  p.vcw = vcw;
-  p.cc = cc;
-  p.party = pty;
-  p.out = out;
-  const RoundKeys rkr = expand_key(key_right);
-  p.rkl = expand_key(key_left);
-  p.rkr = rkr;
-  p.rkv = expand_key(key_value);
-  p.rkd = xor_keys(p.rkl, rkr);
-  {
-    const int64_t n = p.kp * (D + 1);
-    int64_t g = (n + 255) / 256;
-    const int64_t cap = (int64_t)num_cus() * 8;
-    if (g > cap) g = cap;
-    hipLaunchKernelGGL(expand_sum_table_kernel, dim3((unsigned)g), dim3(256), 0, s, num_keys, p.kp,
-                       D, cw_stride, cw_seed, cw_left, cw_right, value_correction, party, cs, vcw,
-                       cc, pty);
-    HIP_TRY(hipGetLastError());
-  }
-  if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s));
-  const LaunchShape sh = chunked_shape(pl.wave_items * 64, "DPF_EXPAND_SUM_DYNAMIC");
-  p.dyn_per_wg = sh.dyn_per_wg;
-  if (desc->kind[0] == DPF_LEAF_XOR) launch_sum<true>(p, pl.group, dim3(sh.grid), dim3(sh.block), s);
-  else launch_sum<false>(p, pl.group, dim3(sh.grid), dim3(sh.block), s);
-  HIP_TRY(hipGetLastError());
-  return kOk;
+  return run_sum(num_keys, num_levels, cw_stride, 64, desc->kind[0] == DPF_LEAF_XOR, key_seed,
+                 party, cw_seed, cw_left, cw_right, key_left, key_right, key_value,
+                 value_correction, workspace, workspace_bytes, out, accumulate,
+                 (hipStream_t)stream);
+}
+
+extern "C" int dpf_hip_expand_sum_packed_supported(const dpf_value_desc* desc) {
+  return packed_type_ok(desc) ? 1 : 0;
+}
+
+extern "C" int dpf_hip_expand_sum_packed(int64_t num_keys, int num_levels, int cw_stride,
+                                         int log_domain_size, const dpf_block* key_seed,
+                                         const uint8_t* party, const dpf_block* cw_seed,
+                                         const uint8_t* cw_left, const uint8_t* cw_right,
+                                         const dpf_aes_key* key_left,
+                                         const dpf_aes_key* key_right,
+                                         const dpf_aes_key* key_value, const dpf_value_desc* desc,
+                                         const dpf_block* value_correction, void* workspace,
+                                         int64_t workspace_bytes, void* out, int64_t out_bytes,
+                                         int accumulate, void* stream) {
+  if (num_keys < 0 || num_keys > INT32_MAX)
+    return fail(kInvalidArgument, "num_keys out of range");
+  if (log_domain_size < 0 || log_domain_size > kSumMaxLogDomain)
+    return fail(kInvalidArgument, "log_domain_size must be in [0, 30]");
+  if (!desc || !key_left || !key_right || !key_value)
+    return fail(kInvalidArgument, "NULL value descriptor or AES key");
+  if (!packed_type_ok(desc))
+    return fail(kUnimplemented,
+                "the packed full-domain sum is implemented for uint8_t, uint16_t, uint32_t, "
+                "uint64_t and XorWrapper of these and of absl::uint128, over a domain of at "
+                "least one full leaf block");
+  const int bits = desc->bits[0];
+  if (num_levels != log_domain_size - log2_elements(bits) || num_levels < 0 ||
+      num_levels > kSumMaxLogDomain - 1)
+    return fail(kInvalidArgument,
+                "num_levels must be log_domain_size - log2(elements per block), in [0, 29]: "
+                "at least one full leaf block");
+  if (cw_stride < num_levels) return fail(kInvalidArgument, "cw_stride < num_levels");
+  if (!out) return fail(kInvalidArgument, "`out` is NULL");
+  if (out_bytes < ((int64_t)16 << num_levels))
+    return fail(kInvalidArgument, "`out` is smaller than 2^log_domain_size elements");
+  return run_sum(num_keys, num_levels, cw_stride, bits, desc->kind[0] == DPF_LEAF_XOR, key_seed,
+                 party, cw_seed, cw_left, cw_right, key_left, key_right, key_value,
+                 value_correction, workspace, workspace_bytes, out, accumulate,
+                 (hipStream_t)stream);
 }

@@ -644,6 +644,48 @@ class DistributedPointFunction:
         _call(self._impl.check_full_domain_sum_args, int(num_keys), bool(batch_matches),
               int(hierarchy_level), out.data_ptr(), out.numel() * out.element_size())
 
+    def evaluate_full_domain_sum_packed_to_device(self, device_batch, hierarchy_level: int, out,
+                                                  accumulate: bool = False, stream=None) -> int:
+        """evaluate_full_domain_sum_to_device for every integer width whose
+        elements fill a leaf block: uint8/16/32/64 summed mod 2^B, XorWrapper of
+        8 to 128 bits XORed.  `out`: a torch device tensor of at least N = 2^n
+        packed elements (N * B / 8 bytes, the layout evaluate_until writes),
+        16-byte aligned; overwritten, or with `accumulate` added (XORed) into
+        element by element.  Returns N.  The 64-bit types give
+        evaluate_full_domain_sum_to_device's bytes; everything else the level
+        could be is UNIMPLEMENTED."""
+        s = stream
+        if s is None:
+            import torch
+            s = torch.cuda.current_stream(out.device)
+        return _call(self._impl.evaluate_full_domain_sum_packed_to_device, device_batch,
+                     int(hierarchy_level), out.data_ptr(), out.numel() * out.element_size(),
+                     bool(accumulate), s.cuda_stream)
+
+    def evaluate_full_domain_sum_packed(self, device_batch, hierarchy_level: int) -> np.ndarray:
+        """evaluate_full_domain_sum_packed_to_device into a fresh vector,
+        returned as a numpy uint8, uint16, uint32 or uint64 array of N elements,
+        or uint64 (N, 2) (low word first) for 128 bits."""
+        raw = _call(self._impl.evaluate_full_domain_sum_packed, device_batch, int(hierarchy_level))
+        size = self.packed_size(int(hierarchy_level))
+        if size == 16:
+            return raw.view(np.uint64).reshape(-1, 2)
+        return raw.view({1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[size])
+
+    def evaluates_full_domain_sum_packed_on_device(self, hierarchy_level: int) -> bool:
+        """Whether evaluate_full_domain_sum_packed_to_device takes this level's
+        value type, domain size and tree level (there is no fallback behind
+        it)."""
+        return self._impl.evaluates_full_domain_sum_packed_on_device(int(hierarchy_level))
+
+    def check_full_domain_sum_packed_args(self, num_keys: int, hierarchy_level: int, out,
+                                          batch_matches: bool = True) -> None:
+        """The host checks of evaluate_full_domain_sum_packed_to_device for a
+        batch of `num_keys` keys, in its order; raises what it would raise.
+        Touches no device and needs no batch."""
+        _call(self._impl.check_full_domain_sum_packed_args, int(num_keys), bool(batch_matches),
+              int(hierarchy_level), out.data_ptr(), out.numel() * out.element_size())
+
     def evaluate_full_domain_sum_sketch_to_device(self, hierarchy_level: int, device_batch,
                                                   weights, sum_out, sketch_out=None,
                                                   accumulate: bool = False, stream=None) -> int:

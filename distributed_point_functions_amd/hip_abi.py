@@ -174,6 +174,9 @@ def load(require_gpu: bool = False):
                              [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I64, P, I, P]),
                             ("dpf_hip_expand_sum_plan",
                              [I64, I, I, ctypes.POINTER(ctypes.c_int64)]),
+                            ("dpf_hip_expand_sum_packed_supported", [P]),
+                            ("dpf_hip_expand_sum_packed",
+                             [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I, P]),
                             ("dpf_hip_expand_sketch_supported", [P]),
                             ("dpf_hip_expand_sketch",
                              [I64, I, I, I, P, P, P, P, P, P, P, P, P, P, I, P, P, I64, P, P, I,
@@ -359,6 +362,13 @@ def expand_sum_supported(desc) -> bool:
     """Whether dpf_hip_expand_sum takes this value type (`desc` None: a NULL
     descriptor; no GPU needed)."""
     return bool(load().dpf_hip_expand_sum_supported(
+        ctypes.byref(desc) if desc is not None else None))
+
+
+def expand_sum_packed_supported(desc) -> bool:
+    """Whether dpf_hip_expand_sum_packed takes this value type (`desc` None: a
+    NULL descriptor; no GPU needed)."""
+    return bool(load().dpf_hip_expand_sum_packed_supported(
         ctypes.byref(desc) if desc is not None else None))
 
 

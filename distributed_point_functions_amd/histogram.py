@@ -42,9 +42,22 @@ def fold(dpf: D.DistributedPointFunction, device_batch, hierarchy_level: int = 0
     """One server's share of the histogram of its batch: a torch int64 device
     tensor of 2^n words holding the uint64 sums.  `out`: the tensor to write
     (or, with `accumulate`, to add into); None makes a fresh one, zeroed when
-    accumulating."""
+    accumulating.  A level of 8-, 16- or 32-bit integers (plain or XorWrapper)
+    or of XorWrapper<uint128> gives its packed elements: torch uint8, int16 or
+    int32 [2^n], or int64 [2^n, 2] (evaluate_full_domain_sum_packed_to_device)."""
     import torch
     n = int(dpf.parameters()[hierarchy_level].log_domain_size)
+    if (not dpf.evaluates_full_domain_sum_on_device(hierarchy_level)
+            and dpf.evaluates_full_domain_sum_packed_on_device(hierarchy_level)):
+        if out is None:
+            shape, dtype = {1: ((1 << n,), torch.uint8), 2: ((1 << n,), torch.int16),
+                            4: ((1 << n,), torch.int32),
+                            16: ((1 << n, 2), torch.int64)}[dpf.packed_size(hierarchy_level)]
+            make = torch.zeros if accumulate else torch.empty
+            out = make(shape, dtype=dtype, device="cuda")
+        dpf.evaluate_full_domain_sum_packed_to_device(device_batch, hierarchy_level, out,
+                                                      accumulate=accumulate, stream=stream)
+        return out
     if out is None:
         make = torch.zeros if accumulate else torch.empty
         out = make(1 << n, dtype=torch.int64, device="cuda")
@@ -58,6 +71,19 @@ def reconstruct(share0, share1, xor: bool) -> np.ndarray:
     a = _host_u64(share0)
     b = _host_u64(share1)
     return a ^ b if xor else a + b
+
+
+def reconstruct_packed(share0, share1, bits: int, xor: bool) -> np.ndarray:
+    """The two servers' packed shares combined element by element: sums mod
+    2^bits, or XOR.  uint8, uint16, uint32 or uint64 [N]; uint64 [N, 2] (low
+    word first) for 128 bits, which only XOR takes."""
+    if bits not in (8, 16, 32, 64, 128) or (bits == 128 and not xor):
+        raise ValueError("bits must be 8, 16, 32 or 64, or 128 with xor")
+    dtype = {8: np.uint8, 16: np.uint16, 32: np.uint32, 64: np.uint64, 128: np.uint64}[bits]
+    a = _host_bits(share0, dtype)
+    b = _host_bits(share1, dtype)
+    r = a ^ b if xor else a + b
+    return r.reshape(-1, 2) if bits == 128 else r.reshape(-1)
 
 
 def fold_checked(dpf: D.DistributedPointFunction, device_batch, weights, hierarchy_level: int = 0,
@@ -109,6 +135,12 @@ def _host_u32(x) -> np.ndarray:
     if hasattr(x, "cpu"):
         x = x.cpu().numpy()
     return np.ascontiguousarray(x).view(np.uint32)
+
+
+def _host_bits(x, dtype) -> np.ndarray:
+    if hasattr(x, "cpu"):
+        x = x.cpu().numpy()
+    return np.ascontiguousarray(x).view(dtype)
 
 
 def _host_u64(x) -> np.ndarray:

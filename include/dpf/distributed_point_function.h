@@ -524,6 +524,51 @@ class DistributedPointFunction {
   // one of this DistributedPointFunction.  Touches no device.
   Status CheckFullDomainSumArgs(int64_t num_keys, bool batch_matches, int hierarchy_level,
                                 const void* device_out, int64_t out_bytes) const;
+  // The full-domain sum for every integer width whose elements fill a leaf
+  // block -- small counters, flag writes and 128-bit payloads without widening
+  // the keys to 64 bits.  With B the bits of T at `hierarchy_level`, E = 128 /
+  // B and y_k as above:
+  //   uintB_t,             B in {8, 16, 32, 64}:      out[i] = sum_k y_k[i] (mod 2^B)
+  //   XorWrapper<uintB_t>, B in {8, 16, 32, 64, 128}: out[i] = XOR_k y_k[i]
+  // `out` is N = 2^n packed little-endian elements of T, N * B / 8 bytes, the
+  // layout EvaluateUntil writes.  A level is taken when its tree level is n -
+  // log2 E (its leaf blocks are full, so n >= log2 E), n <= 30 and the tree has
+  // at most 29 levels (XorWrapper<uint128>: n <= 29).  Everything else --
+  // additive uint128, IntModN, tuples, a domain below one leaf block, a
+  // hierarchy level whose forced tree level leaves blocks partly used -- is
+  // UNIMPLEMENTED; there is no fallback behind this call.  A tree of B-bit
+  // elements is log2(E / 2) levels shallower than the 64-bit one of the same
+  // domain: half the AES at 32 bits, an eighth at 8.  The two 64-bit types
+  // give EvaluateFullDomainSumToDevice's bytes.  `accumulate`, the empty
+  // batch, `stream`, the scratch and the order of the checks (the level, the
+  // type and shape, a null pointer, out_bytes >= N * B / 8, the batch, the
+  // alignment) are that call's.  Returns N.
+  StatusOr<int64_t> EvaluateFullDomainSumPackedToDevice(const DeviceKeyBatch& keys,
+                                                        int hierarchy_level, void* device_out,
+                                                        int64_t out_bytes, bool accumulate,
+                                                        void* stream) const;
+  // The same into a fresh vector of N elements returned to the host.  T must
+  // be the level's value type, as for EvaluateUntil<T>.
+  template <typename T>
+  StatusOr<std::vector<T>> EvaluateFullDomainSumPacked(const DeviceKeyBatch& keys,
+                                                       int hierarchy_level) const {
+    ValueType t = ToValueType<T>();
+    auto packed = EvaluateFullDomainSumPackedBytes(keys, hierarchy_level, &t);
+    if (!packed.ok()) return packed.status();
+    return Unpack<T>(hierarchy_level, *packed);
+  }
+  // The packed bytes of the above; `requested_type`, if given, must equal the
+  // level's value type.
+  StatusOr<std::vector<uint8_t>> EvaluateFullDomainSumPackedBytes(
+      const DeviceKeyBatch& keys, int hierarchy_level, const ValueType* requested_type) const;
+  // True when `hierarchy_level` exists and its value type, domain size and
+  // tree level are ones EvaluateFullDomainSumPackedToDevice takes.
+  bool EvaluatesFullDomainSumPackedOnDevice(int hierarchy_level) const;
+  // EvaluateFullDomainSumPackedToDevice's argument checks, in its order and
+  // with its messages, for a batch of num_keys keys that is (`batch_matches`)
+  // or is not one of this DistributedPointFunction.  Touches no device.
+  Status CheckFullDomainSumPackedArgs(int64_t num_keys, bool batch_matches, int hierarchy_level,
+                                      const void* device_out, int64_t out_bytes) const;
   // Checked private histograms: the full-domain sum of a key batch over a
   // field, with every key's linear sketches taken in the same launch (the
   // per-key vectors exist nowhere else).  For T = IntModN<uint32_t, N_0> or

@@ -827,6 +827,45 @@ int dpf_hip_expand_sum(int64_t num_keys, int num_levels, int cw_stride, int log_
  * [0, 29], num_cus outside [1, 65536]. */
 int dpf_hip_expand_sum_plan(int64_t num_keys, int tree_depth, int num_cus, int64_t out[6]);
 
+/* ---- the full-domain sum for packed 8/16/32/64-bit counters and 128-bit XOR ---
+ * No reference counterpart.  dpf_hip_expand_sum for every integer width whose
+ * elements fill a leaf block: with B the element's bits, E = 128 / B elements
+ * per block, n = log_domain_size, N = 2^n and y_k as above,
+ *   uintB_t,             B in {8, 16, 32, 64}:      out[i] = sum_{k<K} y_k[i] (mod 2^B)
+ *   XorWrapper<uintB_t>, B in {8, 16, 32, 64, 128}: out[i] = XOR_{k<K} y_k[i]
+ * `out` is N packed little-endian elements, N * B / 8 bytes, the layout
+ * EvaluateUntil writes; out_bytes is its size.  The tree has num_levels = n -
+ * log2 E levels (a 32-bit level is one level shallower than a 64-bit one of the
+ * same domain, 8 bits three: an eighth of the AES), so the domain holds at
+ * least one full leaf block, n >= log2 E.  value_correction holds E blocks per
+ * key.  The plan, the workspace and its size are dpf_hip_expand_sum's, by
+ * num_levels (dpf_hip_expand_sum_plan, dpf_hip_expand_sum_workspace_bytes);
+ * the two 64-bit types run the kernels dpf_hip_expand_sum launches and give
+ * its bytes.  Additive 32-bit elements are summed by native 32-bit atomics,
+ * 16- and 8-bit ones by a compare-exchange loop on the 64-bit word (carries
+ * stop at element tops); every XOR by 64-bit atomic XOR.
+ * Checks, all before any device call, the first failing one reported:
+ *   1. num_keys outside [0, 2^31 - 1], log_domain_size outside [0, 30]: 3;
+ *   2. NULL desc or AES keys: 3;
+ *   3. a value type dpf_hip_expand_sum_packed_supported refuses (additive
+ *      128-bit, IntModN, tuples): 12 UNIMPLEMENTED (there is no fallback
+ *      behind this call);
+ *   3a. num_levels != log_domain_size - log2 E, or outside [0, 29] (a domain
+ *      below one leaf block; XorWrapper<uint128> at n = 30): 3;
+ *   4. cw_stride < num_levels: 3;
+ *   5. NULL out, then out_bytes < N * B / 8: 3;
+ *   6. to 9. as dpf_hip_expand_sum. */
+int dpf_hip_expand_sum_packed_supported(const dpf_value_desc* desc);
+int dpf_hip_expand_sum_packed(int64_t num_keys, int num_levels, int cw_stride,
+                              int log_domain_size, const dpf_block* key_seed,
+                              const uint8_t* party, const dpf_block* cw_seed,
+                              const uint8_t* cw_left, const uint8_t* cw_right,
+                              const dpf_aes_key* key_left, const dpf_aes_key* key_right,
+                              const dpf_aes_key* key_value, const dpf_value_desc* desc,
+                              const dpf_block* value_correction, void* workspace,
+                              int64_t workspace_bytes, void* out, int64_t out_bytes,
+                              int accumulate, void* stream);
+
 /* ---- checked private histograms: fused field sum and per-key sketches -------
  * No reference counterpart.  dpf_hip_expand_sum over a field, with the linear
  * sketches of every key's own vector (dpf_hip_sketch_rows' definition) taken
